@@ -253,10 +253,15 @@ def parse_args(argv=None):
                     help="FUNCTIONAL CHECK ONLY: every rank uses device 0 (a 1-GPU box); the line is labelled a non-measurement")
     ap.add_argument("--n1-value", type=float, default=None,
                     help="the N=1 `value` of this same workload (e.g. from BENCH_rNN.json): adds efficiency_vs_n1 = value / (N * n1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_BUDGET_BYTES >> 20} MB in all (larger outputs: a fixed seeded sample, described in DIR/manifest.json)")
     ap.add_argument("--selftest-hostsim", action="store_true",
                     help="FUNCTIONAL CHECK ONLY (no GPU): the rank plumbing on the CPU host simulation of the kernel backend "
                          "(tests/hostsim, tiny backbone, gloo); the line is labelled a non-measurement")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.clips is not None and args.ilaf_clips is not None and args.clips != args.ilaf_clips:
         ap.error("--clips and --ilaf_clips both given with different values")
     if args.workload == "ilaf":
@@ -264,6 +269,57 @@ def parse_args(argv=None):
     elif args.clips is None:      # configs[2]: batch = 8; configs[3]: batch 64 over 8 GPUs = 8 per GPU; configs[1]: batch = 4
         args.clips = 8 if args.workload in ("aens", "config2") else CLIPS_PER_GPU
     return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_WHOLE_BYTES = 1 << 20        # arrays up to this size are always written whole
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: write {name: float32 / float64 array} as out_dir/<name>.npy, within DUMP_BUDGET_BYTES.  Small arrays are written
+    whole; when the rest does not fit, each large array is replaced by the elements at a fixed seeded set of flat indices,
+    `np.sort(np.random.default_rng(DUMP_SEED).choice(size, n, replace=False))` (the same for every build, so two dumps compare element
+    for element); out_dir/manifest.json records each array's full shape and whether it was sampled."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes <= DUMP_WHOLE_BYTES)
+    large = sum(a.nbytes for a in arrays.values() if a.nbytes > DUMP_WHOLE_BYTES)
+    frac = min(1.0, (DUMP_BUDGET_BYTES - small) / large) if large else 1.0
+    manifest = {}
+    for name, a in arrays.items():
+        entry = {"shape": list(a.shape), "dtype": a.dtype.name, "sampled": False}
+        if a.nbytes > DUMP_WHOLE_BYTES and frac < 1.0:
+            n = int(a.size * frac)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+            entry.update(sampled=True, n=n, seed=DUMP_SEED,
+                         indices="np.sort(np.random.default_rng(seed).choice(prod(shape), n, replace=False)) into the flattened array")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        manifest[name] = entry
+    with open(os.path.join(out_dir, "manifest.json"), "w") as fh:
+        json.dump(manifest, fh, indent=1)
+
+
+def step_outputs(workload, result, atk, lane_results=None, lanes=None):
+    """What a caller of the timed path holds after its last step: the adversarial clips it returned (AENS: plus its per-step cost
+    record) and the attack's per-step costs; ILAF: the same for every clip stream."""
+    import numpy as np
+
+    def host(t):
+        return t.detach().float().cpu().numpy()
+    if workload == "ilaf":
+        out = {}
+        for k, (lane, res) in enumerate(zip(lanes, lane_results)):
+            out[f"adv_stream{k}"] = host(res)
+            out[f"costs_stream{k}"] = np.asarray(lane[0].last_costs, dtype=np.float64)
+        return out
+    if workload == "aens":
+        adv, _, cost_saved = result
+        return {"adv": host(adv), "cost_saved": np.asarray(cost_saved, dtype=np.float64),
+                "costs": np.asarray(atk.last_costs, dtype=np.float64), "weights": np.stack(atk.weights).astype(np.float32)}
+    return {"adv": host(result), "costs": np.asarray(atk.last_costs, dtype=np.float64)}
 
 
 def under_launcher():
@@ -446,8 +502,10 @@ def selftest_hostsim(args):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        atk(vids, lab, names)
+        result = atk(vids, lab, names)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(args.workload, result, atk))
     if dist is not None:
         dist.barrier()
     elapsed, per_rank = reduce_max(dist, elapsed, dev)
@@ -463,6 +521,7 @@ def selftest_hostsim(args):
             extra["aens_weights_identical_on_all_ranks"] = bool(all(torch.equal(e, every[0]) for e in every))
     line = {"metric": "SELFTEST (host simulation, not a measurement)", "value": round(args.steps * b * f * world / elapsed, 3),
             "unit": "adversarial frames/s", "n_gpus": world, "steps": args.steps, "warmup": 0, "data": "synthetic",
+            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "ranks_proved_by_allreduce": {"sum_of_rank_ids": rank_sum, "expected": world * (world - 1) // 2},
             "per_gpu": [round(args.steps * b * f / t, 3) for t in per_rank], "config": {"workload": f"selftest {args.workload}"},
             "cpu_affinity_rank0": CPU_PIN, **extra}
@@ -570,16 +629,18 @@ def run_rank(args, framework_child=None):
             a_.plan_for(v_)                   # under the other streams' traffic picked different kernels per stream)
         torch.cuda.synchronize()
 
-        def lane_calls(lane, reps):
-            a, v, o, st = lane
+        lane_results = [None] * len(lanes)            # each stream's last return value (--dump-outputs)
+
+        def lane_calls(k, reps):
+            a, v, o, st = lanes[k]
             torch.cuda.set_device(dev)                    # per-thread state (a new thread starts on device 0)
             with torch.cuda.stream(st):
                 for _ in range(reps):
-                    a(v, o, labels, names)
+                    lane_results[k] = a(v, o, labels, names)
                 st.synchronize()
 
         def atk(v, l, n, reps=1):
-            ths = [threading.Thread(target=lane_calls, args=(ln, reps)) for ln in lanes]
+            ths = [threading.Thread(target=lane_calls, args=(k, reps)) for k in range(len(lanes))]
             for t in ths:
                 t.start()
             for t in ths:
@@ -620,12 +681,17 @@ def run_rank(args, framework_child=None):
         atk(videos, labels, names, reps=args.steps)       # every stream runs `steps` calls back to back
     else:
         for _ in range(args.steps):
-            atk(videos, labels, names)
+            result = atk(videos, labels, names)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
     own_elapsed = elapsed
     elapsed, per_rank_s = reduce_max(dist, elapsed, dev)
+    if args.dump_outputs and rank == 0:       # before any further call reuses the attack's buffers
+        if args.workload == "ilaf":
+            dump_outputs(args.dump_outputs, step_outputs("ilaf", None, None, lane_results, lanes))
+        else:
+            dump_outputs(args.dump_outputs, step_outputs(args.workload, result, atk))
     if timing_outside:                      # one stream, instrumented
         eng.timing_enable(True)
         _ilaf(videos, ori, labels, names); eng.timing_collect()      # event pool

@@ -1,6 +1,9 @@
 """Helpers shared by the parity tests: load a golden fixture (tests/golden/*.npz, produced by
 oracle/make_golden.py from the imported reference classes) and rebuild its inputs."""
 import ast
+import functools
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -27,6 +30,27 @@ def load(name):
         fx["models"] = [str(m) for m in fx["models"]]
         fx["kind"], fx["prec"] = str(fx["kind"]), str(fx["prec"])
     return fx
+
+
+@functools.lru_cache(maxsize=None)
+def ref_live(group):
+    """Arrays the imported reference classes returned for the cases of oracle/make_ref_live.py: `ref_live_<group>.npz`
+    (group: i2v / aens / sign / video)."""
+    z = np.load(os.path.join(GOLDEN, f"ref_live_{group}.npz"), allow_pickle=False)
+    return {k: z[k] for k in z.files}
+
+
+@functools.lru_cache(maxsize=None)
+def ref_live_json():
+    """The reference's command lines, LoopPadding selections, labels and tensor digests (oracle/make_ref_live.py)."""
+    with open(os.path.join(GOLDEN, "ref_live.json")) as fh:
+        return json.load(fh)
+
+
+def digest(t):
+    """dtype, shape and sha256 of a tensor's bytes: bit-identity with a large reference tensor without storing it."""
+    a = np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+    return f"{a.dtype.str}{list(a.shape)}:{hashlib.sha256(a.tobytes()).hexdigest()}"
 
 
 def videos_of(fx, dtype=torch.float32):

@@ -224,22 +224,15 @@ def test_run_image_guided_plan():
 
 
 def test_run_image_guided_matches_the_reference_commands(monkeypatch, capsys):
-    """The reference's own `run_image_guided.py` executed with `os.system` recording instead of running: its formatted
-    command lines (templates `:5-29`, loops `:44-100`), in order, against `plan()` flag for flag -- and against what
-    `--dry_run` prints."""
-    import runpy
+    """The reference's own `run_image_guided.py` executed with `os.system` recording instead of running (oracle/make_ref_live.py
+    kept what it issued, tests/golden/ref_live.json): its formatted command lines (templates `:5-29`, loops `:44-100`), in order,
+    against `plan()` flag for flag -- and against what `--dry_run` prints."""
     import sys
-    from oracle import ref_shim
-    path = os.path.join(ref_shim.REFERENCE_DIR, "run_image_guided.py")
-    if not os.path.isfile(path):
-        pytest.skip("reference not present")
+    from tests import golden_util as gu
     import run_image_guided
+    recorded = gu.ref_live_json()["run_image_guided"]
     for gpu, bs in (("0", 1), ("3", 4)):
-        issued = []
-        monkeypatch.setattr(os, "system", lambda c: issued.append(c.split()) or 0)
-        monkeypatch.setattr(sys, "argv", ["run_image_guided.py", "--gpu", gpu, "--batch_size", str(bs)])
-        runpy.run_path(path, run_name="__main__")
-        monkeypatch.undo()
+        issued = recorded[f"{gpu}_{bs}"]
         ours = [c for pair in run_image_guided.plan(gpu, bs) for c in pair]
         assert len(issued) == len(ours) == 2 * 59
         for ref, mine in zip(issued, ours):
@@ -444,6 +437,42 @@ def test_bench_gpus_n_spawns_n_ranks():
     code, lines, err = _bench(["--gpus", "1", "--selftest-hostsim", "--steps", "1", "--n1-value", "1000"])
     assert code == 0 and lines[0]["n_gpus"] == 1
     assert abs(lines[0]["efficiency_vs_n1"] - lines[0]["value"] / 1000) < 1e-3 and lines[0]["cpu_affinity_rank0"] is None
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned (float32 / float64 .npy), the same for the same arguments run to run;
+    `--steps` sets the timed steps and the line carries `ms_per_step`.  Here on the host simulation."""
+    for workload in ("i2v", "aens"):
+        dumps = []
+        for k in range(2):
+            d = tmp_path / f"{workload}{k}"
+            code, lines, err = _bench(["--gpus", "1", "--selftest-hostsim", "--steps", "2", "--workload", workload, "--dump-outputs", str(d)])
+            assert code == 0, err
+            assert lines[0]["steps"] == 2 and lines[0]["ms_per_step"] > 0
+            man = json.loads((d / "manifest.json").read_text())
+            arrs = {n: np.load(d / (n + ".npy")) for n in man}
+            assert "adv" in arrs and "costs" in arrs and list(arrs["adv"].shape) == man["adv"]["shape"] == [2, 3, 2, 32, 32]
+            assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+            assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+            dumps.append(arrs)
+        assert dumps[0].keys() == dumps[1].keys()
+        for n in dumps[0]:
+            assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
+def test_bench_dump_outputs_samples_large_arrays(tmp_path):
+    """Outputs beyond the 64 MB budget are cut to a fixed seeded sample of their elements; small arrays stay whole."""
+    import bench
+    big = np.arange(20 << 20, dtype=np.float32).reshape(5, 4 << 20)          # 80 MB
+    small = np.arange(10, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path), {"big": big, "small": small})
+    man = json.loads((tmp_path / "manifest.json").read_text())
+    got = np.load(tmp_path / "big.npy")
+    assert man["big"]["sampled"] and man["big"]["shape"] == [5, 4 << 20] and not man["small"]["sampled"]
+    assert got.nbytes + small.nbytes <= 64 << 20 and got.dtype == np.float32 and got.size == man["big"]["n"]
+    idx = np.sort(np.random.default_rng(man["big"]["seed"]).choice(big.size, man["big"]["n"], replace=False))
+    assert np.array_equal(got, big.reshape(-1)[idx])
+    assert np.array_equal(np.load(tmp_path / "small.npy"), small)
 
 
 def test_bench_eight_ranks_aens_weights_follow_the_global_batch():

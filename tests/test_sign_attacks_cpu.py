@@ -5,7 +5,6 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ref_shim
 from tests import golden_util as gu
 from tests.hostsim_util import hostsim_engine
 
@@ -29,10 +28,8 @@ def test_sign_attack_classes_match_reference(cls):
     assert (adv != ref).float().mean() < 1e-3
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference checkout not present")
-def test_ilaf_matches_reference_live():
-    ia = ref_shim.import_reference("image_attacks")
-    import i2v_amd.sign_attacks as sa
+def ilaf_case():
+    """(model, adversarial start clip, clean clip) of the ILAF comparison (same construction in oracle/make_ref_live.py)."""
     torch.manual_seed(0)
     model = torch.nn.Sequential(torch.nn.Conv3d(3, 6, 3, padding=1), torch.nn.ReLU(), torch.nn.Conv3d(6, 4, 3, padding=1),
                                 torch.nn.AdaptiveAvgPool3d(1), torch.nn.Flatten())
@@ -40,15 +37,19 @@ def test_ilaf_matches_reference_live():
     gen = torch.Generator().manual_seed(9)
     ori = gu.videos_of({"clip_u8": torch.randint(0, 256, (1, 3, 4, 16, 16), generator=gen, dtype=torch.uint8).numpy()})
     adv0 = gu.videos_of({"clip_u8": torch.randint(0, 256, (1, 3, 4, 16, 16), generator=gen, dtype=torch.uint8).numpy()})
-    adv0 = ori + 0.1 * (adv0 - ori)
-    with ref_shim.quiet():
-        ref_atk = ia.ILAF(model, "tpn", step_size=0.005, steps=3)
-        ref = ref_atk(adv0.clone(), ori.clone(), torch.zeros(1, dtype=torch.long), ["v"]).detach()
+    return model, ori + 0.1 * (adv0 - ori), ori
+
+
+def test_ilaf_matches_reference_live():
+    """Against the clip and costs the reference's ILAF returned on the same model and clips (oracle/make_ref_live.py)."""
+    import i2v_amd.sign_attacks as sa
+    model, adv0, ori = ilaf_case()
+    ref_arr = gu.ref_live("sign")
+    ref, c_ref = torch.from_numpy(ref_arr["ilaf/adv"]), ref_arr["ilaf/cost"]
     ours = sa.ILAF(model, "tpn", step_size=0.005, steps=3, engine=hostsim_engine())
     got = ours(adv0.clone(), ori.clone(), torch.zeros(1, dtype=torch.long), ["v"]).detach()
     assert got.shape == ref.shape
     assert (got - ref).abs().max() < 1e-6
-    assert ours.loss_info["v"][0]["cost"] == ref_atk.loss_info["v"][0]["cost"]
+    assert float(ours.loss_info["v"][0]["cost"]) == c_ref[0]
     c_ours = np.array([float(ours.loss_info["v"][i]["cost"]) for i in range(3)])
-    c_ref = np.array([float(ref_atk.loss_info["v"][i]["cost"]) for i in range(3)])
     np.testing.assert_allclose(c_ours, c_ref, rtol=1e-3)

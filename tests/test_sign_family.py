@@ -1,7 +1,7 @@
 """CPU (host simulation backend): the DI- / TI- / TI-3D- / SI-FGSM drop-in classes (`base_attacks.py:342-675`) against what the
 imported reference classes returned on the same toy video model with the same seeds (fixture `sign_family.npz`,
-oracle/make_golden.py:run_sign_family), their device kernels against torch, and -- when the reference checkout is present --
-live against the reference classes."""
+oracle/make_golden.py:run_sign_family), their device kernels against torch, and against further reference runs kept in
+`ref_live_sign.npz` (oracle/make_ref_live.py)."""
 import random
 
 import numpy as np
@@ -10,7 +10,6 @@ import torch
 import torch.nn.functional as F
 
 from i2v_amd import sign_attacks as sa
-from oracle import ref_shim
 from oracle.make_golden import SIGN_FAMILY
 from tests import golden_util as gu
 from tests.hostsim_util import hostsim_engine
@@ -104,14 +103,11 @@ def test_smoothing_passes_equal_the_reference_convolutions():
     assert (got3 - want3).abs().max() <= 3e-6 * want3.abs().max()
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference checkout not present")
 @pytest.mark.parametrize("cls", ["TIFGSM", "SIM"])
 def test_sign_family_live_against_reference(cls):
-    ba = ref_shim.import_reference("base_attacks")
     fx = gu.load("sign_family")
     vid = gu.videos_of({"clip_u8": fx["clip_u8"]})
-    with ref_shim.quiet():
-        ref = getattr(ba, cls)(toy_video_model(), epsilon=16 / 255, steps=2, momentum=True)(vid.clone(), torch.tensor([2])).detach()
+    ref = torch.from_numpy(gu.ref_live("sign")[f"sign_family/{cls}/adv"])
     import base_attacks
     got = getattr(base_attacks, cls)(toy_video_model(), epsilon=16 / 255, steps=2, momentum=True, engine=hostsim_engine())(vid.clone(), torch.tensor([2]))
     assert float((got != ref).float().mean()) < 5e-3
@@ -159,13 +155,17 @@ def test_sgm_tap_match_reference_fixture(cls, kw):
         assert atk.hooked == ["relu", "res_layers.0.1.relu", "res_layers.1.1.relu"]           # :511-513 on this model
 
 
+def sgm_input():
+    """(clip, label) of the SGM gradient comparison (same input in oracle/make_ref_live.py)."""
+    return torch.randn(1, 3, 8, 32, 32, generator=torch.Generator().manual_seed(2)) * 0.5, torch.tensor([1])
+
+
 def test_sgm_gain_is_the_reference_hook():
-    """One gradient, hook by hook: the repo's output-gradient gain against the reference's own `register_backward_hook` on the ReLU
-    modules (live; skipped without the reference checkout), and against gamma = 1 (no effect)."""
+    """One gradient, hook by hook: the repo's output-gradient gain against the gradient through the reference's own
+    `register_backward_hook` on the ReLU modules (tests/golden/ref_live_sign.npz), and against gamma = 1 (no effect)."""
     import base_attacks
     from oracle import video_models
-    x = torch.randn(1, 3, 8, 32, 32, generator=torch.Generator().manual_seed(2)) * 0.5
-    lab = torch.tensor([1])
+    x, lab = sgm_input()
 
     def grad_of(model):
         xx = x.clone().requires_grad_(True)
@@ -178,12 +178,7 @@ def test_sgm_gain_is_the_reference_hook():
     base_attacks.SGM(m2, gamma=0.5, engine=hostsim_engine())
     mine = grad_of(m2)
     assert not torch.allclose(mine, plain, rtol=1e-3, atol=0)
-    if not ref_shim.available():
-        pytest.skip("reference checkout not present")
-    m3 = video_models.tiny_stage_classifier()
-    with ref_shim.quiet():
-        ref_shim.import_reference("base_attacks").SGM(m3, gamma=0.5)
-    theirs = grad_of(m3)
+    theirs = torch.from_numpy(gu.ref_live("sign")["sgm_gain/grad"])
     assert torch.allclose(mine, theirs, rtol=1e-5, atol=1e-7 * float(theirs.abs().max()))
 
 

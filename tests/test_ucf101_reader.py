@@ -1,7 +1,7 @@
 """N4, UCF-101 half, the part in FRONT of the device transform: jpg frame folders -> clip list -> LoopPadding(32) -> Pillow decoding
 (`/root/reference/dataset_ucf101.py:14-45,52-99,113-126`, `transforms_ucf101.py:23-40`), `i2v_amd.clips.ucf101_*`, and the whole
-loader (reader + `Engine.clip_resample_crop`) against the oracle's transform of independently decoded frames -- bit for bit -- and,
-where /root/reference exists, against the reference's OWN `attack_ucf101` dataset object on the same folder."""
+loader (reader + `Engine.clip_resample_crop`) against the oracle's transform of independently decoded frames -- bit for bit -- and
+against what the reference's OWN `attack_ucf101` dataset object returned on the same folder (tests/golden/ref_live.json)."""
 import json
 import os
 import pickle
@@ -12,7 +12,8 @@ import torch
 from PIL import Image
 
 from i2v_amd import clips
-from oracle import ref_shim, restate
+from oracle import restate
+from tests import golden_util as gu
 
 
 def write_dataset(root, durations=(40, 5, 33, 12), hw=(60, 80), seed=3):
@@ -52,12 +53,12 @@ def test_loop_padding_quirks():
     assert clips.loop_padding([1], 4) == []                                                   # nothing to cycle through
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="/root/reference is absent")
 def test_loop_padding_equals_the_reference_class():
-    tr = ref_shim.import_reference("transforms_ucf101")
+    """Against the selections the reference's own `LoopPadding(size)` returned (oracle/make_ref_live.py)."""
+    want = gu.ref_live_json()["loop_padding"]
     for n in (0, 1, 2, 3, 5, 16, 31, 32, 33, 34, 100):
         for size in (1, 4, 32):
-            assert clips.loop_padding(list(range(1, n + 1)), size) == tr.LoopPadding(size)(list(range(1, n + 1))), (n, size)
+            assert clips.loop_padding(list(range(1, n + 1)), size) == want[f"{n}_{size}"], (n, size)
 
 
 def test_clip_list_and_index_files(tmp_path):
@@ -126,24 +127,18 @@ def test_whole_loader_bit_exact_on_the_device(tmp_path):
     whole_loader(eng, tmp_path, frames=32, hw=224)
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="/root/reference is absent")
-def test_reader_equals_the_reference_dataset_object(tmp_path, monkeypatch):
+def test_reader_equals_the_reference_dataset_object(tmp_path):
     """The reference's own `attack_ucf101` (`dataset_ucf101.py:52-99`) with its `test_transform()` (:113-126), run in a directory
-    holding `./test01_setting.txt` and `./used_idxs.pkl` as it expects, on the same jpg folders: item by item the clip tensor and the
-    label equal reader + oracle transform (and so, by the tests above, reader + device kernel)."""
+    holding `./test01_setting.txt` and `./used_idxs.pkl` as it expects, on the same jpg folders (oracle/make_ref_live.py kept each
+    item's label and the digest of its clip tensor): item by item the clip tensor and the label equal reader + oracle transform (and
+    so, by the tests above, reader + device kernel)."""
     image_root, setting, used, rows = write_dataset(str(tmp_path), durations=(36, 7, 33), hw=(240, 320))
-    ds_mod = ref_shim.import_reference("dataset_ucf101")
-    monkeypatch.setattr(ds_mod, "UCF_IMAGE_ROOT", image_root)
-    monkeypatch.chdir(tmp_path)
-    spa, tem = ds_mod.test_transform()
-    ds = ds_mod.attack_ucf101(spatial_transform=spa, temporal_transform=tem, get_loader=lambda: __import__("functools").partial(
-        ds_mod.video_loader, image_loader=ds_mod.pil_loader))
+    ds = gu.ref_live_json()["ucf101_dataset_items"]
     ours = list(clips.ucf101_batches(1, setting, image_root, used, frames=32, workers=0))
     assert len(ds) == len(ours) == 3
     for i in range(3):
-        clip, target = ds[i]
-        assert target == int(ours[i][1][0])
-        assert torch.equal(restate.ucf101_transform(ours[i][0].numpy(), 224, 224)[0], clip), i
+        assert ds[i]["target"] == int(ours[i][1][0])
+        assert gu.digest(restate.ucf101_transform(ours[i][0].numpy(), 224, 224)[0]) == ds[i]["clip_digest"], i
 
 
 def test_image_main_ucf101_reads_frame_folders(tmp_path, monkeypatch):

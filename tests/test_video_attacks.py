@@ -1,5 +1,6 @@
 """`video_attacks.TemporalTranslation` (`/root/reference/video_attacks.py:14-229`; what `attack.py --attack_type video` runs):
-live against the imported reference class on one and the same torch classifier (CPU; skipped where /root/reference is absent),
+against what the imported reference class returned on one and the same torch classifier (CPU; tests/golden/ref_live_video.npz,
+captured by oracle/make_ref_live.py),
 and with the NATIVE classifier against the class driving a float64 torch module -- host simulation here, HIP kernels in the
 `gpu`-marked twins."""
 import os
@@ -9,10 +10,8 @@ import pytest
 import torch
 
 from i2v_amd import sign_attacks, video_attacks as va
-from oracle import ref_shim
+from tests import golden_util as gu
 from tests.test_native_classifier import torch_classifier
-
-needs_ref = pytest.mark.skipif(not ref_shim.available(), reason="/root/reference is absent")
 
 
 class F32(torch.nn.Module):
@@ -25,32 +24,30 @@ class F32(torch.nn.Module):
         return self.net(x).float()
 
 
-@needs_ref
 @pytest.mark.parametrize("mode,kernlen", [("gaussian", 15), ("gaussian", 5), ("linear", 7), ("random", 9)])
 def test_temporal_kernels_match_reference(mode, kernlen):
-    ref = ref_shim.import_reference("video_attacks").TemporalTranslation
-    fn = {"gaussian": ref._initial_kernel_gaussian, "linear": ref._initial_kernel_linear, "random": ref._initial_kernel_uniform}[mode]
-    want = fn(None, kernlen).astype(np.float32)
+    want = gu.ref_live("video")[f"temporal_kernel/{mode}_{kernlen}"]
     got = va.TemporalTranslation._temporal_kernel(mode, kernlen).astype(np.float32)
     assert np.array_equal(got, want)
 
 
-@needs_ref
+def translation_case(move_type, momentum, weight, kernlen):
+    """(float32 classifier module, params, clip, labels) of the TemporalTranslation comparison (same in oracle/make_ref_live.py)."""
+    thw, K = (32, 24, 24), 5
+    _, net = torch_classifier("i3d_resnet50", thw, 4, K)
+    params = {"kernlen": kernlen, "momentum": momentum, "weight": weight, "move_type": move_type, "kernel_mode": "gaussian"}
+    vid = torch.randn(1, 3, *thw, generator=torch.Generator().manual_seed(3)) * 0.5
+    return F32(net).eval(), params, vid, torch.tensor([2])
+
+
 @pytest.mark.parametrize("move_type,momentum,weight,kernlen", [("adj", False, 1.0, 5), ("adj", True, 0.4, 5), ("large", False, 0.7, 15)])
 def test_temporal_translation_matches_reference(move_type, momentum, weight, kernlen):
     """Same float32 classifier module on both sides; ours mixes the gradients and takes the step through the C ABI (host
     simulation).  The reference's 1 x D matmul may add in another order than the kernel's fmaf chain, so a few pixels whose
     mixed gradient is ~0 may step the other way."""
     from tests.hostsim_util import hostsim_engine
-    refmod = ref_shim.import_reference("video_attacks")
-    thw, K = (32, 32, 32), 5
-    _, net = torch_classifier("i3d_resnet50", thw, 4, K)
-    model = F32(net).eval()
-    params = {"kernlen": kernlen, "momentum": momentum, "weight": weight, "move_type": move_type, "kernel_mode": "gaussian"}
-    vid = torch.randn(1, 3, *thw, generator=torch.Generator().manual_seed(3)) * 0.5
-    labels = torch.tensor([2])
-    with ref_shim.quiet():
-        want = refmod.TemporalTranslation(model, dict(params), steps=3)(vid.clone(), labels)
+    model, params, vid, labels = translation_case(move_type, momentum, weight, kernlen)
+    want = torch.from_numpy(gu.ref_live("video")[f"temporal_translation/{move_type}_{momentum}_{weight}_{kernlen}"])
     got = va.TemporalTranslation(model, dict(params), steps=3, engine=hostsim_engine())(vid.clone(), labels)
     assert got.shape == want.shape == vid.shape
     same = float(((got - want).abs() < 1e-6).float().mean())
