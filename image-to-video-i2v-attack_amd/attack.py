@@ -10,7 +10,8 @@ artefacts per clip.  The update rule runs in `libi2v_hip.so` (`i2v_sign_step_f32
 cross-entropy gradient are PyTorch, exactly as in the reference -- gluoncv's Kinetics-400 models are not vendored, so
 the classifier comes from a factory like the evaluator's (`reference.py`): `--model_factory pkg.module:function`,
 a callable `name -> torch.nn.Module` on normalised (b,3,f,h,w) clips; default `reference:proxy`.
-`OPT_PATH` is `$I2V_OPT_PATH`; clips come from `i2v_amd.clips` (synthetic or `--clip_dir`)."""
+`OPT_PATH` is `$I2V_OPT_PATH`; clips come from `i2v_amd.clips` (synthetic, `--clip_dir`, or `--video_dir` of whole decoded videos
+through the reference's frame selection -- its attack.py:72 uses the same loader as image_main.py)."""
 import argparse
 import importlib
 import os
@@ -19,6 +20,7 @@ import numpy as np
 import torch
 
 import base_attacks
+import image_main
 import video_attacks
 from i2v_amd import clips
 
@@ -60,7 +62,9 @@ def arg_parse(argv=None):
     parser.add_argument("--num_clips", type=int, default=400)
     parser.add_argument("--frames", type=int, default=32)
     parser.add_argument("--hw", type=int, default=224)
+    image_main.add_video_flags(parser)
     args = parser.parse_args(argv)
+    image_main.check_video_flags(parser, args)
     args.adv_path = os.path.join(OPT_PATH, "{}-{}-{}-{}".format(args.model, args.attack_method, args.step, args.file_prefix))
     os.makedirs(args.adv_path, exist_ok=True)
     return args
@@ -90,12 +94,17 @@ def main(argv=None):
         print(spe_params)                                                                       # UnboundLocalError for any other name, as there
         attack_method = getattr(video_attacks, args.attack_method)(model, params=spe_params, steps=args.step)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    total = clips.num_batches(args.batch_size, args.anno, args.clip_dir, args.num_clips)
-    for step, (val_batch, val_label, _) in enumerate(clips.batches(args.batch_size, args.anno, args.clip_dir, args.frames,
-                                                                    args.hw, args.num_clips)):
+    if args.video_dir:
+        total, source = image_main.video_source(args)
+    else:
+        total = clips.num_batches(args.batch_size, args.anno, args.clip_dir, args.num_clips)
+        source = clips.batches(args.batch_size, args.anno, args.clip_dir, args.frames, args.hw, args.num_clips)
+    for step, item in enumerate(source):
         if step % world != rank:
             continue
+        *data, val_label, _ = item
         print("Running {}, {}/{}".format(args.attack_method, step + 1, total))
+        val_batch = image_main.video_transform(tuple(data), args.hw) if len(data) == 2 else data[0]
         val_batch, val_label = val_batch.to(dev), val_label.to(dev)
         adv_batches = attack_method(val_batch, val_label % args.num_classes)
         val_batch = val_batch.detach()

@@ -43,6 +43,9 @@ static int fail(const char* fmt, ...) {
     return 1;
 }
 
+// the error slot of i2v_last_error() for C entry points defined in other translation units (i2v_loader.hip)
+int i2v_api_fail(const char* msg) { return fail("%s", msg); }
+
 #define CHECK_BE(expr)                                                            \
     do {                                                                          \
         if ((expr) != 0) return fail("%s: %s", #expr, be_error() ? be_error() : "backend error"); \

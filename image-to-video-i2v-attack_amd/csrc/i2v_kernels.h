@@ -17,6 +17,7 @@ int  be_d2d_2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t 
                i2v_stream_t s);                                               // async strided copy
 int  be_memset0(void* p, size_t bytes, i2v_stream_t s);
 const char* be_error();
+int  i2v_api_fail(const char* msg);                                          // sets i2v_last_error() (i2v_engine.cpp), returns 1
 // timing instrumentation (bench.py roofline): stream-ordered event pairs around a launch
 void* be_event_create();
 void be_event_destroy(void* ev);

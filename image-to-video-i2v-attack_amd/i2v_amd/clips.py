@@ -1,10 +1,13 @@
 """Clip sources for the CLI.  The reference decodes Kinetics-400 mp4s with decord
-(`/root/reference/datasets.py`, out of scope: SURVEY.md 8(f) N4); here a batch is either
+(`/root/reference/datasets.py`; mp4 decoding is out of scope: SURVEY.md 8(f) N4); here a batch is either
 
   * synthetic: 8-bit uniform-noise clips seeded by the sample's row index, labelled
-    from the reference's sample list format `path,gt_label,clip_index`, or
+    from the reference's sample list format `path,gt_label,clip_index`,
   * a directory of `{label}-ori.npy` float32 (3,32,224,224) normalised clips (the format the
-    reference's own `attack.py` writes next to `{label}-adv.npy`).
+    reference's own `attack.py` writes next to `{label}-adv.npy`) or `{label}-raw.npy` decoded clips, or
+  * whole decoded videos, one `.npy` per sample-list row, from which each clip's frames are selected by the
+    reference loader's arithmetic (`kinetics_frame_indices`, `kinetics_video_batches`): a ragged pool of
+    distinct frames plus offset / geometry tables for `Engine.clip_gather_resize_crop`.
 
 Each item mirrors the reference's validation item `(clip, label, name)` (`datasets.py:138-150`)."""
 import csv
@@ -166,7 +169,8 @@ def pil_resample_table(n_in, n_out):
 # decoding -- everything in front of the loader's spatial transform, which runs on the device (`Engine.clip_resample_crop`).
 # Decoding is Pillow's (installed here, and what the reference calls, :14-18), so the reader is pinned by construction.
 # (The Kinetics-400 half of N4 -- decord reading mp4s, `datasets.py:188-244` -- is NOT buildable in this image: no decord,
-# PyAV, OpenCV or ffmpeg.  `--clip_dir` of `{label}-raw.npy` decoded frames is that half's entry point.)
+# PyAV, OpenCV or ffmpeg.  Its entry points are `--clip_dir` of `{label}-raw.npy` cut clips and `--video_dir` of whole decoded
+# videos, below.)
 # ---------------------------------------------------------------------------------------------------------------
 def loop_padding(frame_indices, size=32):
     """`transforms_ucf101.LoopPadding(size)` (:23-40), quirks included: the selection starts at the SECOND entry
@@ -256,6 +260,154 @@ def ucf101_batches(batch_size, setting, image_root, used_idxs=None, frames=32, w
 
 def ucf101_num_batches(batch_size, setting, image_root, used_idxs=None):
     return (len(ucf101_clip_list(setting, image_root, used_idxs)) + batch_size - 1) // batch_size
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Kinetics-400 whole decoded videos (`VideoClsDataset`, `/root/reference/datasets.py`, validation mode): the frame selection of
+# `loadvideo_decord` (:216-244) with each row's `clip_index` (:48-51, 138-150), applied to videos decoded ahead of time.  The
+# spatial transform runs on the device over the ragged batch (`Engine.clip_gather_resize_crop`).
+# The reference reads clip_len / frame_sample_rate / num_segment and the Resize / CenterCrop sizes from gluoncv's
+# `i3d_nl5_resnet101_v1_kinetics400.yaml` (image_main.py:55), which it does not ship: 32 / 2 / 1 and 256 / 224 are ASSUMED values
+# from that public config, and every one of them is a flag of the CLIs (--frames, --frame_sample_rate, --num_segment,
+# --short_side, --hw).
+# ---------------------------------------------------------------------------------------------------------------
+KINETICS_CLIP_LEN, KINETICS_FRAME_SAMPLE_RATE, KINETICS_NUM_SEGMENT = 32, 2, 1
+KINETICS_SHORT_SIDE, KINETICS_CROP = 256, 224
+
+
+def kinetics_frame_indices(n_frames, clip_ind, clip_len=KINETICS_CLIP_LEN, frame_sample_rate=KINETICS_FRAME_SAMPLE_RATE,
+                           num_segment=KINETICS_NUM_SEGMENT):
+    """int64 indices of the frames `loadvideo_decord` hands to `vr.get_batch` for a video of `n_frames` frames (validation mode,
+    sample_rate_scale = 1), `clip_len * num_segment` of them:
+      converted_len = clip_len * frame_sample_rate, seg_len = n_frames // num_segment; per segment i
+      short (seg_len <= converted_len): linspace(0, seg_len, seg_len // rate), padded to clip_len with seg_len, clipped to
+                                        [0, seg_len - 1] -- the padding repeats the segment's last frame;
+      long: end = seg_len - 1 for clip_ind == -1, else randint(converted_len, seg_len) seeded by clip_ind; the clip is
+            linspace(end - converted_len, end, clip_len) clipped to [start, end - 1];
+      then cast to int64 and shifted by i * seg_len.
+    Deliberate difference: the draw comes from a local `np.random.RandomState(clip_ind)` -- the same number as the reference's
+    `np.random.seed(clip_ind); np.random.randint(...)` -- and leaves numpy's global random state alone.  A video with fewer frames
+    than segments (the reference would clip to [0, -1]) is refused."""
+    n_frames, clip_len, rate, nseg = int(n_frames), int(clip_len), int(frame_sample_rate), int(num_segment)
+    if clip_len < 1 or rate < 1 or nseg < 1:
+        raise ValueError(f"clip_len, frame_sample_rate and num_segment must be >= 1 (got {clip_len}, {rate}, {nseg})")
+    if n_frames < 1 or n_frames < nseg:
+        raise ValueError(f"a video of {n_frames} frames cannot give {nseg} segment(s)")
+    converted_len = clip_len * rate
+    seg_len = n_frames // nseg
+    out = []
+    for i in range(nseg):
+        if seg_len <= converted_len:
+            index = np.linspace(0, seg_len, num=seg_len // rate)
+            index = np.concatenate((index, np.ones(clip_len - seg_len // rate) * seg_len))
+            index = np.clip(index, 0, seg_len - 1).astype(np.int64)
+        else:
+            if clip_ind == -1:
+                end_idx = seg_len - 1
+            else:
+                end_idx = np.random.RandomState(clip_ind).randint(converted_len, seg_len)
+            str_idx = end_idx - converted_len
+            index = np.linspace(str_idx, end_idx, num=clip_len)
+            index = np.clip(index, str_idx, end_idx - 1).astype(np.int64)
+        out.append(index + i * seg_len)
+    return np.concatenate(out).astype(np.int64)
+
+
+def kinetics_rows(csv_path, n=400):
+    """[(path, gt_label, clip_index)] of the reference's sample list `path,gt_label,clip_index` (datasets.py:48-51)."""
+    with open(csv_path) as fh:
+        return [(r["path"], int(r["gt_label"]), int(r["clip_index"])) for r in csv.DictReader(fh)][:n]
+
+
+def kinetics_video_path(video_dir, path):
+    """`<video_dir>/<path minus its extension>.npy`: the whole decoded video of a row (VAL_DATA_PATH + path, datasets.py:190)."""
+    return os.path.join(video_dir, os.path.splitext(path)[0] + ".npy")
+
+
+def gather_geometry(sizes, short_side=KINETICS_SHORT_SIDE, crop=KINETICS_CROP):
+    """Per clip frame size (H, W) -> the tables of `i2v_clip_gather_resize_crop_u8_f32`: geometry int32 (b, 8) = (H, W, rh, rw,
+    crop y, crop x, first xtab row, first ytab row) and the concatenated cv2 resize tables xtab / ytab int32 (rows, 3).  Clips of
+    one frame size share their tables."""
+    geom, xparts, yparts, seen = [], [], [], {}
+    xrows = yrows = 0
+    for H, W in sizes:
+        H, W = int(H), int(W)
+        rh, rw = resize_sizes(H, W, short_side)
+        if rh < crop or rw < crop:
+            raise ValueError(f"a {H} x {W} frame resized to {rh} x {rw} is smaller than the {crop} x {crop} crop")
+        if (H, W) not in seen:
+            seen[(H, W)] = (xrows, yrows)
+            xparts.append(resize_table(rw, W))
+            yparts.append(resize_table(rh, H))
+            xrows, yrows = xrows + rw, yrows + rh
+        cy, cx = center_crop_origin(rh, rw, crop, crop)
+        geom.append((H, W, rh, rw, cy, cx) + seen[(H, W)])
+    return np.asarray(geom, np.int32).reshape(-1, 8), np.concatenate(xparts), np.concatenate(yparts)
+
+
+POOL_ALIGN = 16             # every frame of the pool starts on a 16-byte boundary (the kernel stages rows with 16-byte loads)
+
+
+def pack_frames(videos, indices, pin=False):
+    """Distinct selected frames of each clip, packed once: returns (pool uint8 (bytes,), offsets int64 (b, t)).  `videos[i]` is an
+    array-like (N, H, W, 3) uint8 (a memory map reads only the frames asked for); `indices[i]` the clip's frame indices."""
+    offsets = np.empty((len(videos), len(indices[0])), np.int64)
+    picks, total = [], 0
+    for ci, (v, idx) in enumerate(zip(videos, indices)):
+        slot = {}
+        fbytes = int(np.prod(v.shape[1:]))
+        for ti, f in enumerate(idx):
+            f = int(f)
+            if f not in slot:
+                slot[f] = total
+                picks.append((ci, f, total, fbytes))
+                total += (fbytes + POOL_ALIGN - 1) // POOL_ALIGN * POOL_ALIGN
+            offsets[ci, ti] = slot[f]
+    pool = torch.empty(max(total, POOL_ALIGN), dtype=torch.uint8, pin_memory=pin)
+    host = pool.numpy()
+    for ci, f, off, fbytes in picks:
+        host[off:off + fbytes] = np.ascontiguousarray(videos[ci][f]).reshape(-1)
+    return pool, offsets
+
+
+def _open_video(video_dir, path, row):
+    p = kinetics_video_path(video_dir, path)
+    if not os.path.exists(p):
+        raise FileNotFoundError(f"row {row} ({path}): no decoded video {p}")
+    v = np.load(p, mmap_mode="r")
+    if v.dtype != np.uint8 or v.ndim != 4 or v.shape[-1] != 3:
+        raise ValueError(f"row {row} ({path}): {p} holds {v.dtype} {v.shape}, expected uint8 (N, H, W, 3)")
+    if v.shape[0] == 0:
+        raise ValueError(f"row {row} ({path}): {p} holds no frames")
+    return v
+
+
+def kinetics_video_batches(batch_size, csv_path, video_dir, clip_len=KINETICS_CLIP_LEN, frame_sample_rate=KINETICS_FRAME_SAMPLE_RATE,
+                           num_segment=KINETICS_NUM_SEGMENT, short_side=KINETICS_SHORT_SIDE, crop=KINETICS_CROP, n=400, workers=0,
+                           pin=None):
+    """The reference's validation loader over whole decoded videos (datasets.py:138-150, 188-244) up to its spatial transform:
+    yields (pool, tables, labels (b,), names) in list order, where pool is one uint8 tensor of the batch's DISTINCT selected frames
+    (pinned when a GPU is present) and tables = (offsets int64 (b, t), geometry int32 (b, 8), xtab, ytab) as `gather_geometry`
+    describes them; `Engine.clip_gather_resize_crop(pool, offsets, (geometry, xtab, ytab))` gives the (b,3,t,crop,crop) batch.
+    Names follow the reference, `path.split(".")[0]` (:150).  Each row's video is `kinetics_video_path(video_dir, path)`, memory
+    mapped so that only the selected frames are read.  A missing or empty video is an error naming its row -- where the reference
+    draws another row, calls `loadvideo_decord(sample)` without its clip index and dies with a TypeError (:144-147)."""
+    rows = kinetics_rows(csv_path, n)
+    if pin is None:
+        pin = torch.cuda.is_available()
+
+    def load(s):
+        chunk = rows[s:s + batch_size]
+        videos = [_open_video(video_dir, path, s + i) for i, (path, _, _) in enumerate(chunk)]
+        indices = [kinetics_frame_indices(v.shape[0], ci, clip_len, frame_sample_rate, num_segment) for v, (_, _, ci) in zip(videos, chunk)]
+        pool, offsets = pack_frames(videos, indices, pin)
+        geom, xtab, ytab = gather_geometry([v.shape[1:3] for v in videos], short_side, crop)
+        return pool, (offsets, geom, xtab, ytab), torch.tensor([r[1] for r in chunk]), [r[0].split(".")[0] for r in chunk]
+    yield from _prefetched(load, list(range(0, len(rows), batch_size)), workers)
+
+
+def kinetics_num_batches(batch_size, csv_path, n=400):
+    return (len(kinetics_rows(csv_path, n)) + batch_size - 1) // batch_size
 
 
 def _prefetched(load, starts, workers):

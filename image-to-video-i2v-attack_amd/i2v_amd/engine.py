@@ -132,6 +132,33 @@ class Engine:
             cy, cx, crop, crop, self.stream()))
         return out
 
+    def clip_gather_resize_crop(self, pool: torch.Tensor, offsets, geometry, short_side=256, crop=224) -> torch.Tensor:
+        """The validation transform of `clip_resize_crop` over a RAGGED batch in one kernel: clip bi, frame ti is the H*W*3 bytes at
+        pool[offsets[bi, ti]:] (pool: uint8, on the device or in host memory -- then uploaded on this engine's stream), each clip
+        with its own frame size.  `geometry` is what `clips.kinetics_video_batches` yields -- (geometry int32 (b, 8), xtab, ytab) from
+        `clips.gather_geometry` -- or the clips' frame sizes (H, W) (b, 2), from which that is built with `short_side` / `crop`.
+        Returns (b,3,t,crop,crop) float32; the library checks every offset and table on the host before it launches."""
+        from . import clips as _clips
+        import numpy as np
+        assert pool.dtype == torch.uint8 and pool.is_contiguous()
+        if isinstance(geometry, (tuple, list)) and len(geometry) == 3:
+            geom, xtab, ytab = (np.ascontiguousarray(a, np.int32) for a in geometry)
+        else:
+            geom, xtab, ytab = _clips.gather_geometry(np.asarray(geometry).reshape(-1, 2), short_side, crop)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        b, t = offsets.shape
+        assert geom.shape == (b, 8) and xtab.ndim == 2 and xtab.shape[1] == 3 and ytab.ndim == 2 and ytab.shape[1] == 3
+        if pool.device != self.device:
+            pool = pool.to(self.device, non_blocking=True)
+        nbytes = int(self.capi.i2v_clip_gather_scratch_bytes(b, t, xtab.shape[0], ytab.shape[0]))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out = torch.empty(b, 3, t, crop, crop, dtype=torch.float32, device=self.device)
+        _lib.check(self.capi, self.capi.i2v_clip_gather_resize_crop_u8_f32(
+            C.c_void_p(pool.data_ptr()), pool.numel(), offsets.ctypes.data_as(C.c_void_p), geom.ctypes.data_as(C.c_void_p), b, t,
+            xtab.ctypes.data_as(C.c_void_p), xtab.shape[0], ytab.ctypes.data_as(C.c_void_p), ytab.shape[0], crop, crop, _ptr(out, self),
+            C.c_void_p(scratch.data_ptr()), nbytes, self.stream()))
+        return out
+
     def clip_resample_crop(self, frames_u8: torch.Tensor, size=224, crop=224) -> torch.Tensor:
         """(b,t,H,W,3) uint8 decoded frames on the device -> the UCF-101 loader's validation transform (dataset_ucf101.py:113-126:
         PIL BILINEAR `Scale(size)`, `CornerCrop(crop, 'c')`, ToTensor, Normalize) -> (b,3,t,crop,crop) float32, in one kernel."""

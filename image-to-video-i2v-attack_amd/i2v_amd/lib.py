@@ -112,10 +112,17 @@ _PROTOS = {
     "i2v_aens_reduce_f32": ([_P, _P, _I, _I, _P, _P, _P], _I),
 }
 EXPORTS = tuple(_PROTOS)
+# The ragged clip transform (`include/i2v_loader.h`): a header of its own, outside the ABI the planner's host simulation implements,
+# so bound only on the product library.
+_LOADER_PROTOS = {
+    "i2v_clip_gather_scratch_bytes": ([_I, _I, _I, _I], _L),
+    "i2v_clip_gather_resize_crop_u8_f32": ([_P, _L, _P, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P], _I),
+}
+LOADER_EXPORTS = tuple(_LOADER_PROTOS)
 
 
-def bind(cdll):
-    for name, (args, res) in _PROTOS.items():
+def bind(cdll, protos=_PROTOS):
+    for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
         fn.argtypes, fn.restype = args, res
     return cdll
@@ -136,6 +143,7 @@ def load():
         lib = bind(C.CDLL(path))
         if lib.i2v_backend() != HIP_BACKEND:
             raise I2VError(f"{path} reports backend {lib.i2v_backend()!r}, expected {HIP_BACKEND!r}")
+        bind(lib, _LOADER_PROTOS)
         _lib = lib
     return _lib
 

@@ -4,7 +4,8 @@ window (`:61-63`), same artefacts -- `OPT_PATH/Image-{method}-{step}-{prefix}/{l
 (float32 (3,32,224,224), normalised) and `loss_info_{batch_index}.json` (`:45,90-95`).
 
 Differences: `OPT_PATH` comes from `$I2V_OPT_PATH` (the reference hard-codes an empty constant,
-`utils.py:21`); clips come from `i2v_amd.clips` (synthetic or `--clip_dir`), not decord; under
+`utils.py:21`); clips come from `i2v_amd.clips` (synthetic, `--clip_dir`, or `--video_dir` of whole videos decoded ahead of
+time, with the reference's frame selection), not decord; under
 `torchrun` the shard defaults to (WORLD_SIZE, RANK+1) so 8 GPUs need no manual `--batch_index`;
 `--resume` skips clips whose `{label}-adv.npy` already exists."""
 import argparse
@@ -48,6 +49,8 @@ def arg_parse(argv=None, ucf101=False):
     parser.add_argument("--frames", type=int, default=32)
     parser.add_argument("--hw", type=int, default=224)
     parser.add_argument("--resume", action="store_true")
+    if not ucf101:       # whole decoded Kinetics videos (datasets.py:188-244; the sample list is --anno)
+        add_video_flags(parser)
     if ucf101:           # the UCF-101 loader's inputs (dataset_ucf101.py:52-64, utils.UCF_IMAGE_ROOT): jpg frame folders + clip list
         parser.add_argument("--frame_dir", type=str, default=os.environ.get("I2V_UCF_IMAGE_ROOT", ""),
                             help="UCF_IMAGE_ROOT: <frame_dir>/<video_path>/image_00001.jpg ...; decoded by Pillow on the --workers threads")
@@ -65,11 +68,54 @@ def arg_parse(argv=None, ucf101=False):
                         help="run on the seeded synthetic initialiser when no checkpoint lies under $I2V_WEIGHTS_DIR "
                              "(same as I2V_SYNTHETIC_WEIGHTS=1); without it a missing checkpoint is an error")
     args = parser.parse_args(argv)
+    if not ucf101:
+        check_video_flags(parser, args)
     if args.synthetic_weights:
         os.environ["I2V_SYNTHETIC_WEIGHTS"] = "1"
     args.adv_path = os.path.join(OPT_PATH, "{}-{}-{}-{}".format("Image", args.attack_method, args.step, args.file_prefix))
     os.makedirs(args.adv_path, exist_ok=True)
     return args
+
+
+def add_video_flags(parser):
+    """The whole-video reader's flags (shared with attack.py).  Defaults: gluoncv's i3d_nl5_resnet101_v1_kinetics400.yaml, which the
+    reference loads but does not ship (ASSUMED values, i2v_amd/clips.py)."""
+    parser.add_argument("--video_dir", type=str, default="",
+                        help="VAL_DATA_PATH of whole decoded videos: <video_dir>/<csv path minus extension>.npy, uint8 (N,H,W,3) each; "
+                             "32 frames per --anno row are selected as the reference's loader does, with the row's clip_index")
+    parser.add_argument("--frame_sample_rate", type=int, default=clips.KINETICS_FRAME_SAMPLE_RATE)
+    parser.add_argument("--num_segment", type=int, default=clips.KINETICS_NUM_SEGMENT,
+                        help="segments per video; --frames is the clip's length over all of them (clip_len x num_segment)")
+    parser.add_argument("--short_side", type=int, default=clips.KINETICS_SHORT_SIDE, help="Resize(short_side) before the --hw centre crop")
+
+
+def check_video_flags(parser, args):
+    if not args.video_dir:
+        return
+    if args.clip_dir:
+        parser.error("--video_dir and --clip_dir are two sources of clips: give one")
+    if not args.anno:
+        parser.error("--video_dir needs --anno, the sample list `path,gt_label,clip_index`")
+    if args.frame_sample_rate < 1 or args.num_segment < 1 or args.frames % args.num_segment:
+        parser.error(f"--frames {args.frames} must be clip_len x --num_segment {args.num_segment} (clip_len * num_segment == --frames) "
+                     f"with --frame_sample_rate >= 1")
+    if args.short_side < args.hw:
+        parser.error(f"--short_side {args.short_side} is smaller than the --hw {args.hw} crop")
+
+
+def video_source(args, workers=0):
+    """(total batches, generator) of the whole-video reader for parsed CLI flags."""
+    total = clips.kinetics_num_batches(args.batch_size, args.anno, args.num_clips)
+    return total, clips.kinetics_video_batches(args.batch_size, args.anno, args.video_dir, args.frames // args.num_segment,
+                                               args.frame_sample_rate, args.num_segment, args.short_side, args.hw, args.num_clips,
+                                               workers=workers)
+
+
+def video_transform(batch, hw):
+    """A whole-video batch (pool, (offsets, geometry, xtab, ytab)) -> the normalised (b,3,t,hw,hw) batch on the device."""
+    from i2v_amd import attacks as _attacks
+    pool, (offsets, geom, xtab, ytab) = batch
+    return _attacks.get_engine().clip_gather_resize_crop(pool, offsets, (geom, xtab, ytab), crop=hw)
 
 
 def build_attack(args, ucf101=False):
@@ -119,6 +165,11 @@ def main(argv=None, ucf101=False):
 
         def source():
             return clips.ucf101_batches(args.batch_size, args.setting, frame_dir, used, args.frames, workers=args.workers)
+    elif getattr(args, "video_dir", ""):      # whole decoded videos: frame selection + de-duplicated pool on the host, transform on the device
+        total = video_source(args)[0]
+
+        def source():
+            return video_source(args, workers=args.workers)[1]
     else:
         total = clips.num_batches(args.batch_size, args.anno, args.clip_dir, args.num_clips)
 
@@ -153,10 +204,14 @@ def main(argv=None, ucf101=False):
             for step, item in enumerate(source()):
                 if not (left <= step < right):
                     continue
-                if args.resume and all(os.path.exists(os.path.join(args.adv_path, f"{l.item()}-adv.npy")) for l in item[1]):
+                *data, labels, names = item         # (batch, labels, names), or (pool, tables, labels, names) of whole videos
+                if args.resume and all(os.path.exists(os.path.join(args.adv_path, f"{l.item()}-adv.npy")) for l in labels):
                     continue
-                batch = item[0].pin_memory() if cuda else item[0]
-                todo.put((step, batch, item[1], item[2]))
+                if len(data) == 2:
+                    batch = (data[0] if data[0].is_pinned() or not cuda else data[0].pin_memory(), data[1])
+                else:
+                    batch = data[0].pin_memory() if cuda else data[0]
+                todo.put((step, batch, labels, names))
         except BaseException as e:             # a clip that cannot be read must end the run, not leave the main loop waiting
             reader_error.append(e)
         finally:
@@ -205,17 +260,19 @@ def main(argv=None, ucf101=False):
             if item is None:
                 ended = True
                 break
-            if items and nclips + int(item[1].shape[0]) > max(group, args.batch_size):
+            if items and nclips + int(item[2].shape[0]) > max(group, args.batch_size):
                 carry = item                # the plan was reserved for `group` clips: never collect more (a larger group would re-plan)
                 break
             items.append(item)
-            nclips += int(item[1].shape[0])
+            nclips += int(item[2].shape[0])
         if not items:
             break
         batches = []
         for step, val_batch, val_label, video_names in items:
             print("Running {}, {}/{}".format(args.attack_method, step + 1, total))
-            if val_batch.dtype == torch.uint8:          # decoded frames (b,t,H,W,3): the loader's Resize/CenterCrop/ToTensor/Normalize on the device
+            if isinstance(val_batch, tuple):           # whole videos: the ragged pool through the same transform, one launch
+                val_batch = video_transform(val_batch, args.hw)
+            elif val_batch.dtype == torch.uint8:          # decoded frames (b,t,H,W,3): the loader's Resize/CenterCrop/ToTensor/Normalize on the device
                 from i2v_amd import attacks as _attacks
                 eng = _attacks.get_engine()
                 raw = val_batch.to(eng.device, non_blocking=True).contiguous()
