@@ -112,7 +112,11 @@ class _ImageGuided(Attack):
         for m, ds, whole in zip(self.model_names, self._depths, self._whole):
             g = self._builder(m, hw)
             sd = _weights.load_state_dict(g, self._wseed)
-            nets.append(self.engine.build_net(g, sd, [g.hook_for(d, whole) for d in ds], frames))
+            hooks = [g.hook_for(d, whole) for d in ds]
+            if isinstance(g, _graphs.VitSpec):          # the transformer surrogate: a planned block stack of its own
+                nets.append(self.engine.build_vit_net(g, sd, hooks, frames))
+            else:
+                nets.append(self.engine.build_net(g, sd, hooks, frames))
         self._nets, self._net_key, self._max_frames = nets, key, frames
         return nets
 

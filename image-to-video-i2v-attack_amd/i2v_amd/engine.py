@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import Graph
+from .graphs import Graph, VitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -81,6 +81,15 @@ class Engine:
             t0 = time.perf_counter()
             net = Net(self, graph, state_dict, list(hook_tensors), max_frames, relu_gain)
             self.plan_ms += 1e3 * (time.perf_counter() - t0)      # pack + upload + plan + autotune (i2v_net_plan syncs)
+            self.plans += 1
+            return net
+
+    def build_vit_net(self, spec: VitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "VitNet":
+        """The ViT surrogate (`include/i2v_vit.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
+        with self.plan_lock:
+            t0 = time.perf_counter()
+            net = VitNet(self, spec, state_dict, list(hook_blocks), max_frames)
+            self.plan_ms += 1e3 * (time.perf_counter() - t0)
             self.plans += 1
             return net
 
@@ -560,3 +569,65 @@ class Net:
 
     def scratch_bytes(self, frames: int) -> int:
         return max(self.eng.capi.i2v_cossim_scratch_bytes(hi.D, frames) for hi in self.hooks)
+
+
+class VitNet(Net):
+    """The ViT surrogate behind the `Net` interface the attack loop uses (`forward`, `backward`, `save_hook`, `cossim`, `stdloss`,
+    `scratch_bytes`, `hooks`): a hook is the residual stream after one block, (tokens * dim) floats per frame; the loss kernels are the
+    ones every backbone uses."""
+
+    def __init__(self, eng: Engine, spec: VitSpec, sd, hook_blocks: List[int], max_frames: int):
+        self.eng, capi = eng, eng.capi
+        self.graph, self.max_frames, self.id = spec, max_frames, None
+        self.hook_tensors = list(hook_blocks)
+        nb = max(hook_blocks) + 1
+        keys = ["patch_embed.proj.weight", "patch_embed.proj.bias", "cls_token", "pos_embed"]
+        keys += [k for i in range(nb) for k in spec.block_keys(i)]
+        self._w = [sd[k].detach().float().cpu().contiguous() for k in keys]      # kept alive until the upload in i2v_vit_create
+        ptrs = (C.c_void_p * len(self._w))(*[t.data_ptr() for t in self._w])
+        cfg = _lib.VitConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.ln_eps)
+        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
+        h = C.c_void_p()
+        _lib.check(capi, capi.i2v_vit_create(eng.device.index or 0, C.byref(cfg), ptrs, len(self._w), hb, len(hook_blocks), max_frames,
+                                             C.byref(h)))
+        self._w = None
+        self.h = h
+        self.hooks = []
+        for i in range(len(hook_blocks)):
+            act, grad = C.c_void_p(), C.c_void_p()
+            a_s, g_s, D = C.c_int64(), C.c_int64(), C.c_int64()
+            _lib.check(capi, capi.i2v_vit_hook_info(h, i, C.byref(act), C.byref(a_s), C.byref(grad), C.byref(g_s), C.byref(D)))
+            hi = HookInfo()
+            hi.act, hi.act_stride, hi.grad, hi.grad_stride, hi.D, hi.post_relu = act.value, a_s.value, grad.value, g_s.value, D.value, 0
+            hi.shape, hi.T = (spec.tokens, spec.dim, 1), 1
+            self.hooks.append(hi)
+
+    def close(self):
+        if getattr(self, "h", None) and self.eng.h:
+            with self.eng.plan_lock:
+                self.eng.capi.i2v_vit_destroy(self.h)
+        self.h = None
+
+    def workspace_bytes(self) -> int:
+        return int(self.eng.capi.i2v_vit_workspace_bytes(self.h))
+
+    def forward(self, x: torch.Tensor):
+        spec = self.graph
+        if tuple(x.shape[1:]) != (spec.in_chans, spec.img, spec.img):
+            raise _lib.I2VError(f"{spec.arch}: frames of shape {tuple(x.shape[1:])}, expected {(spec.in_chans, spec.img, spec.img)}")
+        _lib.check(self.eng.capi, self.eng.capi.i2v_vit_forward(self.h, _ptr(x, self.eng), x.shape[0], self.eng.stream()))
+
+    def backward(self, gx: torch.Tensor, accumulate=False):
+        _lib.check(self.eng.capi, self.eng.capi.i2v_vit_backward(self.h, _ptr(gx, self.eng), 1 if accumulate else 0, self.eng.stream()))
+
+    def read_hook(self, i: int, frames: int, grad=False) -> torch.Tensor:
+        out = torch.empty(frames, self.graph.tokens, self.graph.dim, dtype=torch.float32, device=self.eng.device)
+        _lib.check(self.eng.capi, self.eng.capi.i2v_vit_read_hook(self.h, i, 1 if grad else 0, _ptr(out, self.eng), frames,
+                                                                 self.eng.stream()))
+        return out
+
+    def save_hook(self, i: int, frames: int) -> torch.Tensor:
+        return self.read_hook(i, frames)
+
+    def hook_frames(self, i: int, in_frames: int) -> int:
+        return in_frames

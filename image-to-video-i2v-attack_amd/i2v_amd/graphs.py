@@ -702,6 +702,84 @@ def video_hooks(g: Graph, model_type: str) -> List[int]:
 
 
 # ---------------------------------------------------------------------------
+# the ViT surrogate: not a graph of this IR -- a fixed transformer stack, planned by its own library entry (include/i2v_vit.h)
+# ---------------------------------------------------------------------------
+VIT_NAME = "vit_base_patch16_224"       # the timm name `get_vits()` passes (TPAMI_attack.py:88-98)
+
+
+@dataclass
+class VitSpec:
+    """timm `VisionTransformer`: patch embedding (patch x patch convolution, stride patch, bias), cls token
+    prepended, pos_embed added, then `blocks` pre-norm blocks x += proj(MHSA(LN1 x)); x += fc2(GELU(fc1(LN2 x))), LayerNorm eps
+    `ln_eps`, exact GELU, scale (dim / heads) ** -0.5.  `hooks`: depth d (1..4) -> zero-based block 3d - 1, whose OUTPUT (the residual
+    stream after it, all tokens) is the hooked feature."""
+    arch: str
+    img: int
+    patch: int = 16
+    in_chans: int = 3
+    dim: int = 768
+    heads: int = 12
+    mlp: int = 3072
+    blocks: int = 12
+    ln_eps: float = 1e-6
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        if not self.hooks:
+            self.hooks = {d: 3 * d - 1 for d in (1, 2, 3, 4) if 3 * d - 1 < self.blocks}
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def tokens(self) -> int:
+        return 1 + (self.img // self.patch) ** 2
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def block_keys(self, i: int) -> List[str]:
+        p = f"blocks.{i}."
+        return [p + k for k in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
+                                "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block (`norm.*` / `head.*` are not used below a hook)."""
+        D, H = self.dim, self.mlp
+        out = {"patch_embed.proj.weight": (D, self.in_chans, self.patch, self.patch), "patch_embed.proj.bias": (D,),
+               "cls_token": (1, 1, D), "pos_embed": (1, self.tokens, D)}
+        for i in range(self.blocks):
+            shapes = [(D,), (D,), (3 * D, D), (3 * D,), (D, D), (D,), (D,), (D,), (H, D), (H,), (D, H), (D,)]
+            out.update(zip(self.block_keys(i), shapes))
+        return out
+
+    def macs_per_frame(self) -> int:
+        T, D, H = self.tokens, self.dim, self.mlp
+        per_block = T * D * (3 * D + D + 2 * H) + 2 * T * T * D
+        return (T - 1) * D * self.in_chans * self.patch ** 2 + self.blocks * per_block
+
+
+def vit(in_hw=(224, 224)) -> VitSpec:
+    """ViT-B/16 at 224 x 224 only: interpolating pos_embed to another size is not offered."""
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{VIT_NAME} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}); "
+                         "interpolating its pos_embed to another size is not supported")
+    return VitSpec(VIT_NAME, 224)
+
+
+def vit_tiny(in_hw=(64, 64)) -> VitSpec:
+    """The same topology at test size: patch 16, dim 64, 2 heads, 6 blocks, MLP ratio 4; square frames, a multiple of 16."""
+    if in_hw[0] != in_hw[1] or in_hw[0] % 16:
+        raise ValueError(f"the tiny ViT takes square frames of a multiple of 16 pixels (got {tuple(in_hw)})")
+    return VitSpec("vit_tiny", int(in_hw[0]), 16, 3, 64, 2, 256, 6)
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -722,6 +800,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return densenet(32, (6, 12, 24, 16), 64, 4, in_hw, "densenet121")
     if model_name == "densenet161":
         return densenet(48, (6, 12, 36, 24), 96, 4, in_hw, "densenet161")
+    if model_name == VIT_NAME:          # extension: the transformer surrogate of `get_vits()` (TPAMI_attack.py:88-98)
+        return vit(in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -744,4 +824,6 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return squeezenet(4, in_hw, "squeezenet_tiny")
     if model_name in ("densenet121", "densenet161"):
         return densenet(8, (2, 3, 2, 2), 16, 2, in_hw, "densenet_tiny")
+    if model_name == VIT_NAME:
+        return vit_tiny(in_hw)
     return build(model_name, in_hw)

@@ -121,6 +121,32 @@ _LOADER_PROTOS = {
 LOADER_EXPORTS = tuple(_LOADER_PROTOS)
 
 
+class VitConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("img", "patch", "in_chans", "dim", "heads", "mlp", "blocks")] + [("ln_eps", C.c_float)]
+
+
+# The ViT surrogate (`include/i2v_vit.h`): like the loader, a header of its own outside the host simulation's ABI.
+_VIT_PROTOS = {
+    "i2v_vit_create": ([_I, C.POINTER(VitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    "i2v_vit_destroy": ([_P], _I),
+    "i2v_vit_workspace_bytes": ([_P], _L),
+    "i2v_vit_forward": ([_P, _P, _I, _P], _I),
+    "i2v_vit_backward": ([_P, _P, _I, _P], _I),
+    "i2v_vit_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+    "i2v_vit_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    "i2v_vit_linear_f32": ([_P, _I, _I, _P, _P, _I, _P, _P, _P, _P], _I),
+    "i2v_vit_linear_bwd_f32": ([_P, _I, _I, _P, _I, _P, _P, _P], _I),
+    "i2v_vit_layernorm_f32": ([_P, _L, _I, _P, _P, _F, _P, _P, _P, _P], _I),
+    "i2v_vit_layernorm_bwd_f32": ([_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P], _I),
+    "i2v_vit_probs_ld": ([_I], _I),
+    "i2v_vit_attention_f32": ([_P, _I, _I, _I, _I, _F, _P, _P, _P], _I),
+    "i2v_vit_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P], _I),
+    "i2v_vit_embed_f32": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P], _I),
+    "i2v_vit_embed_bwd_f32": ([_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P], _I),
+}
+VIT_EXPORTS = tuple(_VIT_PROTOS)
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
@@ -144,6 +170,7 @@ def load():
         if lib.i2v_backend() != HIP_BACKEND:
             raise I2VError(f"{path} reports backend {lib.i2v_backend()!r}, expected {HIP_BACKEND!r}")
         bind(lib, _LOADER_PROTOS)
+        bind(lib, _VIT_PROTOS)
         _lib = lib
     return _lib
 

@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import Graph
+from .graphs import Graph, VitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -27,7 +27,26 @@ def _gen(seed: int, key: str) -> torch.Generator:
     return g
 
 
+def _vit_synthetic(spec: VitSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained ViT, drawn per key like the CNN initialiser: truncated-normal-like (clamped at 2 std) matrices of
+    std 0.02 as timm initialises them, except qkv at 0.05 so that the attention logits reach O(1) and the softmax is not uniform;
+    LayerNorm gains near 1; small biases.  The residual stream stays O(1) through the 12 blocks (the tests check the hooks)."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.endswith("norm1.weight") or k.endswith("norm2.weight"):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            std = 0.05 if k.endswith("attn.qkv.weight") else 0.02
+            sd[k] = torch.randn(*shp, generator=g).clamp_(-2.0, 2.0) * std
+    return sd
+
+
 def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]:
+    if isinstance(graph, VitSpec):
+        return _vit_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op != "conv":

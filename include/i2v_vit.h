@@ -1,0 +1,88 @@
+/* libi2v_hip.so -- C ABI of the ViT surrogate (timm `vit_base_patch16_224`, the model the reference's `get_vits()` builds,
+ * TPAMI_attack.py:88-98), forward to its hooked blocks and backward to the input.
+ *
+ * Same conventions as i2v_hip.h: every function returns 0 on success and non-zero on error with the text in `i2v_last_error()`;
+ * tensors are caller-owned contiguous fp32 DEVICE pointers; work is enqueued on `stream` (a hipStream_t as void*, 0 = default) and
+ * nothing synchronises the host inside a forward or backward.  Kept in a header of its own: i2v_hip.h is the ABI that the planner's
+ * host simulation implements in full, and a ViT has no place in that planner.
+ *
+ * Model: patch embedding (a patch x patch convolution with stride patch and bias, in_chans -> dim), flattened to
+ * tokens, `cls_token` prepended, `pos_embed` added; then `blocks` pre-norm transformer blocks
+ *   x = x + proj(MHSA(LN1(x)));  x = x + fc2(GELU(fc1(LN2(x))))
+ * LayerNorm with eps `ln_eps`, biased variance and an affine transform; qkv rows [q; k; v], head h owning rows h*dh .. h*dh+dh-1 of each
+ * (dh = dim / heads); softmax over keys of (q k^T) * dh^-0.5; exact (erf) GELU.  Activations are held TOKEN-MAJOR: a frame is
+ * (tokens, dim) row-major, tokens = 1 + (img / patch)^2.
+ *
+ * A hook is the output of a block -- the residual stream after it, all tokens including cls: D = tokens * dim floats per frame.
+ */
+#ifndef I2V_VIT_H
+#define I2V_VIT_H
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct i2v_vit* i2v_vit_handle;
+
+typedef struct {
+    int32_t img, patch, in_chans, dim, heads, mlp, blocks;   /* input side, patch side, input channels, width, heads, MLP width, blocks */
+    float ln_eps;
+} i2v_vit_config;
+
+/* Weights: host fp32 arrays in this order (timm `state_dict` shapes; 4 + 12 * blocks_used entries, blocks_used = deepest hook + 1):
+ *   patch_embed.proj.weight (dim, in_chans, patch, patch), patch_embed.proj.bias (dim), cls_token (dim), pos_embed (tokens, dim),
+ *   then per block i: norm1.weight, norm1.bias (dim), attn.qkv.weight (3 dim, dim), attn.qkv.bias (3 dim), attn.proj.weight (dim, dim),
+ *   attn.proj.bias, norm2.weight, norm2.bias (dim), mlp.fc1.weight (mlp, dim), mlp.fc1.bias (mlp), mlp.fc2.weight (dim, mlp),
+ *   mlp.fc2.bias (dim).
+ * hook_blocks: zero-based block indices, distinct, in the order the hooks fire.  Uploads the weights and allocates the activation arena
+ * for up to `max_frames` frames on `device` (synchronous: a planning step). */
+int i2v_vit_create(int device, const i2v_vit_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_blocks,
+                   int n_hooks, int max_frames, i2v_vit_handle* out);
+int i2v_vit_destroy(i2v_vit_handle net);
+/* Bytes of device memory the net holds (weights and arena). */
+int64_t i2v_vit_workspace_bytes(i2v_vit_handle net);
+/* x: (frames, in_chans, img, img), frames <= max_frames.  Runs up to the deepest hook, keeping what the backward needs. */
+int i2v_vit_forward(i2v_vit_handle net, const float* x, int frames, void* stream);
+/* d(cost)/d(x) of the last forward from the hooks' gradient views (all of them are read): written into gx (accumulate = 0) or added
+ * to it (accumulate = 1).  gx: (frames, in_chans, img, img). */
+int i2v_vit_backward(i2v_vit_handle net, float* gx, int accumulate, void* stream);
+/* Hook `hook`'s activation and gradient views: frame stride (elements) and D contiguous elements per frame -- what
+ * `i2v_cossim_fwd_bwd_f32` / `i2v_std_*` of i2v_hip.h read and fill. */
+int i2v_vit_hook_info(i2v_vit_handle net, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride, int64_t* D);
+/* Copy hook `hook`'s activation (which = 0) or gradient (which = 1) for `frames` frames into out (frames, D), on `stream`. */
+int i2v_vit_read_hook(i2v_vit_handle net, int hook, int which, float* out, int frames, void* stream);
+
+/* ---- the kernels on their own (tests) ----------------------------------------------------------------------------------------
+ * y (M, N) = x (M, K) W^T + bias (+ residual);  W: (N, K) as torch.nn.Linear; bias / residual may be null.  With gelu_out non-null, y is
+ * the pre-activation and gelu_out = GELU(y). */
+int i2v_vit_linear_f32(const float* x, int M, int K, const float* W, const float* bias, int N, const float* residual, float* y,
+                       float* gelu_out, void* stream);
+/* dx (M, K) = dy (M, N) W, times GELU'(pre) elementwise when pre (M, K) is non-null. */
+int i2v_vit_linear_bwd_f32(const float* dy, int M, int N, const float* W, int K, const float* pre, float* dx, void* stream);
+/* LayerNorm over the last axis of x (rows, C): out, mean (rows), rstd (rows).  Backward: dx = add0 + add1 + d LN / dx applied to dy
+ * (add0 / add1 may be null, dx may alias either). */
+int i2v_vit_layernorm_f32(const float* x, int64_t rows, int C, const float* gamma, const float* beta, float eps, float* out, float* mean,
+                          float* rstd, void* stream);
+int i2v_vit_layernorm_bwd_f32(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, int64_t rows,
+                              int C, const float* add0, const float* add1, float* dx, void* stream);
+/* Multi-head attention core over qkv (frames, T, 3 heads dh): probs (frames, heads, T, ld) with ld = i2v_vit_probs_ld(T), out
+ * (frames, T, heads dh) = softmax(scale q k^T) v per (frame, head).  Backward from dout (frames, T, heads dh): dqkv (frames, T,
+ * 3 heads dh); dprobs: scratch of the probs' size. */
+int i2v_vit_probs_ld(int T);
+int i2v_vit_attention_f32(const float* qkv, int frames, int T, int heads, int dh, float scale, float* probs, float* out, void* stream);
+int i2v_vit_attention_bwd_f32(const float* qkv, const float* probs, const float* dout, int frames, int T, int heads, int dh, float scale,
+                              float* dprobs, float* dqkv, void* stream);
+/* Token assembly: img (frames, in_chans, g*patch, g*patch) -> tokens (frames, 1 + g*g, dim) = [cls; patches W^T + b] + pos;
+ * patches: scratch (frames * g*g, in_chans*patch*patch), emb: scratch (frames * g*g, dim).  Backward: gimg (=, or += with accumulate)
+ * from dtokens (frames, 1 + g*g, dim); patches is scratch again. */
+int i2v_vit_embed_f32(const float* img, int frames, int in_chans, int g, int patch, const float* W, const float* b, const float* cls,
+                      const float* pos, int dim, float* patches, float* emb, float* tokens, void* stream);
+int i2v_vit_embed_bwd_f32(const float* dtokens, int frames, int in_chans, int g, int patch, const float* W, int dim, float* patches,
+                          float* gimg, int accumulate, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
