@@ -115,6 +115,8 @@ class _ImageGuided(Attack):
             hooks = [g.hook_for(d, whole) for d in ds]
             if isinstance(g, _graphs.VitSpec):          # the transformer surrogate: a planned block stack of its own
                 nets.append(self.engine.build_vit_net(g, sd, hooks, frames))
+            elif isinstance(g, _graphs.SwinSpec):       # the windowed transformer: stages, hooked before their patch merging
+                nets.append(self.engine.build_swin_net(g, sd, hooks, frames))
             else:
                 nets.append(self.engine.build_net(g, sd, hooks, frames))
         self._nets, self._net_key, self._max_frames = nets, key, frames

@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import Graph, VitSpec
+from .graphs import Graph, SwinSpec, VitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -89,6 +89,15 @@ class Engine:
         with self.plan_lock:
             t0 = time.perf_counter()
             net = VitNet(self, spec, state_dict, list(hook_blocks), max_frames)
+            self.plan_ms += 1e3 * (time.perf_counter() - t0)
+            self.plans += 1
+            return net
+
+    def build_swin_net(self, spec: SwinSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "SwinNet":
+        """A Swin surrogate (`include/i2v_swin.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
+        with self.plan_lock:
+            t0 = time.perf_counter()
+            net = SwinNet(self, spec, state_dict, list(hook_stages), max_frames)
             self.plan_ms += 1e3 * (time.perf_counter() - t0)
             self.plans += 1
             return net
@@ -628,6 +637,69 @@ class VitNet(Net):
         out = torch.empty(frames, self.graph.tokens, self.graph.dim, dtype=torch.float32, device=self.eng.device)
         _lib.check(self.eng.capi, self.eng.capi.i2v_vit_read_hook(self.h, i, 1 if grad else 0, _ptr(out, self.eng), frames,
                                                                  self.eng.stream()))
+        return out
+
+    def save_hook(self, i: int, frames: int) -> torch.Tensor:
+        return self.read_hook(i, frames)
+
+    def hook_frames(self, i: int, in_frames: int) -> int:
+        return in_frames
+
+
+class SwinNet(Net):
+    """A Swin surrogate behind the `Net` interface the attack loop uses: a hook is the stream after the last block of a stage, before
+    that stage's patch merging, (grid^2 * width) floats per frame; the loss kernels are the ones every backbone uses."""
+
+    def __init__(self, eng: Engine, spec: SwinSpec, sd, hook_stages: List[int], max_frames: int):
+        self.eng, capi = eng, eng.capi
+        self.graph, self.max_frames, self.id = spec, max_frames, None
+        self.hook_tensors = list(hook_stages)
+        ns = max(hook_stages) + 1
+        # native order (include/i2v_swin.h): the embedding, then per stage its blocks and the merging behind it; kept alive until the upload
+        self._w = [sd[k].detach().float().cpu().contiguous() for k in spec.native_keys(ns)]
+        ptrs = (C.c_void_p * len(self._w))(*[t.data_ptr() for t in self._w])
+        pad = lambda v: (C.c_int32 * 4)(*(list(v) + [0] * (4 - len(v))))
+        cfg = _lib.SwinConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.window, spec.stages, pad(spec.depths), pad(spec.heads),
+                              spec.ln_eps)
+        hs = (C.c_int32 * len(hook_stages))(*hook_stages)
+        h = C.c_void_p()
+        _lib.check(capi, capi.i2v_swin_create(eng.device.index or 0, C.byref(cfg), ptrs, len(self._w), hs, len(hook_stages), max_frames,
+                                              C.byref(h)))
+        self._w = None
+        self.h = h
+        self.hooks = []
+        for i, st in enumerate(hook_stages):
+            act, grad = C.c_void_p(), C.c_void_p()
+            a_s, g_s, D = C.c_int64(), C.c_int64(), C.c_int64()
+            _lib.check(capi, capi.i2v_swin_hook_info(h, i, C.byref(act), C.byref(a_s), C.byref(grad), C.byref(g_s), C.byref(D)))
+            hi = HookInfo()
+            hi.act, hi.act_stride, hi.grad, hi.grad_stride, hi.D, hi.post_relu = act.value, a_s.value, grad.value, g_s.value, D.value, 0
+            hi.shape, hi.T = (spec.tokens(st), spec.width(st), 1), 1
+            self.hooks.append(hi)
+
+    def close(self):
+        if getattr(self, "h", None) and self.eng.h:
+            with self.eng.plan_lock:
+                self.eng.capi.i2v_swin_destroy(self.h)
+        self.h = None
+
+    def workspace_bytes(self) -> int:
+        return int(self.eng.capi.i2v_swin_workspace_bytes(self.h))
+
+    def forward(self, x: torch.Tensor):
+        spec = self.graph
+        if tuple(x.shape[1:]) != (spec.in_chans, spec.img, spec.img):
+            raise _lib.I2VError(f"{spec.arch}: frames of shape {tuple(x.shape[1:])}, expected {(spec.in_chans, spec.img, spec.img)}")
+        _lib.check(self.eng.capi, self.eng.capi.i2v_swin_forward(self.h, _ptr(x, self.eng), x.shape[0], self.eng.stream()))
+
+    def backward(self, gx: torch.Tensor, accumulate=False):
+        _lib.check(self.eng.capi, self.eng.capi.i2v_swin_backward(self.h, _ptr(gx, self.eng), 1 if accumulate else 0, self.eng.stream()))
+
+    def read_hook(self, i: int, frames: int, grad=False) -> torch.Tensor:
+        st = self.hook_tensors[i]
+        out = torch.empty(frames, self.graph.tokens(st), self.graph.width(st), dtype=torch.float32, device=self.eng.device)
+        _lib.check(self.eng.capi, self.eng.capi.i2v_swin_read_hook(self.h, i, 1 if grad else 0, _ptr(out, self.eng), frames,
+                                                                  self.eng.stream()))
         return out
 
     def save_hook(self, i: int, frames: int) -> torch.Tensor:

@@ -854,6 +854,205 @@ def vit_tiny(in_hw=(64, 64), n_prefix: int = 1, patch: int = 16) -> VitSpec:
 
 
 # ---------------------------------------------------------------------------
+# the Swin surrogates: hierarchical, windowed transformers, planned by a library entry of their own (include/i2v_swin.h)
+# ---------------------------------------------------------------------------
+#: timm 0.5.0's 224 x 224, ImageNet-1k Swin models (patch 4, window 7, MLP ratio 4, head width 32): name -> (C, depths, heads).
+SWIN_MODELS: Dict[str, Tuple[int, Tuple[int, ...], Tuple[int, ...]]] = {
+    "swin_tiny_patch4_window7_224": (96, (2, 2, 6, 2), (3, 6, 12, 24)),
+    "swin_small_patch4_window7_224": (96, (2, 2, 18, 2), (3, 6, 12, 24)),
+    "swin_base_patch4_window7_224": (128, (2, 2, 18, 2), (4, 8, 16, 32)),
+    "swin_large_patch4_window7_224": (192, (2, 2, 18, 2), (6, 12, 24, 48)),
+}
+
+
+@dataclass
+class SwinSpec:
+    """timm `SwinTransformer`: patch embedding (patch x patch convolution, stride patch, bias) and LayerNorm, no
+    class token, no position embedding; stage i is `depths[i]` blocks at width dim * 2^i on a grid of (img / patch) / 2^i, with patch
+    merging behind every stage but the last.  A block is x += proj(WMSA(LN1 x)); x += fc2(GELU(fc1(LN2 x))) with window attention
+    (relative-position bias; odd blocks shifted by window // 2 with the region mask; window = grid and no shift where the grid is not
+    larger than the window), LayerNorm eps `ln_eps`, exact GELU, MLP ratio 4.
+    `hooks`: depth d (1..stages) -> zero-based stage d - 1, whose last block's OUTPUT, before that stage's patch merging, is the
+    hooked feature: grid_i^2 * width_i floats per frame."""
+    arch: str
+    img: int
+    patch: int = 4
+    in_chans: int = 3
+    dim: int = 96
+    window: int = 7
+    depths: Tuple[int, ...] = (2, 2, 6, 2)
+    heads: Tuple[int, ...] = (3, 6, 12, 24)
+    ln_eps: float = 1e-5
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        self.depths, self.heads = tuple(self.depths), tuple(self.heads)
+        if len(self.depths) != len(self.heads) or not 1 <= len(self.depths) <= 4:
+            raise ValueError(f"{self.arch}: depths {self.depths} and heads {self.heads} must name the same 1..4 stages")
+        for i in range(self.stages):
+            if self.grid(i) * self.patch << i != self.img or self.grid(i) % self.window:
+                raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame does not give stage {i} a grid of whole "
+                                 f"{self.window} x {self.window} windows")
+            if self.width(i) % self.heads[i]:
+                raise ValueError(f"{self.arch}: width {self.width(i)} of stage {i} is not a multiple of its {self.heads[i]} heads")
+        if not self.hooks:
+            self.hooks = {d: d - 1 for d in range(1, self.stages + 1)}
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def stages(self) -> int:
+        return len(self.depths)
+
+    def grid(self, i: int) -> int:
+        return (self.img // self.patch) >> i
+
+    def width(self, i: int) -> int:
+        return self.dim << i
+
+    def tokens(self, i: int) -> int:
+        return self.grid(i) ** 2
+
+    def hook_dim(self, i: int) -> int:
+        """Floats per frame of the feature hooked at stage i."""
+        return self.tokens(i) * self.width(i)
+
+    def shift(self, i: int, j: int) -> int:
+        """Cyclic shift of block j of stage i."""
+        return self.window // 2 if j % 2 == 1 and self.grid(i) > self.window else 0
+
+    @property
+    def n_index(self) -> int:
+        return (2 * self.window - 1) ** 2
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based stage whose last block depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def block_keys(self, i: int, j: int) -> List[str]:
+        p = f"layers.{i}.blocks.{j}."
+        return [p + k for k in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.relative_position_bias_table",
+                                "attn.proj.weight", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias",
+                                "mlp.fc2.weight", "mlp.fc2.bias")]
+
+    def merge_keys(self, i: int) -> List[str]:
+        p = f"layers.{i}.downsample."
+        return [p + "norm.weight", p + "norm.bias", p + "reduction.weight"]
+
+    def embed_keys(self) -> List[str]:
+        return ["patch_embed.proj.weight", "patch_embed.proj.bias", "patch_embed.norm.weight", "patch_embed.norm.bias"]
+
+    def native_keys(self, n_stages: int) -> List[str]:
+        """The keys in the order `i2v_swin_create` takes the arrays, for the first `n_stages` stages."""
+        out = self.embed_keys()
+        for i in range(n_stages):
+            for j in range(self.depths[i]):
+                out += self.block_keys(i, j)
+            if i + 1 < n_stages:
+                out += self.merge_keys(i)
+        return out
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block (the merging behind the last stage does not exist;
+        `norm.*` and `head.*` are not used below a hook; the `relative_position_index` / `attn_mask` buffers are computed)."""
+        C = self.dim
+        out = dict(zip(self.embed_keys(), [(C, self.in_chans, self.patch, self.patch), (C,), (C,), (C,)]))
+        for i in range(self.stages):
+            D, H = self.width(i), self.heads[i]
+            for j in range(self.depths[i]):
+                shapes = [(D,), (D,), (3 * D, D), (3 * D,), (self.n_index, H), (D, D), (D,), (D,), (D,), (4 * D, D), (4 * D,), (D, 4 * D), (D,)]
+                out.update(zip(self.block_keys(i, j), shapes))
+            if i + 1 < self.stages:
+                out.update(zip(self.merge_keys(i), [(4 * D,), (4 * D,), (2 * D, 4 * D)]))
+        return out
+
+    def relative_position_index(self) -> "torch.Tensor":
+        """(window^2, window^2) int64: idx[i, j] = (r_i - r_j + window - 1)(2 window - 1) + c_i - c_j + window - 1."""
+        import torch
+        w = self.window
+        r, c = torch.arange(w * w) // w, torch.arange(w * w) % w
+        return (r[:, None] - r[None, :] + w - 1) * (2 * w - 1) + (c[:, None] - c[None, :] + w - 1)
+
+    def attn_mask(self, i: int) -> "torch.Tensor":
+        """(windows, window^2, window^2) float32 mask of the shifted blocks of stage i, by the closed formula: 0 where the two tokens
+        lie in the same region of the rolled grid, -100 elsewhere."""
+        import torch
+        g, w, sh = self.grid(i), self.window, self.window // 2
+        y = torch.arange(g)
+        reg1 = (y >= g - w).long() + (y >= g - sh).long()
+        reg = (reg1[:, None] * 3 + reg1[None, :]).reshape(g // w, w, g // w, w).permute(0, 2, 1, 3).reshape(-1, w * w)
+        return torch.where(reg[:, :, None] == reg[:, None, :], 0.0, -100.0).float()
+
+    def macs_per_frame(self) -> int:
+        total = self.tokens(0) * self.dim * self.in_chans * self.patch ** 2
+        for i in range(self.stages):
+            T, D = self.tokens(i), self.width(i)
+            total += self.depths[i] * (T * D * 12 * D + 2 * T * min(self.window, self.grid(i)) ** 2 * D)
+            if i + 1 < self.stages:
+                total += (T // 4) * 8 * D * D
+        return total
+
+    def workspace_bytes(self, hook_stages: Sequence[int], frames: int) -> int:
+        """Device bytes `i2v_swin_create` plans for these hooked stages and `frames` frames (the formula of csrc/i2v_swin.cpp: weights of
+        the stages run; patches, embedding and its LayerNorm statistics; per block the input stream, qkv, the mid stream, the fc1
+        pre-activation and four statistics per token; per stage its output stream; per merging the gathered rows and their statistics;
+        the shared scratch; one gradient view per hook)."""
+        F, ns = frames, max(hook_stages) + 1
+        KP, T0, D0 = self.in_chans * self.patch ** 2, self.tokens(0), self.dim
+        weights = D0 * KP + 3 * D0
+        acts = F * T0 * (KP + D0 + 2)
+        for i in range(ns):
+            D, FT = self.width(i), F * self.tokens(i)
+            weights += self.depths[i] * (12 * D * D + 13 * D + self.n_index * self.heads[i])
+            acts += self.depths[i] * (9 * FT * D + 4 * FT) + FT * D
+            if i + 1 < ns:
+                weights += 8 * D + 8 * D * D
+                acts += FT * D + 2 * (FT // 4)
+        acts += 9 * F * T0 * D0
+        acts += sum(F * self.hook_dim(s) for s in hook_stages)
+        return 4 * (weights + acts)
+
+
+def is_swin_name(model_name: str) -> bool:
+    """A name of timm's Swin vocabulary, served (`SWIN_MODELS`) or not: `graphs.build` routes these to `swin_named`, which refuses the
+    ones that are not offered with a message that lists the served names."""
+    return model_name in SWIN_MODELS or model_name.startswith("swin_")
+
+
+def swin_named(model_name: str, in_hw=(224, 224)) -> SwinSpec:
+    """Any row of `SWIN_MODELS`, at 224 x 224 only.  Refused, each with the reason: the window-12 384 x 384 models and every other input
+    size, the `in22k` checkpoints, and names outside the table."""
+    served = "served: " + ", ".join(SWIN_MODELS)
+    if model_name not in SWIN_MODELS:
+        if "384" in model_name or "window12" in model_name:
+            why = "the window-12 384 x 384 models are not offered (224 x 224 with window 7 only)"
+        elif "in22k" in model_name:
+            why = "the in22k checkpoints (21841-class heads) are not offered"
+        else:
+            why = "not a model of this table"
+        raise ValueError(f"Swin surrogate {model_name!r}: {why}; {served}")
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}): its window-7 stages need "
+                         "the 56 / 28 / 14 / 7 grids")
+    dim, depths, heads = SWIN_MODELS[model_name]
+    return SwinSpec(model_name, 224, 4, 3, dim, 7, depths, heads)
+
+
+def swin_tiny(in_hw=(64, 64)) -> SwinSpec:
+    """The same topology at test size ("swin_test": not timm's `swin_tiny_patch4_window7_224`): patch 4, window 4, C = 16, depths (2, 2),
+    heads (1, 2), head width 16.  A 64 x 64 frame is a 16 x 16 grid of 16 windows, then 8 x 8 with 4: both blocks of both stages are real,
+    the shifted one included, and there is one patch merging.  Square frames of a multiple of 32 pixels."""
+    if in_hw[0] != in_hw[1] or in_hw[0] % 32:
+        raise ValueError(f"the test-size Swin takes square frames of a multiple of 32 pixels (got {tuple(in_hw)})")
+    return SwinSpec("swin_test", int(in_hw[0]), 4, 3, 16, 4, (2, 2), (1, 2))
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -876,6 +1075,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return densenet(48, (6, 12, 36, 24), 96, 4, in_hw, "densenet161")
     if is_vit_name(model_name):         # extension: the transformer surrogate of `get_vits()` (TPAMI_attack.py:88-98) and its timm family
         return vit_named(model_name, in_hw)
+    if is_swin_name(model_name):        # extension: timm's Swin Transformer family (hierarchical, windowed attention)
+        return swin_named(model_name, in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -901,4 +1102,6 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
     if model_name in VIT_MODELS:        # one test-size twin per token layout: plain, distilled (2 prefix tokens), patch 32
         patch, _, _, _, _, n_prefix = VIT_MODELS[model_name]
         return vit_tiny(in_hw, n_prefix, patch)
+    if model_name in SWIN_MODELS:
+        return swin_tiny(in_hw)
     return build(model_name, in_hw)

@@ -150,6 +150,30 @@ _VIT_PROTOS = {
 VIT_EXPORTS = tuple(_VIT_PROTOS)
 
 
+class SwinConfig(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("img", "patch", "in_chans", "dim", "window", "stages")]
+                + [("depths", C.c_int32 * 4), ("heads", C.c_int32 * 4), ("ln_eps", C.c_float)])
+
+
+# The Swin surrogates (`include/i2v_swin.h`): a header of its own as well, bound on the product library only.
+_SWIN_PROTOS = {
+    "i2v_swin_create": ([_I, C.POINTER(SwinConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    "i2v_swin_destroy": ([_P], _I),
+    "i2v_swin_workspace_bytes": ([_P], _L),
+    "i2v_swin_forward": ([_P, _P, _I, _P], _I),
+    "i2v_swin_backward": ([_P, _P, _I, _P], _I),
+    "i2v_swin_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+    "i2v_swin_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    "i2v_swin_window_attention_f32": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    "i2v_swin_window_attention_bwd_f32": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    "i2v_swin_merge_f32": ([_P, _I, _I, _I, _I, _P, _P], _I),
+    "i2v_swin_merge_bwd_f32": ([_P, _I, _I, _I, _I, _P, _I, _P], _I),
+    "i2v_swin_embed_f32": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P], _I),
+    "i2v_swin_embed_bwd_f32": ([_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P], _I),
+}
+SWIN_EXPORTS = tuple(_SWIN_PROTOS)
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
@@ -174,6 +198,7 @@ def load():
             raise I2VError(f"{path} reports backend {lib.i2v_backend()!r}, expected {HIP_BACKEND!r}")
         bind(lib, _LOADER_PROTOS)
         bind(lib, _VIT_PROTOS)
+        bind(lib, _SWIN_PROTOS)
         _lib = lib
     return _lib
 

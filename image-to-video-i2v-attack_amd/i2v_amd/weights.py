@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import Graph, VitSpec
+from .graphs import Graph, SwinSpec, VitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -44,9 +44,51 @@ def _vit_synthetic(spec: VitSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _swin_synthetic(spec: SwinSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained Swin, drawn per key: matrices of std 0.02 clamped at 2 std as timm initialises them, except qkv at
+    width^-0.5, which puts the attention logits at O(1) at every stage's width (96 .. 1536), and the relative-position bias table at
+    std 0.5, so that the bias visibly shapes the softmax; LayerNorm gains near 1; small biases.  Each block then adds a few tenths to a
+    unit-variance stream, which stays O(1) through swin_small's 24 blocks (the tests check the hooks' spread)."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.endswith("relative_position_bias_table"):
+            sd[k] = torch.randn(*shp, generator=g).clamp_(-2.0, 2.0) * 0.5
+        elif k.endswith(("norm1.weight", "norm2.weight", "norm.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            std = shp[1] ** -0.5 if k.endswith("attn.qkv.weight") else 0.02
+            sd[k] = torch.randn(*shp, generator=g).clamp_(-2.0, 2.0) * std
+    return sd
+
+
+def check_swin_buffers(spec: SwinSpec, sd, where: str) -> None:
+    """timm's Swin checkpoints carry the buffers `relative_position_index` and `attn_mask`; they are computed from the geometry here
+    and never loaded, so one that differs describes another model: refused by key name."""
+    idx = spec.relative_position_index()
+    for i in range(spec.stages):
+        for j in range(spec.depths[i]):
+            p = f"layers.{i}.blocks.{j}."
+            k = p + "attn.relative_position_index"
+            if k in sd and not (tuple(sd[k].shape) == tuple(idx.shape) and torch.equal(sd[k].long(), idx)):
+                raise ValueError(f"{where}: buffer {k} differs from the index computed for window {spec.window}")
+            k = p + "attn_mask"
+            if k in sd and sd[k] is not None:
+                if spec.shift(i, j) == 0:
+                    raise ValueError(f"{where}: buffer {k} is a mask, but block {j} of stage {i} is not shifted")
+                want = spec.attn_mask(i)
+                if not (tuple(sd[k].shape) == tuple(want.shape) and torch.equal(sd[k].float(), want)):
+                    raise ValueError(f"{where}: buffer {k} differs from the mask computed for a {spec.grid(i)} x {spec.grid(i)} grid, "
+                                     f"window {spec.window}, shift {spec.shift(i, j)}")
+
+
 def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]:
     if isinstance(graph, VitSpec):
         return _vit_synthetic(graph, seed)
+    if isinstance(graph, SwinSpec):
+        return _swin_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op != "conv":
@@ -112,6 +154,8 @@ def load_state_dict(graph: Graph, seed=None, keep_head: bool = False) -> Dict[st
         missing = [k for k in shapes if k not in sd]
         if missing:
             raise KeyError(f"{path}: missing keys {missing[:4]}...")
+        if isinstance(graph, SwinSpec):
+            check_swin_buffers(graph, sd, path)
         for k, shp in shapes.items():
             if tuple(sd[k].shape) != tuple(shp):
                 raise ValueError(f"{path}: {k} has shape {tuple(sd[k].shape)}, expected {shp}")

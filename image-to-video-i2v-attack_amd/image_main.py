@@ -41,7 +41,8 @@ def arg_parse(argv=None, ucf101=False):
     parser.add_argument("--dropout", type=float, default=0.1, help="")
     parser.add_argument("--direction_image_model", type=str, default="resnet",
                         help="resnet, densenet, squeezenet, vgg, alexnet (added: resnet50, densenet121, densenet161, and timm's plain "
-                             "ViT / DeiT names at 224 x 224: " + ", ".join(graphs.VIT_MODELS) + ")")
+                             "ViT / DeiT names at 224 x 224: " + ", ".join(graphs.VIT_MODELS) + "; and timm's Swin names at 224 x 224: "
+                             + ", ".join(graphs.SWIN_MODELS) + ")")
     # additions (not in the reference)
     parser.add_argument("--anno", type=str, default=os.environ.get("I2V_ANNO", ""),
                         help="sample list csv `path,gt_label,clip_index` (the reference's kinetics400_attack_samples.csv, utils.py:29); without it 400 synthetic names with labels 0..399 are used")
@@ -79,6 +80,15 @@ def arg_parse(argv=None, ucf101=False):
             parser.error(f"--direction_image_model: {e}")
         if args.depth not in spec.hooks:
             parser.error(f"--depth {args.depth}: {spec.arch} hooks depths {sorted(spec.hooks)} (blocks {[spec.hooks[d] for d in sorted(spec.hooks)]})")
+    if args.attack_method in ("ImageGuidedStd_Adam", "ImageGuidedFMDirection_Adam") and graphs.is_swin_name(args.direction_image_model):
+        # a Swin name: the same early refusal, and --depth checked against the spec's stages
+        try:
+            spec = graphs.swin_named(args.direction_image_model, (args.hw, args.hw))
+        except ValueError as e:
+            parser.error(f"--direction_image_model: {e}")
+        if args.depth not in spec.hooks:
+            parser.error(f"--depth {args.depth}: {spec.arch} hooks depths {sorted(spec.hooks)} (the last block of stages "
+                         f"{[spec.hooks[d] for d in sorted(spec.hooks)]})")
     if args.synthetic_weights:
         os.environ["I2V_SYNTHETIC_WEIGHTS"] = "1"
     args.adv_path = os.path.join(OPT_PATH, "{}-{}-{}-{}".format("Image", args.attack_method, args.step, args.file_prefix))

@@ -1,0 +1,341 @@
+"""CPU: timm's Swin Transformer family as image surrogates -- for every served name the spec, grids, widths, heads,
+hook sizes, key manifest and checkpoint loading; the refusals; the computed buffers; the restatement (tests/swin_reference.py) pinned by
+construction; the test-size twin; the attack classes and the CLI; and the new native symbols."""
+import ctypes as C
+import os
+
+import pytest
+import torch
+
+from i2v_amd import attacks, graphs, weights
+from i2v_amd import lib as _lib
+from tests import swin_reference as sr
+from tests import vit_family_reference as fam
+from tests.swin_reference import SwinReference
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+#: the issue's table: name -> (C, depths, heads)
+TABLE = {
+    "swin_tiny_patch4_window7_224": (96, (2, 2, 6, 2), (3, 6, 12, 24)),
+    "swin_small_patch4_window7_224": (96, (2, 2, 18, 2), (3, 6, 12, 24)),
+    "swin_base_patch4_window7_224": (128, (2, 2, 18, 2), (4, 8, 16, 32)),
+    "swin_large_patch4_window7_224": (192, (2, 2, 18, 2), (6, 12, 24, 48)),
+}
+NAMES = sorted(TABLE)
+TINY = "swin_tiny_patch4_window7_224"
+BLOCK_KEYS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.relative_position_bias_table", "attn.proj.weight",
+              "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+
+
+def _rand(*shape, seed=0):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_spec_grids_widths_heads_and_hooks_of_every_name(name):
+    dim, depths, heads = TABLE[name]
+    spec = graphs.build(name)
+    assert isinstance(spec, graphs.SwinSpec) and spec.arch == name and spec.video is False and spec.in_hw == (224, 224)
+    assert (spec.img, spec.patch, spec.in_chans, spec.dim, spec.window, spec.depths, spec.heads, spec.ln_eps) == \
+        (224, 4, 3, dim, 7, depths, heads, 1e-5)
+    assert [spec.grid(i) for i in range(4)] == [56, 28, 14, 7]
+    assert [spec.width(i) for i in range(4)] == [dim, 2 * dim, 4 * dim, 8 * dim]
+    assert all(spec.width(i) // spec.heads[i] == 32 for i in range(4))
+    assert {d: spec.hook_for(d) for d in (1, 2, 3, 4)} == {1: 0, 2: 1, 3: 2, 4: 3}
+    assert [spec.hook_dim(spec.hook_for(d)) for d in (1, 2, 3, 4)] == [3136 * dim, 784 * 2 * dim, 196 * 4 * dim, 49 * 8 * dim]
+    if name == TINY:
+        assert [spec.hook_dim(i) for i in range(4)] == [301056, 150528, 75264, 37632]
+    assert [[spec.shift(i, j) for j in range(2)] for i in range(4)] == [[0, 3], [0, 3], [0, 3], [0, 0]]      # stage 3: the window is the grid
+    assert spec.hook_for(3, whole_module=True) == 2
+    with pytest.raises(KeyError):
+        spec.hook_for(5)
+    assert graphs.swin_named(name, (224, 224)) == spec and graphs.is_swin_name(name) and not graphs.is_vit_name(name)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_key_manifest_and_shapes_of_every_name(name):
+    dim, depths, heads = TABLE[name]
+    shapes = graphs.build(name).param_shapes()
+    keys = ["patch_embed.proj.weight", "patch_embed.proj.bias", "patch_embed.norm.weight", "patch_embed.norm.bias"]
+    for i in range(4):
+        keys += [f"layers.{i}.blocks.{j}.{k}" for j in range(depths[i]) for k in BLOCK_KEYS]
+        if i < 3:
+            keys += [f"layers.{i}.downsample.norm.weight", f"layers.{i}.downsample.norm.bias", f"layers.{i}.downsample.reduction.weight"]
+    assert list(shapes) == keys
+    assert shapes["patch_embed.proj.weight"] == (dim, 3, 4, 4) and shapes["patch_embed.norm.bias"] == (dim,)
+    for i in range(4):
+        D = dim << i
+        per_block = [(D,), (D,), (3 * D, D), (3 * D,), (169, heads[i]), (D, D), (D,), (D,), (D,), (4 * D, D), (4 * D,), (D, 4 * D), (D,)]
+        for j in (0, depths[i] - 1):
+            assert [shapes[f"layers.{i}.blocks.{j}.{k}"] for k in BLOCK_KEYS] == per_block
+        if i < 3:
+            assert shapes[f"layers.{i}.downsample.reduction.weight"] == (2 * D, 4 * D)
+            assert shapes[f"layers.{i}.downsample.norm.weight"] == (4 * D,)
+    assert "layers.3.downsample.reduction.weight" not in shapes and "layers.0.downsample.reduction.bias" not in shapes
+    assert not any(k.startswith(("norm.", "head.")) or "relative_position_index" in k or "attn_mask" in k for k in shapes)
+
+
+def test_refusals_name_the_reason_and_list_the_served_names():
+    for name, why in (("swin_base_patch4_window12_384", "384"), ("swin_large_patch4_window12_384_in22k", "384"),
+                      ("swin_base_patch4_window7_224_in22k", "in22k"), ("swin_large_patch4_window7_224_in22k", "in22k"),
+                      ("swin_huge_patch4_window7_224", "not a model"), ("swin_v2_tiny", "not a model")):
+        with pytest.raises(ValueError, match=why) as ei:
+            graphs.build(name)
+        assert all(n in str(ei.value) for n in NAMES)
+        with pytest.raises(ValueError):
+            graphs.swin_named(name)
+        with pytest.raises(ValueError):
+            graphs.build_tiny(name)
+    for name in NAMES:
+        for hw in ((384, 384), (112, 112), (224, 192)):
+            with pytest.raises(ValueError, match="224 x 224"):
+                graphs.build(name, hw)
+
+
+def test_existing_names_behave_as_before():
+    with pytest.raises(UnboundLocalError):
+        graphs.build("transformer")
+    with pytest.raises(ValueError, match="384") as ei:
+        graphs.build("vit_base_patch16_384")
+    assert all(n in str(ei.value) for n in graphs.VIT_MODELS) and not any(n in str(ei.value) for n in NAMES)
+    assert not set(graphs.VIT_MODELS) & set(graphs.SWIN_MODELS) and set(graphs.SWIN_MODELS) == set(NAMES)
+    assert {n: graphs.SWIN_MODELS[n] for n in NAMES} == TABLE
+    assert isinstance(graphs.build(graphs.VIT_NAME), graphs.VitSpec) and graphs.build("resnet").arch == "resnet101"
+
+
+def _checkpoint(spec):
+    """A checkpoint of the spec's shapes that costs no memory on disk: every tensor is one zero expanded to its shape."""
+    sd = {k: torch.zeros(1).expand(shp) for k, shp in spec.param_shapes().items()}
+    top = spec.width(spec.stages - 1)
+    sd.update({"norm.weight": torch.ones(top), "norm.bias": torch.zeros(top), "head.weight": torch.zeros(1).expand(1000, top),
+               "head.bias": torch.zeros(1000)})
+    return sd
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_checkpoint_of_every_name_loads_from_its_own_file(name, tmp_path, monkeypatch):
+    spec = graphs.build(name)
+    monkeypatch.delenv("I2V_SYNTHETIC_WEIGHTS", raising=False)
+    monkeypatch.setenv("I2V_WEIGHTS_DIR", str(tmp_path))
+    with pytest.raises(weights.MissingWeights, match=name):
+        weights.load_state_dict(spec)
+    sd = _checkpoint(spec)
+    sd["patch_embed.norm.weight"] = torch.full((spec.dim,), 0.25)
+    # the buffers timm saves, equal to the computed ones: accepted and not returned
+    sd["layers.0.blocks.0.attn.relative_position_index"] = sr.relative_position_index(7)
+    sd["layers.1.blocks.1.attn_mask"] = sr.shift_mask(28, 28, 7, 3, torch.float32)
+    torch.save(sd, tmp_path / f"{name}.pth")
+    got = weights.load_state_dict(spec)
+    assert list(got) == list(spec.param_shapes())
+    assert all(tuple(got[k].shape) == shp and got[k].is_contiguous() for k, shp in spec.param_shapes().items())
+    assert float(got["patch_embed.norm.weight"].mean()) == 0.25
+    for n in NAMES:
+        if n != name:
+            with pytest.raises(weights.MissingWeights, match=n):
+                weights.load_state_dict(graphs.build(n))
+
+
+def test_wrong_buffers_and_missing_or_misshaped_keys_are_refused_by_key(tmp_path, monkeypatch):
+    spec = graphs.build(TINY)
+    monkeypatch.setenv("I2V_WEIGHTS_DIR", str(tmp_path))
+    sd = _checkpoint(spec)
+    path = tmp_path / f"{TINY}.pth"
+    idx = sr.relative_position_index(7)
+    torch.save(dict(sd, **{"layers.2.blocks.3.attn.relative_position_index": idx.T.contiguous() + 1}), path)
+    with pytest.raises(ValueError, match=r"layers\.2\.blocks\.3\.attn\.relative_position_index"):
+        weights.load_state_dict(spec)
+    torch.save(dict(sd, **{"layers.0.blocks.1.attn_mask": sr.shift_mask(56, 56, 7, 2, torch.float32)}), path)     # another shift's mask
+    with pytest.raises(ValueError, match=r"layers\.0\.blocks\.1\.attn_mask"):
+        weights.load_state_dict(spec)
+    torch.save(dict(sd, **{"layers.0.blocks.0.attn_mask": sr.shift_mask(56, 56, 7, 3, torch.float32)}), path)     # a mask on an unshifted block
+    with pytest.raises(ValueError, match=r"layers\.0\.blocks\.0\.attn_mask"):
+        weights.load_state_dict(spec)
+    short = dict(sd)
+    del short["layers.1.downsample.reduction.weight"]
+    torch.save(short, path)
+    with pytest.raises(KeyError, match=r"layers\.1\.downsample\.reduction\.weight"):
+        weights.load_state_dict(spec)
+    torch.save(dict(sd, **{"layers.0.blocks.0.attn.relative_position_bias_table": torch.zeros(169, 4)}), path)
+    with pytest.raises(ValueError, match="relative_position_bias_table"):
+        weights.load_state_dict(spec)
+
+
+def test_synthetic_weights_under_the_opt_in_only(monkeypatch, tmp_path):
+    monkeypatch.setenv("I2V_WEIGHTS_DIR", str(tmp_path))
+    monkeypatch.delenv("I2V_SYNTHETIC_WEIGHTS", raising=False)
+    spec = graphs.build(TINY)
+    with pytest.raises(weights.MissingWeights):
+        weights.load_state_dict(spec)
+    sd = weights.load_state_dict(spec, seed=3)
+    assert {k: tuple(v.shape) for k, v in sd.items()} == spec.param_shapes()
+    assert all(torch.equal(sd[k], v) for k, v in weights.synthetic_state_dict(spec, 3).items())
+    assert float(sd["layers.0.blocks.0.attn.relative_position_bias_table"].std()) > 0.4          # large enough that B matters
+    monkeypatch.setenv("I2V_SYNTHETIC_WEIGHTS", "1")
+    assert list(weights.load_state_dict(spec)) == list(sd)
+
+
+# ---- the restatement, pinned by construction --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ws", [4, 7])
+def test_bias_index_equals_the_direct_formula(ws):
+    idx = sr.relative_position_index(ws)
+    for i in range(ws * ws):
+        for j in range(ws * ws):
+            assert int(idx[i, j]) == (i // ws - j // ws + ws - 1) * (2 * ws - 1) + (i % ws - j % ws + ws - 1)
+    spec = graphs.build(TINY) if ws == 7 else graphs.build_tiny(TINY)
+    assert torch.equal(spec.relative_position_index(), idx) and int(idx.max()) == spec.n_index - 1 and int(idx.min()) == 0
+
+
+@pytest.mark.parametrize("g,ws,shift", [(14, 7, 3), (8, 4, 2)])
+def test_mask_equals_the_brute_force_region_test(g, ws, shift):
+    """Two tokens of a window of the rolled grid may attend to each other exactly when they were neighbours before the roll: when
+    neither axis wraps between them, i.e. both lie on the same side of the seam at rolled coordinate g - shift, on each axis -- tested
+    for every token pair of every window.  (In the interior windows no seam passes: no mask.)"""
+    m = sr.shift_mask(g, g, ws, shift)
+    nw = g // ws
+    for wy in range(nw):
+        for wx in range(nw):
+            for i in range(ws * ws):
+                for j in range(ws * ws):
+                    yi, xi, yj, xj = wy * ws + i // ws, wx * ws + i % ws, wy * ws + j // ws, wx * ws + j % ws
+                    same = ((yi >= g - shift) == (yj >= g - shift)) and ((xi >= g - shift) == (xj >= g - shift))
+                    assert float(m[wy * nw + wx, i, j]) == (0.0 if same else -100.0)
+    spec = graphs.build(TINY) if ws == 7 else graphs.build_tiny(TINY)
+    assert torch.equal(spec.attn_mask(2 if ws == 7 else 1).double(), m)           # the closed formula of the spec
+
+
+def _stage_input(spec, i, n=2, seed=1):
+    return _rand(n, spec.tokens(i), spec.width(i), seed=seed)
+
+
+def test_unshifted_zero_bias_attention_is_vit_attention_per_window():
+    spec = graphs.build_tiny(TINY, (64, 64))
+    sd = {k: v.double() for k, v in weights.synthetic_state_dict(spec, 0).items()}
+    g, ws, H, D = spec.grid(0), 4, spec.heads[0], spec.width(0)
+    qkv = _rand(2, g * g, 3 * D, seed=2)
+    got = sr.window_attention(qkv, g, g, ws, 0, H, torch.zeros(49, H, dtype=torch.float64))
+    w = sr.window_partition(qkv.reshape(2, g, g, 3 * D), ws)                       # every window a "frame" of 16 tokens
+    q, k, v = w.reshape(-1, 16, 3, H, D // H).permute(2, 0, 3, 1, 4)
+    o = (torch.softmax((q @ k.transpose(-2, -1)) * (D // H) ** -0.5, -1) @ v).transpose(1, 2).reshape(-1, 16, D)    # fam.block's attention
+    want = sr.window_reverse(o, ws, g, g).reshape(2, g * g, D)
+    assert float((got - want).abs().max()) <= 1e-12
+    # and through a whole block: fam.block on the windows with the Swin block's weights under the ViT key names
+    x = _stage_input(spec, 0)
+    vsd = {k.replace("layers.0.blocks.0.", "blocks.0."): v for k, v in sd.items()}
+    vspec = graphs.VitSpec("probe", 16, 4, 3, D, H, 4 * D, 1, ln_eps=spec.ln_eps)
+    per_window = fam.block(sr.window_partition(x.reshape(2, g, g, D), ws), vsd, vspec, 0)
+    whole = sr.block(x, sd, spec, 0, 0, zero_bias=True)
+    assert float((whole - sr.window_reverse(per_window, ws, g, g).reshape(2, g * g, D)).abs().max()) <= 1e-12
+
+
+def test_unshifted_block_commutes_with_a_roll_by_a_whole_window():
+    spec = graphs.build(TINY)
+    sd = {k: v.double() for k, v in weights.synthetic_state_dict(spec, 0).items() if k.startswith("layers.2.blocks.0.")}
+    x = _stage_input(spec, 2, n=1)
+    g, D = spec.grid(2), spec.width(2)
+    roll = lambda t: torch.roll(t.reshape(1, g, g, D), (7, 7), (1, 2)).reshape(1, g * g, D)      # noqa: E731
+    assert float((sr.block(roll(x), sd, spec, 2, 0) - roll(sr.block(x, sd, spec, 2, 0))).abs().max()) <= 1e-12
+
+
+@pytest.mark.parametrize("tiny", [True, False])
+def test_shifted_block_is_the_unshifted_one_on_the_rolled_input_where_no_mask_applies(tiny):
+    spec = graphs.build_tiny(TINY, (64, 64)) if tiny else graphs.build(TINY)
+    i = 0 if tiny else 2
+    sd = {k: v.double() for k, v in weights.synthetic_state_dict(spec, 0).items() if k.startswith(f"layers.{i}.blocks.1.")}
+    g, D, ws, sh = spec.grid(i), spec.width(i), spec.window, spec.window // 2
+    x = _stage_input(spec, i, n=1, seed=3)
+    rolled = torch.roll(x.reshape(1, g, g, D), (-sh, -sh), (1, 2)).reshape(1, g * g, D)
+    plain = sr.block(rolled, sd, spec, i, 1, shift=0)                              # in rolled coordinates
+    shifted = torch.roll(sr.block(x, sd, spec, i, 1).reshape(1, g, g, D), (-sh, -sh), (1, 2))
+    plain = plain.reshape(1, g, g, D)
+    free = g - ws                                                                  # windows of the first rows and columns carry no mask
+    assert float((shifted[:, :free, :free] - plain[:, :free, :free]).abs().max()) <= 1e-12
+    assert float((shifted[:, free:, free:] - plain[:, free:, free:]).abs().max()) > 1e-6       # ... and the masked corner differs
+
+
+def test_patch_merging_and_its_adjoint_are_a_permutation():
+    x = _rand(2, 8 * 6, 5, seed=4).requires_grad_(True)
+    m = sr.patch_merge_gather(x, 8, 6)
+    assert m.shape == (2, 12, 20)
+    assert torch.equal(torch.autograd.grad(m, x, m.detach())[0], x.detach())       # adjoint after gather: the identity
+    g = x.detach().reshape(2, 8, 6, 5)
+    assert torch.equal(m[:, 4].detach(), torch.cat([g[:, 2, 2], g[:, 3, 2], g[:, 2, 3], g[:, 3, 3]], -1))    # cell (1, 1): (0,0) (1,0) (0,1) (1,1)
+
+
+def test_test_size_twin():
+    t = graphs.build_tiny(TINY, (64, 64))
+    assert t == graphs.build_tiny("swin_large_patch4_window7_224", (64, 64))
+    assert t.arch == "swin_test" and t.arch not in graphs.SWIN_MODELS and not t.arch.startswith("swin_tiny")
+    assert (t.patch, t.window, t.dim, t.depths, t.heads) == (4, 4, 16, (2, 2), (1, 2))
+    assert [t.grid(i) for i in range(2)] == [16, 8] and [t.width(i) // t.heads[i] for i in range(2)] == [16, 16]
+    assert [[t.shift(i, j) for j in range(2)] for i in range(2)] == [[0, 2], [0, 2]] and t.hooks == {1: 0, 2: 1}
+    assert [k for k in t.param_shapes() if "downsample" in k] == [f"layers.0.downsample.{s}" for s in ("norm.weight", "norm.bias", "reduction.weight")]
+    with pytest.raises(ValueError):
+        graphs.build_tiny(TINY, (48, 48))
+    sd = weights.synthetic_state_dict(t, 0)
+    ref = SwinReference(t, sd, [0, 1])
+    f = ref.forward(torch.randn(2, 3, 64, 64))
+    assert [tuple(a.shape) for a in f] == [(2, 256 * 16), (2, 64 * 32)]
+    assert ref.backward([torch.ones_like(a) for a in f]).shape == (2, 3, 64, 64)
+    # the softmax is visibly non-uniform, and the bias is part of why
+    x = _rand(1, 256, 16, seed=5)
+    dsd = {k: v.double() for k, v in sd.items()}
+    assert float((sr.block(x, dsd, t, 0, 0) - sr.block(x, dsd, t, 0, 0, zero_bias=True)).abs().max()) > 1e-3
+
+
+def test_synthetic_stream_stays_of_order_one_through_swin_small():
+    spec = graphs.build("swin_small_patch4_window7_224")
+    sd = weights.synthetic_state_dict(spec, 0)
+    f = SwinReference(spec, sd, [0, 1, 2, 3], dtype=torch.float32).forward(torch.randn(1, 3, 224, 224))
+    assert all(0.1 < float(a.std()) < 10 for a in f), [float(a.std()) for a in f]
+
+
+def test_attack_classes_and_the_cli_take_the_names(tmp_path, monkeypatch):
+    for name in NAMES:
+        atk = attacks.ImageGuidedFMDirection_Adam([name], depth=4, step_size=0.005, steps=2, weight_seed=0)
+        assert atk.model_names == [name]
+    attacks.ImageGuidedStd_Adam(["swin_base_patch4_window7_224"], depth=1, step_size=0.005, weight_seed=0)
+    attacks.ImageGuidedFML2_Adam_MultiModels(["resnet", "deit_base_distilled_patch16_224", TINY],
+                                             depths={"resnet": 2, "deit_base_distilled_patch16_224": 3, TINY: 1}, weight_seed=0)
+    attacks.AENS_I2V_MF([TINY, "vgg", "vit_small_patch32_224"], depths={TINY: [2, 4], "vgg": [2, 3], "vit_small_patch32_224": [1]},
+                        step_size=0.005, weight_seed=0)
+    with pytest.raises(KeyError):
+        attacks.ImageGuidedFMDirection_Adam([TINY], depth=5, step_size=0.005, weight_seed=0)
+    with pytest.raises(ValueError, match="384"):
+        attacks.ImageGuidedFMDirection_Adam(["swin_base_patch4_window12_384"], depth=2, step_size=0.005, weight_seed=0)
+    import image_main
+    monkeypatch.setattr(image_main, "OPT_PATH", str(tmp_path))
+    base = ["--attack_method", "ImageGuidedFMDirection_Adam", "--step", "2"]
+    a = image_main.arg_parse(base + ["--direction_image_model", "swin_large_patch4_window7_224", "--depth", "4"])
+    assert image_main.build_attack(a).model_names == ["swin_large_patch4_window7_224"]
+    for bad in (["--direction_image_model", "swin_base_patch4_window12_384"], ["--direction_image_model", TINY, "--depth", "5"],
+                ["--direction_image_model", TINY, "--hw", "112"], ["--direction_image_model", "swin_base_patch4_window7_224_in22k"]):
+        with pytest.raises(SystemExit):
+            image_main.arg_parse(base + bad)
+
+
+def test_planned_bytes_are_counted_in_64_bits_and_grow_as_the_design_states():
+    big = graphs.build("swin_large_patch4_window7_224")
+    assert 2 ** 34 < big.workspace_bytes([0, 1, 2, 3], 128) < 2 ** 36
+    t = graphs.build(TINY)
+    # one more frame costs, per block of stage i, 9 T D + 4 T floats: 36 T D + 16 T bytes
+    for i in range(4):
+        per = lambda hooks: t.workspace_bytes(hooks, 3) - t.workspace_bytes(hooks, 2)       # noqa: E731
+        T, D = t.tokens(i), t.width(i)
+        assert t.depths[i] * (36 * T * D + 16 * T) < per([i]) - (per([i - 1]) if i else 0)
+    assert t.macs_per_frame() == pytest.approx(4.49e9, rel=0.01)                   # the 4.5 GMACs swin_tiny is known by
+
+
+def test_new_native_symbols_are_exported_and_the_host_simulation_still_loads():
+    import __graft_entry__ as ge
+    for n in ("i2v_swin_create", "i2v_swin_destroy", "i2v_swin_workspace_bytes", "i2v_swin_forward", "i2v_swin_backward",
+              "i2v_swin_hook_info", "i2v_swin_read_hook", "i2v_swin_window_attention_f32", "i2v_swin_window_attention_bwd_f32",
+              "i2v_swin_merge_f32", "i2v_swin_merge_bwd_f32", "i2v_swin_embed_f32", "i2v_swin_embed_bwd_f32"):
+        assert n in _lib.SWIN_EXPORTS
+    cd = C.CDLL(ge.LIB)
+    assert all(hasattr(cd, n) for n in _lib.SWIN_EXPORTS)
+    assert not set(_lib.SWIN_EXPORTS) & (set(_lib.EXPORTS) | set(_lib.VIT_EXPORTS) | set(_lib.LOADER_EXPORTS))
+    assert "i2v_swin.hip" in ge.UNITS and "i2v_swin.cpp" in ge.UNITS
+    hs = C.CDLL(os.path.join(ROOT, "tests", "hostsim", "libi2v_hostsim.so"))
+    _lib.bind(hs)
+    assert hs.i2v_backend() == b"hostsim"
