@@ -1,57 +1,15 @@
 // Planner and executor of the ViT surrogate (include/i2v_vit.h): one arena per (net, max frames), the forward as a fixed launch sequence
-// up to the deepest hook, and the input-gradient pass -- no weight gradients, as the CNN path.  The kernels are in i2v_vit.hip.
-#include <hip/hip_runtime.h>
+// up to the deepest hook, and the input-gradient pass -- no weight gradients, as the CNN path.  The arena, the hook list and the pre-norm
+// block are shared with the Swin planner (i2v_xf.h); this file brings the embedding with its prefix rows, the attention over all tokens
+// with saved probabilities, and the ViT sizes.  The kernels are in i2v_vit.hip.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
 
 #include "../../include/i2v_vit.h"
-#include "i2v_kernels.h"
-#include "i2v_vit_kernels.h"
+#include "i2v_xf.h"
 
 namespace {
 
-int fail(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-int fail(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return i2v_api_fail(buf);
-}
-#define VCHK(expr) do { if ((expr) != 0) return 1; } while (0)
-#define HCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(e_)); } while (0)
-
 int probs_ld(int T) { return (T + 3) / 4 * 4; }
-
-// y (M, N) = x (M, K) W^T (+ bias) (+ residual), W (N, K)
-int linear(const float* x, int M, int K, const float* W, const float* bias, int N, const float* residual, float* y, float* gelu_out,
-           hipStream_t s) {
-    VitGemm g{};
-    g.A = x; g.a_sm = K; g.a_sk = 1;
-    g.B = W; g.b_sk = 1; g.b_sn = K;
-    g.C = y; g.c_sm = N;
-    g.bias = bias; g.R = residual; g.C2 = gelu_out;
-    g.M = M; g.N = N; g.K = K; g.batch = 1; g.nb_in = 1; g.alpha = 1.f;
-    g.mode = gelu_out ? VIT_EPI_GELU : VIT_EPI_PLAIN;
-    return vit_gemm(g, s);
-}
-
-// dx (M, K) = dy (M, N) W (* gelu'(pre))
-int linear_bwd(const float* dy, int M, int N, const float* W, int K, const float* pre, float* dx, hipStream_t s) {
-    VitGemm g{};
-    g.A = dy; g.a_sm = N; g.a_sk = 1;
-    g.B = W; g.b_sk = K; g.b_sn = 1;
-    g.C = dx; g.c_sm = K;
-    g.H = pre;
-    g.M = M; g.N = K; g.K = N; g.batch = 1; g.nb_in = 1; g.alpha = 1.f;
-    g.mode = pre ? VIT_EPI_GELU_BWD : VIT_EPI_PLAIN;
-    return vit_gemm(g, s);
-}
 
 // batch b = frame * heads + head.  qkv (F, T, 3C): q of head h at column h*dh, k at C + h*dh, v at 2C + h*dh; probs (F, heads, T, ld)
 int attention(const float* qkv, int F, int T, int heads, int dh, float scale, float* P, float* out, hipStream_t s) {
@@ -126,63 +84,36 @@ int embed_bwd(const float* dtok, int F, int Cin, int gsz, int P, const float* W,
     return vit_patchify(nullptr, patches, F, Cin, gsz, gsz, P, gimg, accumulate, s);
 }
 
-struct Block {
-    const float *n1w, *n1b, *qkvw, *qkvb, *projw, *projb, *n2w, *n2b, *fc1w, *fc1b, *fc2w, *fc2b;
-    float *x, *qkv, *P, *y, *h, *stats;        // saved per block: input stream, qkv, probabilities, mid stream, fc1 pre-activation, LN stats
-};
-
 }  // namespace
 
-struct i2v_vit {
+struct i2v_vit : XfNet {
     i2v_vit_config cfg{};
-    int device = 0, T = 0, gsz = 0, nb = 0, max_frames = 0, frames = 0, ld = 0, npre = 1;
+    int T = 0, gsz = 0, nb = 0, ld = 0, npre = 1;
     float scale = 0.f;
-    std::vector<void*> allocs;
     const float *pe_w = nullptr, *pe_b = nullptr, *prefix = nullptr, *pos = nullptr;
     std::vector<Block> blocks;
     float* x_top = nullptr;                      // stream after the last block run
-    float *t1 = nullptr, *t2 = nullptr, *dP = nullptr, *dqkv = nullptr, *G = nullptr, *patches = nullptr, *emb = nullptr;
-    std::vector<int> hook_block;
-    std::vector<float*> hook_grad;
-    int64_t bytes = 0, planned = 0;              // held so far; what the whole plan takes (weights, arena, hook gradients)
+    float *dP = nullptr, *patches = nullptr, *emb = nullptr;
 
-    float* alloc(int64_t n) {
-        void* p = nullptr;
-        if (hipMalloc(&p, (size_t)n * 4) != hipSuccess) return nullptr;
-        allocs.push_back(p);
-        bytes += n * 4;
-        return (float*)p;
-    }
-    int oom(const char* what) {                  // an allocation of the plan failed: say what the whole plan needs
-        (void)hipGetLastError();
-        return fail("i2v_vit_create: out of device memory (%s): the net needs %lld bytes for %d frames and %d blocks "
-                                "(%lld allocated when it failed); plan fewer frames or a shallower hook", what, (long long)planned,
-                                max_frames, nb, (long long)bytes);
-    }
-    ~i2v_vit() {
-        for (void* p : allocs) (void)hipFree(p);
-    }
     float* stream_after(int b) { return b + 1 < nb ? blocks[b + 1].x : x_top; }
+    BlockRun run(int frames, hipStream_t s) const {
+        return {frames, T, cfg.dim, cfg.mlp, (int64_t)max_frames * T, cfg.ln_eps, t1, t2, dqkv, G, s};
+    }
 };
 
 namespace {
 
 int vit_plan(i2v_vit* n, const float* const* w, int nw, const int32_t* hooks, int n_hooks) {
     const i2v_vit_config& c = n->cfg;
+    Arena& A = n->arena;
     if (c.img <= 0 || c.patch <= 0 || c.img % c.patch != 0 || c.patch % 4 != 0 || c.in_chans <= 0 || c.dim <= 0 || c.heads <= 0 ||
         c.dim % c.heads != 0 || c.dim % 4 != 0 || (c.dim / c.heads) % 4 != 0 || c.mlp <= 0 || c.mlp % 4 != 0 || c.blocks <= 0)
         return fail("i2v_vit_create: unsupported configuration (img %d patch %d dim %d heads %d mlp %d blocks %d)", c.img, c.patch, c.dim, c.heads,
                     c.mlp, c.blocks);
     if (n->npre < 1 || n->npre > 2) return fail("i2v_vit_create: %d prefix tokens (1: cls_token, or 2: cls_token and dist_token)", n->npre);
-    if (n_hooks <= 0) return fail("i2v_vit_create: no hooks");
-    int deepest = -1;
-    for (int i = 0; i < n_hooks; ++i) {
-        if (hooks[i] < 0 || hooks[i] >= c.blocks) return fail("i2v_vit_create: hook block %d outside 0..%d", hooks[i], c.blocks - 1);
-        for (int j = 0; j < i; ++j)
-            if (hooks[j] == hooks[i]) return fail("i2v_vit_create: block %d hooked twice", hooks[i]);
-        deepest = hooks[i] > deepest ? hooks[i] : deepest;
-    }
-    n->nb = deepest + 1;
+    const int deepest = Hooks::deepest(hooks, n_hooks, c.blocks, A);
+    if (deepest < 0) return 1;
+    n->nb = A.depth = deepest + 1;
     if (nw != 4 + 12 * n->nb) return fail("i2v_vit_create: %d weight arrays given, %d expected for %d blocks", nw, 4 + 12 * n->nb, n->nb);
     n->gsz = c.img / c.patch;
     n->T = n->npre + n->gsz * n->gsz;
@@ -199,37 +130,23 @@ int vit_plan(i2v_vit* n, const float* const* w, int nw, const int32_t* hooks, in
     const int64_t shared = FT * D + FT * D + FT * Hm + probs + FT * 3 * D + FT * D + F * NPt * KP + F * NPt * D;
     int64_t total = n->nb * per_block + shared + (int64_t)n_hooks * FT * D;
     for (int64_t v : sizes) total += v;
-    n->planned = total * 4;
-    std::vector<const float*> dev(sizes.size());
-    for (size_t i = 0; i < sizes.size(); ++i) {
-        if (!w[i]) return fail("i2v_vit_create: weight array %zu is null", i);
-        float* p = n->alloc(sizes[i]);
-        if (!p) return n->oom("weights");
-        HCHK(hipMemcpy(p, w[i], (size_t)sizes[i] * 4, hipMemcpyHostToDevice));
-        dev[i] = p;
-    }
+    VCHK(A.plan(total, FT));
+    std::vector<const float*> dev;
+    VCHK(A.upload(sizes, w, dev));
     n->pe_w = dev[0]; n->pe_b = dev[1]; n->prefix = dev[2]; n->pos = dev[3];
     n->blocks.resize(n->nb);
     for (int b = 0; b < n->nb; ++b) {
         Block& B = n->blocks[b];
-        const float* const* q = &dev[4 + 12 * b];
-        B.n1w = q[0]; B.n1b = q[1]; B.qkvw = q[2]; B.qkvb = q[3]; B.projw = q[4]; B.projb = q[5];
-        B.n2w = q[6]; B.n2b = q[7]; B.fc1w = q[8]; B.fc1b = q[9]; B.fc2w = q[10]; B.fc2b = q[11];
-        if (!(B.x = n->alloc(FT * D)) || !(B.qkv = n->alloc(FT * 3 * D)) || !(B.P = n->alloc(probs)) ||
-            !(B.y = n->alloc(FT * D)) || !(B.h = n->alloc(FT * Hm)) || !(B.stats = n->alloc(4 * FT)))
-            return n->oom("saved activations of a block");
+        B.weights(&dev[4 + 12 * b], &dev[8 + 12 * b]);
+        if (!(B.x = A.alloc(FT * D)) || !(B.qkv = A.alloc(FT * 3 * D)) || !(B.P = A.alloc(probs)) ||
+            !(B.y = A.alloc(FT * D)) || !(B.h = A.alloc(FT * Hm)) || !(B.stats = A.alloc(4 * FT)))
+            return A.oom("saved activations of a block");
     }
-    if (!(n->x_top = n->alloc(FT * D)) || !(n->t1 = n->alloc(FT * D)) || !(n->t2 = n->alloc(FT * Hm)) ||
-        !(n->dP = n->alloc(probs)) || !(n->dqkv = n->alloc(FT * 3 * D)) || !(n->G = n->alloc(FT * D)) ||
-        !(n->patches = n->alloc(F * NPt * KP)) || !(n->emb = n->alloc(F * NPt * D)))
-        return n->oom("scratch");
-    for (int i = 0; i < n_hooks; ++i) {
-        n->hook_block.push_back(hooks[i]);
-        float* g = n->alloc(FT * D);
-        if (!g) return n->oom("hook gradients");
-        HCHK(hipMemset(g, 0, (size_t)FT * D * 4));
-        n->hook_grad.push_back(g);
-    }
+    if (!(n->x_top = A.alloc(FT * D)) || !(n->t1 = A.alloc(FT * D)) || !(n->t2 = A.alloc(FT * Hm)) ||
+        !(n->dP = A.alloc(probs)) || !(n->dqkv = A.alloc(FT * 3 * D)) || !(n->G = A.alloc(FT * D)) ||
+        !(n->patches = A.alloc(F * NPt * KP)) || !(n->emb = A.alloc(F * NPt * D)))
+        return A.oom("scratch");
+    for (int i = 0; i < n_hooks; ++i) VCHK(n->hooks.add(A, hooks[i], FT * D));
     return 0;
 }
 
@@ -243,20 +160,11 @@ extern "C" int i2v_vit_create(int device, const i2v_vit_config* cfg, const float
 extern "C" int i2v_vit_create_ex(int device, const i2v_vit_config* cfg, int n_prefix, const float* const* weights, int n_weights,
                                  const int32_t* hook_blocks, int n_hooks, int max_frames, i2v_vit_handle* out) {
     if (!cfg || !weights || !hook_blocks || !out) return fail("i2v_vit_create: null argument");
-    if (max_frames <= 0) return fail("i2v_vit_create: max_frames must be positive");
-    *out = nullptr;
-    HCHK(hipSetDevice(device));
-    i2v_vit* n = new i2v_vit();
-    n->cfg = *cfg;
-    n->device = device;
-    n->max_frames = max_frames;
-    n->npre = n_prefix;
-    if (vit_plan(n, weights, n_weights, hook_blocks, n_hooks) != 0) {
-        delete n;
-        return 1;
-    }
-    *out = n;
-    return 0;
+    return create_net("i2v_vit_create", "block", device, max_frames, out, [&](i2v_vit* n) {
+        n->cfg = *cfg;
+        n->npre = n_prefix;
+        return vit_plan(n, weights, n_weights, hook_blocks, n_hooks);
+    });
 }
 
 extern "C" int i2v_vit_destroy(i2v_vit_handle net) {
@@ -264,29 +172,21 @@ extern "C" int i2v_vit_destroy(i2v_vit_handle net) {
     return 0;
 }
 
-extern "C" int64_t i2v_vit_workspace_bytes(i2v_vit_handle net) { return net ? net->bytes : -1; }
+extern "C" int64_t i2v_vit_workspace_bytes(i2v_vit_handle net) { return net ? net->arena.bytes : -1; }
 
 extern "C" int i2v_vit_forward(i2v_vit_handle n, const float* x, int frames, void* stream) {
     if (!n || !x) return fail("i2v_vit_forward: null argument");
     if (frames <= 0 || frames > n->max_frames) return fail("i2v_vit_forward: %d frames, the net is planned for 1..%d", frames, n->max_frames);
     hipStream_t s = (hipStream_t)stream;
     const i2v_vit_config& c = n->cfg;
-    const int D = c.dim, T = n->T, M = frames * T, dh = D / c.heads;
-    const int64_t FT = (int64_t)frames * T;
+    const int heads = c.heads, dh = c.dim / heads;
+    const BlockRun r = n->run(frames, s);
     n->frames = frames;
-    VCHK(embed(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, n->prefix, n->npre, n->pos, D, n->patches, n->emb, n->blocks[0].x, s));
-    for (int b = 0; b < n->nb; ++b) {
-        Block& B = n->blocks[b];
-        float* st = B.stats;                                   // [mean1 | rstd1 | mean2 | rstd2], FT each at max_frames spacing
-        const int64_t sp = (int64_t)n->max_frames * T;
-        VCHK(vit_layernorm(B.x, FT, D, B.n1w, B.n1b, c.ln_eps, n->t1, st, st + sp, s));
-        VCHK(linear(n->t1, M, D, B.qkvw, B.qkvb, 3 * D, nullptr, B.qkv, nullptr, s));
-        VCHK(attention(B.qkv, frames, T, c.heads, dh, n->scale, B.P, n->t1, s));
-        VCHK(linear(n->t1, M, D, B.projw, B.projb, D, B.x, B.y, nullptr, s));             // y = x + proj(attn)
-        VCHK(vit_layernorm(B.y, FT, D, B.n2w, B.n2b, c.ln_eps, n->t1, st + 2 * sp, st + 3 * sp, s));
-        VCHK(linear(n->t1, M, D, B.fc1w, B.fc1b, c.mlp, nullptr, B.h, n->t2, s));         // h = fc1(LN2(y)), t2 = gelu(h)
-        VCHK(linear(n->t2, M, c.mlp, B.fc2w, B.fc2b, D, B.y, n->stream_after(b), nullptr, s));   // x' = y + fc2(gelu(h))
-    }
+    VCHK(embed(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, n->prefix, n->npre, n->pos, c.dim, n->patches, n->emb, n->blocks[0].x, s));
+    for (int b = 0; b < n->nb; ++b)
+        VCHK(block_forward(n->blocks[b], r, n->stream_after(b), [&](const Block& B, float* o) {
+            return attention(B.qkv, frames, n->T, heads, dh, n->scale, B.P, o, s);
+        }));
     return 0;
 }
 
@@ -295,47 +195,28 @@ extern "C" int i2v_vit_backward(i2v_vit_handle n, float* gx, int accumulate, voi
     if (n->frames <= 0) return fail("i2v_vit_backward: no forward pass to differentiate");
     hipStream_t s = (hipStream_t)stream;
     const i2v_vit_config& c = n->cfg;
-    const int frames = n->frames, D = c.dim, T = n->T, M = frames * T, dh = D / c.heads;
-    const int64_t FT = (int64_t)frames * T, sp = (int64_t)n->max_frames * T;
-    auto grad_at = [&](int b) -> const float* {              // hook gradient of the stream after block b, or null
-        for (size_t i = 0; i < n->hook_block.size(); ++i)
-            if (n->hook_block[i] == b) return n->hook_grad[i];
-        return nullptr;
-    };
+    const int frames = n->frames, heads = c.heads, dh = c.dim / heads;
+    const BlockRun r = n->run(frames, s);
     for (int b = n->nb - 1; b >= 0; --b) {
-        Block& B = n->blocks[b];
-        const float* st = B.stats;
         // gradient of the stream after block b: the top hook's view for the deepest block, the running gradient G below it (where
         // the LN1 backward of block b + 1 has already added the hook at that stream)
-        const float* gin = b == n->nb - 1 ? grad_at(b) : n->G;
-        VCHK(linear_bwd(gin, M, D, B.fc2w, c.mlp, B.h, n->t2, s));                       // dh = (g fc2) * gelu'(h)
-        VCHK(linear_bwd(n->t2, M, c.mlp, B.fc1w, D, nullptr, n->t1, s));                // d LN2 out
-        VCHK(vit_layernorm_bwd(n->t1, B.y, st + 2 * sp, st + 3 * sp, B.n2w, FT, D, gin, nullptr, n->G, s));   // G = dy
-        VCHK(linear_bwd(n->G, M, D, B.projw, D, nullptr, n->t1, s));                    // d attention out
-        VCHK(attention_bwd(B.qkv, B.P, n->t1, frames, T, c.heads, dh, n->scale, n->dP, n->dqkv, s));
-        VCHK(linear_bwd(n->dqkv, M, 3 * D, B.qkvw, D, nullptr, n->t1, s));              // d LN1 out
-        VCHK(vit_layernorm_bwd(n->t1, B.x, st, st + sp, B.n1w, FT, D, n->G, b > 0 ? grad_at(b - 1) : nullptr, n->G, s));   // G = dx (+ hook)
+        const float* gin = b == n->nb - 1 ? n->hooks.grad_at(b) : n->G;
+        VCHK(block_backward(n->blocks[b], r, gin, b > 0 ? n->hooks.grad_at(b - 1) : nullptr, [&](const Block& B, const float* dout) {
+            return attention_bwd(B.qkv, B.P, dout, frames, n->T, heads, dh, n->scale, n->dP, n->dqkv, s);
+        }));
     }
-    return embed_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, D, n->npre, n->patches, gx, accumulate, s);
+    return embed_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, c.dim, n->npre, n->patches, gx, accumulate, s);
 }
 
 extern "C" int i2v_vit_hook_info(i2v_vit_handle n, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride, int64_t* D) {
-    if (!n || hook < 0 || hook >= (int)n->hook_block.size()) return fail("i2v_vit_hook_info: no hook %d", hook);
-    const int64_t d = (int64_t)n->T * n->cfg.dim;
-    if (act) *act = n->stream_after(n->hook_block[hook]);
-    if (act_stride) *act_stride = d;
-    if (grad) *grad = n->hook_grad[hook];
-    if (grad_stride) *grad_stride = d;
-    if (D) *D = d;
-    return 0;
+    if (!n || !n->hooks.has(hook)) return fail("i2v_vit_hook_info: no hook %d", hook);
+    return hook_info(n->stream_after(n->hooks.at[hook]), n->hooks.grad[hook], (int64_t)n->T * n->cfg.dim, act, act_stride, grad, grad_stride, D);
 }
 
 extern "C" int i2v_vit_read_hook(i2v_vit_handle n, int hook, int which, float* out, int frames, void* stream) {
-    if (!n || !out || hook < 0 || hook >= (int)n->hook_block.size()) return fail("i2v_vit_read_hook: no hook %d", hook);
-    if (frames <= 0 || frames > n->max_frames) return fail("i2v_vit_read_hook: %d frames, the net is planned for 1..%d", frames, n->max_frames);
-    const float* src = which ? n->hook_grad[hook] : n->stream_after(n->hook_block[hook]);
-    HCHK(hipMemcpyAsync(out, src, (size_t)frames * n->T * n->cfg.dim * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return 0;
+    if (!n || !out || !n->hooks.has(hook)) return fail("i2v_vit_read_hook: no hook %d", hook);
+    return read_hook("i2v_vit_read_hook", which ? n->hooks.grad[hook] : n->stream_after(n->hooks.at[hook]), (int64_t)n->T * n->cfg.dim, out,
+                     frames, n->max_frames, stream);
 }
 
 // ---- the kernels on their own ----

@@ -74,33 +74,26 @@ class Engine:
         except Exception:
             pass
 
-    def build_net(self, graph: Graph, state_dict, hook_tensors: Sequence[int], max_frames: int, relu_gain=None) -> "Net":
+    def _build(self, cls, *args):
         """Thread-safe (concurrent clip streams plan their own nets); execution of DIFFERENT nets on different
         streams needs no lock -- a planned net owns its arena, the library keeps no other mutable state."""
         with self.plan_lock:
             t0 = time.perf_counter()
-            net = Net(self, graph, state_dict, list(hook_tensors), max_frames, relu_gain)
+            net = cls(self, *args)
             self.plan_ms += 1e3 * (time.perf_counter() - t0)      # pack + upload + plan + autotune (i2v_net_plan syncs)
             self.plans += 1
             return net
 
+    def build_net(self, graph: Graph, state_dict, hook_tensors: Sequence[int], max_frames: int, relu_gain=None) -> "Net":
+        return self._build(Net, graph, state_dict, list(hook_tensors), max_frames, relu_gain)
+
     def build_vit_net(self, spec: VitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "VitNet":
         """The ViT surrogate (`include/i2v_vit.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        with self.plan_lock:
-            t0 = time.perf_counter()
-            net = VitNet(self, spec, state_dict, list(hook_blocks), max_frames)
-            self.plan_ms += 1e3 * (time.perf_counter() - t0)
-            self.plans += 1
-            return net
+        return self._build(VitNet, spec, state_dict, list(hook_blocks), max_frames)
 
     def build_swin_net(self, spec: SwinSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "SwinNet":
         """A Swin surrogate (`include/i2v_swin.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        with self.plan_lock:
-            t0 = time.perf_counter()
-            net = SwinNet(self, spec, state_dict, list(hook_stages), max_frames)
-            self.plan_ms += 1e3 * (time.perf_counter() - t0)
-            self.plans += 1
-            return net
+        return self._build(SwinNet, spec, state_dict, list(hook_stages), max_frames)
 
     # ---- measurement ----
     KINDS = ("conv_igemm_fwd", "conv_igemm_imggrad", "pool_fwd", "pool_bwd", "addmask", "conv_igemm_dgrad")
@@ -580,130 +573,105 @@ class Net:
         return max(self.eng.capi.i2v_cossim_scratch_bytes(hi.D, frames) for hi in self.hooks)
 
 
-class VitNet(Net):
-    """The ViT surrogate behind the `Net` interface the attack loop uses (`forward`, `backward`, `save_hook`, `cossim`, `stdloss`,
-    `scratch_bytes`, `hooks`): a hook is the residual stream after one block, (tokens * dim) floats per frame; the loss kernels are the
-    ones every backbone uses."""
+class TokenNet(Net):
+    """A transformer surrogate behind the `Net` interface the attack loop uses (`forward`, `backward`, `save_hook`, `cossim`, `stdloss`,
+    `scratch_bytes`, `hooks`): a hook is a residual stream of `hook_shape(i)[0]` tokens, `hook_shape(i)[1]` wide; the loss kernels are
+    the ones every backbone uses.  A family sets `_api` (its C entries are `i2v_<_api>_*`), packs its weights and calls its create entry
+    in `_create(spec, sd, hooks, max_frames)`, and gives `hook_shape(i)`."""
+    _api = None
 
-    def __init__(self, eng: Engine, spec: VitSpec, sd, hook_blocks: List[int], max_frames: int):
-        self.eng, capi = eng, eng.capi
-        self.graph, self.max_frames, self.id = spec, max_frames, None
-        self.hook_tensors = list(hook_blocks)
+    def __init__(self, eng: Engine, spec, sd, hooks: List[int], max_frames: int):
+        self.eng, self.graph, self.max_frames, self.id = eng, spec, max_frames, None
+        self.hook_tensors = list(hooks)
+        self.h = self._create(spec, sd, self.hook_tensors, max_frames)
+        self.hooks = []
+        for i in range(len(hooks)):
+            act, grad = C.c_void_p(), C.c_void_p()
+            a_s, g_s, D = C.c_int64(), C.c_int64(), C.c_int64()
+            _lib.check(eng.capi, self._c("hook_info")(self.h, i, C.byref(act), C.byref(a_s), C.byref(grad), C.byref(g_s), C.byref(D)))
+            hi = HookInfo()
+            hi.act, hi.act_stride, hi.grad, hi.grad_stride, hi.D, hi.post_relu = act.value, a_s.value, grad.value, g_s.value, D.value, 0
+            hi.shape, hi.T = self.hook_shape(i), 1
+            self.hooks.append(hi)
+
+    def _c(self, name):
+        return getattr(self.eng.capi, f"i2v_{self._api}_{name}")
+
+    def close(self):
+        if getattr(self, "h", None) and self.eng.h:
+            with self.eng.plan_lock:
+                self._c("destroy")(self.h)
+        self.h = None
+
+    def workspace_bytes(self) -> int:
+        return int(self._c("workspace_bytes")(self.h))
+
+    def forward(self, x: torch.Tensor):
+        spec = self.graph
+        if tuple(x.shape[1:]) != (spec.in_chans, spec.img, spec.img):
+            raise _lib.I2VError(f"{spec.arch}: frames of shape {tuple(x.shape[1:])}, expected {(spec.in_chans, spec.img, spec.img)}")
+        _lib.check(self.eng.capi, self._c("forward")(self.h, _ptr(x, self.eng), x.shape[0], self.eng.stream()))
+
+    def backward(self, gx: torch.Tensor, accumulate=False):
+        _lib.check(self.eng.capi, self._c("backward")(self.h, _ptr(gx, self.eng), 1 if accumulate else 0, self.eng.stream()))
+
+    def read_hook(self, i: int, frames: int, grad=False) -> torch.Tensor:
+        out = torch.empty(frames, *self.hook_shape(i)[:2], dtype=torch.float32, device=self.eng.device)
+        _lib.check(self.eng.capi, self._c("read_hook")(self.h, i, 1 if grad else 0, _ptr(out, self.eng), frames, self.eng.stream()))
+        return out
+
+    def save_hook(self, i: int, frames: int) -> torch.Tensor:
+        return self.read_hook(i, frames)
+
+    def hook_frames(self, i: int, in_frames: int) -> int:
+        return in_frames
+
+
+class VitNet(TokenNet):
+    """The ViT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame."""
+    _api = "vit"
+
+    def _create(self, spec: VitSpec, sd, hook_blocks, max_frames):
+        eng, capi = self.eng, self.eng.capi
         nb = max(hook_blocks) + 1
         keys = [k for i in range(nb) for k in spec.block_keys(i)]
         # native order: patch weight, patch bias, the prefix tokens as one (n_prefix, dim) array (cls_token, then dist_token), pos_embed,
         # then the blocks; kept alive until the upload in i2v_vit_create_ex
         prefix = torch.cat([sd[k].detach().float().cpu().reshape(1, spec.dim) for k in spec.prefix_keys], 0)
-        self._w = [sd[k].detach().float().cpu().contiguous() for k in ("patch_embed.proj.weight", "patch_embed.proj.bias")]
-        self._w += [prefix.contiguous(), sd["pos_embed"].detach().float().cpu().contiguous()]
-        self._w += [sd[k].detach().float().cpu().contiguous() for k in keys]
-        ptrs = (C.c_void_p * len(self._w))(*[t.data_ptr() for t in self._w])
+        w = [sd[k].detach().float().cpu().contiguous() for k in ("patch_embed.proj.weight", "patch_embed.proj.bias")]
+        w += [prefix.contiguous(), sd["pos_embed"].detach().float().cpu().contiguous()]
+        w += [sd[k].detach().float().cpu().contiguous() for k in keys]
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
         cfg = _lib.VitConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.ln_eps)
         hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
         h = C.c_void_p()
-        _lib.check(capi, capi.i2v_vit_create_ex(eng.device.index or 0, C.byref(cfg), spec.n_prefix, ptrs, len(self._w), hb,
-                                                len(hook_blocks), max_frames, C.byref(h)))
-        self._w = None
-        self.h = h
-        self.hooks = []
-        for i in range(len(hook_blocks)):
-            act, grad = C.c_void_p(), C.c_void_p()
-            a_s, g_s, D = C.c_int64(), C.c_int64(), C.c_int64()
-            _lib.check(capi, capi.i2v_vit_hook_info(h, i, C.byref(act), C.byref(a_s), C.byref(grad), C.byref(g_s), C.byref(D)))
-            hi = HookInfo()
-            hi.act, hi.act_stride, hi.grad, hi.grad_stride, hi.D, hi.post_relu = act.value, a_s.value, grad.value, g_s.value, D.value, 0
-            hi.shape, hi.T = (spec.tokens, spec.dim, 1), 1
-            self.hooks.append(hi)
+        _lib.check(capi, capi.i2v_vit_create_ex(eng.device.index or 0, C.byref(cfg), spec.n_prefix, ptrs, len(w), hb, len(hook_blocks),
+                                                max_frames, C.byref(h)))
+        return h
 
-    def close(self):
-        if getattr(self, "h", None) and self.eng.h:
-            with self.eng.plan_lock:
-                self.eng.capi.i2v_vit_destroy(self.h)
-        self.h = None
-
-    def workspace_bytes(self) -> int:
-        return int(self.eng.capi.i2v_vit_workspace_bytes(self.h))
-
-    def forward(self, x: torch.Tensor):
-        spec = self.graph
-        if tuple(x.shape[1:]) != (spec.in_chans, spec.img, spec.img):
-            raise _lib.I2VError(f"{spec.arch}: frames of shape {tuple(x.shape[1:])}, expected {(spec.in_chans, spec.img, spec.img)}")
-        _lib.check(self.eng.capi, self.eng.capi.i2v_vit_forward(self.h, _ptr(x, self.eng), x.shape[0], self.eng.stream()))
-
-    def backward(self, gx: torch.Tensor, accumulate=False):
-        _lib.check(self.eng.capi, self.eng.capi.i2v_vit_backward(self.h, _ptr(gx, self.eng), 1 if accumulate else 0, self.eng.stream()))
-
-    def read_hook(self, i: int, frames: int, grad=False) -> torch.Tensor:
-        out = torch.empty(frames, self.graph.tokens, self.graph.dim, dtype=torch.float32, device=self.eng.device)
-        _lib.check(self.eng.capi, self.eng.capi.i2v_vit_read_hook(self.h, i, 1 if grad else 0, _ptr(out, self.eng), frames,
-                                                                 self.eng.stream()))
-        return out
-
-    def save_hook(self, i: int, frames: int) -> torch.Tensor:
-        return self.read_hook(i, frames)
-
-    def hook_frames(self, i: int, in_frames: int) -> int:
-        return in_frames
+    def hook_shape(self, i):
+        return (self.graph.tokens, self.graph.dim, 1)
 
 
-class SwinNet(Net):
-    """A Swin surrogate behind the `Net` interface the attack loop uses: a hook is the stream after the last block of a stage, before
-    that stage's patch merging, (grid^2 * width) floats per frame; the loss kernels are the ones every backbone uses."""
+class SwinNet(TokenNet):
+    """A Swin surrogate: a hook is the stream after the last block of a stage, before that stage's patch merging, (grid^2 * width) floats
+    per frame."""
+    _api = "swin"
 
-    def __init__(self, eng: Engine, spec: SwinSpec, sd, hook_stages: List[int], max_frames: int):
-        self.eng, capi = eng, eng.capi
-        self.graph, self.max_frames, self.id = spec, max_frames, None
-        self.hook_tensors = list(hook_stages)
+    def _create(self, spec: SwinSpec, sd, hook_stages, max_frames):
+        eng, capi = self.eng, self.eng.capi
         ns = max(hook_stages) + 1
         # native order (include/i2v_swin.h): the embedding, then per stage its blocks and the merging behind it; kept alive until the upload
-        self._w = [sd[k].detach().float().cpu().contiguous() for k in spec.native_keys(ns)]
-        ptrs = (C.c_void_p * len(self._w))(*[t.data_ptr() for t in self._w])
+        w = [sd[k].detach().float().cpu().contiguous() for k in spec.native_keys(ns)]
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
         pad = lambda v: (C.c_int32 * 4)(*(list(v) + [0] * (4 - len(v))))
         cfg = _lib.SwinConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.window, spec.stages, pad(spec.depths), pad(spec.heads),
                               spec.ln_eps)
         hs = (C.c_int32 * len(hook_stages))(*hook_stages)
         h = C.c_void_p()
-        _lib.check(capi, capi.i2v_swin_create(eng.device.index or 0, C.byref(cfg), ptrs, len(self._w), hs, len(hook_stages), max_frames,
-                                              C.byref(h)))
-        self._w = None
-        self.h = h
-        self.hooks = []
-        for i, st in enumerate(hook_stages):
-            act, grad = C.c_void_p(), C.c_void_p()
-            a_s, g_s, D = C.c_int64(), C.c_int64(), C.c_int64()
-            _lib.check(capi, capi.i2v_swin_hook_info(h, i, C.byref(act), C.byref(a_s), C.byref(grad), C.byref(g_s), C.byref(D)))
-            hi = HookInfo()
-            hi.act, hi.act_stride, hi.grad, hi.grad_stride, hi.D, hi.post_relu = act.value, a_s.value, grad.value, g_s.value, D.value, 0
-            hi.shape, hi.T = (spec.tokens(st), spec.width(st), 1), 1
-            self.hooks.append(hi)
+        _lib.check(capi, capi.i2v_swin_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hs, len(hook_stages), max_frames, C.byref(h)))
+        return h
 
-    def close(self):
-        if getattr(self, "h", None) and self.eng.h:
-            with self.eng.plan_lock:
-                self.eng.capi.i2v_swin_destroy(self.h)
-        self.h = None
-
-    def workspace_bytes(self) -> int:
-        return int(self.eng.capi.i2v_swin_workspace_bytes(self.h))
-
-    def forward(self, x: torch.Tensor):
-        spec = self.graph
-        if tuple(x.shape[1:]) != (spec.in_chans, spec.img, spec.img):
-            raise _lib.I2VError(f"{spec.arch}: frames of shape {tuple(x.shape[1:])}, expected {(spec.in_chans, spec.img, spec.img)}")
-        _lib.check(self.eng.capi, self.eng.capi.i2v_swin_forward(self.h, _ptr(x, self.eng), x.shape[0], self.eng.stream()))
-
-    def backward(self, gx: torch.Tensor, accumulate=False):
-        _lib.check(self.eng.capi, self.eng.capi.i2v_swin_backward(self.h, _ptr(gx, self.eng), 1 if accumulate else 0, self.eng.stream()))
-
-    def read_hook(self, i: int, frames: int, grad=False) -> torch.Tensor:
+    def hook_shape(self, i):
         st = self.hook_tensors[i]
-        out = torch.empty(frames, self.graph.tokens(st), self.graph.width(st), dtype=torch.float32, device=self.eng.device)
-        _lib.check(self.eng.capi, self.eng.capi.i2v_swin_read_hook(self.h, i, 1 if grad else 0, _ptr(out, self.eng), frames,
-                                                                  self.eng.stream()))
-        return out
-
-    def save_hook(self, i: int, frames: int) -> torch.Tensor:
-        return self.read_hook(i, frames)
-
-    def hook_frames(self, i: int, in_frames: int) -> int:
-        return in_frames
+        return (self.graph.tokens(st), self.graph.width(st), 1)

@@ -72,23 +72,20 @@ def arg_parse(argv=None, ucf101=False):
     args = parser.parse_args(argv)
     if not ucf101:
         check_video_flags(parser, args)
-    if args.attack_method in ("ImageGuidedStd_Adam", "ImageGuidedFMDirection_Adam") and graphs.is_vit_name(args.direction_image_model):
-        # a ViT / DeiT name: refused here with the served names when it is not offered, and --depth checked against the spec's hooks
-        try:
-            spec = graphs.vit_named(args.direction_image_model, (args.hw, args.hw))
-        except ValueError as e:
-            parser.error(f"--direction_image_model: {e}")
-        if args.depth not in spec.hooks:
-            parser.error(f"--depth {args.depth}: {spec.arch} hooks depths {sorted(spec.hooks)} (blocks {[spec.hooks[d] for d in sorted(spec.hooks)]})")
-    if args.attack_method in ("ImageGuidedStd_Adam", "ImageGuidedFMDirection_Adam") and graphs.is_swin_name(args.direction_image_model):
-        # a Swin name: the same early refusal, and --depth checked against the spec's stages
-        try:
-            spec = graphs.swin_named(args.direction_image_model, (args.hw, args.hw))
-        except ValueError as e:
-            parser.error(f"--direction_image_model: {e}")
-        if args.depth not in spec.hooks:
-            parser.error(f"--depth {args.depth}: {spec.arch} hooks depths {sorted(spec.hooks)} (the last block of stages "
-                         f"{[spec.hooks[d] for d in sorted(spec.hooks)]})")
+    if args.attack_method in ("ImageGuidedStd_Adam", "ImageGuidedFMDirection_Adam"):
+        # a ViT / DeiT or a Swin name: refused here with the served names when it is not offered, and --depth checked against the spec's
+        # hooked blocks / stages
+        for is_name, named, hooked in ((graphs.is_vit_name, graphs.vit_named, "blocks {}"),
+                                       (graphs.is_swin_name, graphs.swin_named, "the last block of stages {}")):
+            if not is_name(args.direction_image_model):
+                continue
+            try:
+                spec = named(args.direction_image_model, (args.hw, args.hw))
+            except ValueError as e:
+                parser.error(f"--direction_image_model: {e}")
+            if args.depth not in spec.hooks:
+                parser.error(f"--depth {args.depth}: {spec.arch} hooks depths {sorted(spec.hooks)} "
+                             f"({hooked.format([spec.hooks[d] for d in sorted(spec.hooks)])})")
     if args.synthetic_weights:
         os.environ["I2V_SYNTHETIC_WEIGHTS"] = "1"
     args.adv_path = os.path.join(OPT_PATH, "{}-{}-{}-{}".format("Image", args.attack_method, args.step, args.file_prefix))

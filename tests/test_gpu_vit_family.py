@@ -301,6 +301,25 @@ def test_create_refuses_a_bad_prefix_count_and_reports_its_error(eng):
     assert b"prefix" in capi.i2v_last_error() and not h.value
 
 
+def test_create_refuses_more_rows_than_the_kernels_count_before_any_allocation(eng):
+    """The kernels count the rows of a stream (frames x tokens) in an int: a plan past 2^31 / 4 rows is refused on the host, as Swin's is."""
+    capi = eng.capi
+    spec = graphs.build_tiny(DISTILLED, (64, 64))
+    sd = weights.synthetic_state_dict(spec, 0)
+    w = [torch.zeros(s).float() for s in ((64, 3, 16, 16), (64,), (2, 64), (18, 64))] + [sd[k].float().contiguous() for k in spec.block_keys(0)]
+    ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
+    cfg = _lib.VitConfig(64, 16, 3, 64, 2, 256, 6, 1e-6)
+    frames = (0x7fffffff // 4) // spec.tokens + 1
+    for n_frames, refused in ((frames, True), (2, False)):
+        h = C.c_void_p()
+        rc = capi.i2v_vit_create_ex(0, C.byref(cfg), 2, ptrs, len(w), (C.c_int32 * 1)(0), 1, n_frames, C.byref(h))
+        if refused:
+            assert rc != 0 and b"i2v_vit_create" in capi.i2v_last_error() and b"too many frames" in capi.i2v_last_error() and not h.value
+        else:
+            assert rc == 0 and h.value
+            capi.i2v_vit_destroy(h)
+
+
 def _video(b, f, hw, seed):
     gen = torch.Generator().manual_seed(seed)
     u8 = torch.randint(0, 256, (b, 3, f, hw, hw), generator=gen, dtype=torch.uint8)
