@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE -- scalar host implementation of csrc/i2v_kernels.h.
 //
-// Linked with csrc/i2v_engine.cpp into tests/hostsim/libi2v_hostsim.so so that the graph planner
+// Linked with the engine units (csrc/i2v_engine.cpp, i2v_pack.cpp, i2v_plan.cpp, i2v_tune.cpp, i2v_run.cpp,
+// i2v_loop_api.cpp) into tests/hostsim/libi2v_hostsim.so so that the graph planner
 // (weight packing, k-tables, stride-parity classes, addend/mask fusion, arena layout) can be
 // checked against the oracle WITHOUT a GPU (`pytest -m "not gpu"`).  It is never loaded by the
 // product package: `i2v_amd.lib` only accepts a library whose `i2v_backend()` is "hip:gfx950".

@@ -7,10 +7,10 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "hostsim", "libi2v_hostsim.so")
-SRCS = [os.path.join(HERE, "hostsim", "hostsim_backend.cpp"),
-        os.path.join(HERE, "..", "image-to-video-i2v-attack_amd", "csrc", "i2v_engine.cpp"),
-        os.path.join(HERE, "..", "image-to-video-i2v-attack_amd", "csrc", "i2v_params.h"),
-        os.path.join(HERE, "..", "image-to-video-i2v-attack_amd", "csrc", "i2v_kernels.h"),
+CSRC = os.path.join(HERE, "..", "image-to-video-i2v-attack_amd", "csrc")
+SRCS = [os.path.join(HERE, "hostsim", "hostsim_backend.cpp")] + [
+        os.path.join(CSRC, f) for f in ("i2v_engine.cpp", "i2v_pack.cpp", "i2v_plan.cpp", "i2v_tune.cpp", "i2v_run.cpp", "i2v_loop_api.cpp",
+                                        "i2v_net.h", "i2v_params.h", "i2v_kernels.h")] + [
         os.path.join(HERE, "..", "include", "i2v_hip.h")]
 _engine = None
 
