@@ -186,6 +186,45 @@ extern "C" int i2v_net_add_conv(i2v_handle h, int net, const i2v_conv_desc* d, c
     return i2v_net_add_conv3d(h, net, &q, weight, scale, shift);
 }
 
+// A grouped 3x3 convolution.  The node is stored with its block-diagonal dense weight -- the dense route (I2V_GCONV=0, and the host
+// simulation) packs and runs it as any other convolution -- and with the compact kernel k_gconv reads.
+extern "C" int i2v_net_add_conv_grouped(i2v_handle h, int net, const i2v_conv_desc* d, int groups, const float* weight,
+                                        const float* scale, const float* shift) {
+    if (!d || !weight || !scale || !shift) return fail("i2v_net_add_conv_grouped: null argument");
+    if (groups == 1) return i2v_net_add_conv(h, net, d, weight, scale, shift);
+    if (groups < 1 || d->cin % groups || d->cout % groups)
+        return fail("i2v_net_add_conv_grouped: %d input and %d output channels are not divisible by %d groups", d->cin, d->cout, groups);
+    if (d->kh != 3 || d->kw != 3 || d->pad != 1 || (d->stride != 1 && d->stride != 2))
+        return fail("i2v_net_add_conv_grouped: only 3x3 / pad 1 / stride 1 or 2 is supported (got %dx%d, pad %d, stride %d)", d->kh, d->kw, d->pad, d->stride);
+    const int gi = d->cin / groups, go = d->cout / groups;
+    if (gi != go || (gi != 4 && gi != 8 && gi != 16 && gi != 32 && gi != 64))
+        return fail("i2v_net_add_conv_grouped: group width %d -> %d is not one of 4, 8, 16, 32, 64 in and out (depthwise is not supported)", gi, go);
+    if (d->residual >= 0) return fail("i2v_net_add_conv_grouped: a residual addend on a grouped convolution is not supported");
+    std::vector<float> dense((size_t)d->cout * d->cin * 9, 0.f);
+    for (int co = 0; co < d->cout; ++co)
+        for (int ci = 0; ci < gi; ++ci)
+            for (int t = 0; t < 9; ++t)
+                dense[((size_t)co * d->cin + (co / go) * gi + ci) * 9 + t] = weight[((size_t)co * gi + ci) * 9 + t];
+    if (i2v_net_add_conv(h, net, d, dense.data(), scale, shift)) return 1;
+    Node& nd = get_net(h, net)->nodes.back();
+    nd.groups = groups;
+    nd.wg.resize((size_t)d->cout * gi * 9);
+    for (int co = 0; co < d->cout; ++co)
+        for (int i = 0; i < gi * 9; ++i) nd.wg[(size_t)co * gi * 9 + i] = weight[(size_t)co * gi * 9 + i] * scale[co];
+    std::vector<float>().swap(nd.w);         // the dense expansion (groups times the floats) is rebuilt from `wg` only by a plan on the dense route
+    return 0;
+}
+
+// the block-diagonal dense weight of a grouped node, for the dense route's packings
+static void expand_grouped(Node& nd) {
+    const i2v_conv3d_desc& c = nd.cd;
+    const int gi = c.cin / nd.groups, go = c.cout / nd.groups;
+    nd.w.assign((size_t)c.cout * c.cin * 9, 0.f);
+    for (int co = 0; co < c.cout; ++co)
+        for (int ci = 0; ci < gi; ++ci)
+            for (int t = 0; t < 9; ++t) nd.w[((size_t)co * c.cin + (co / go) * gi + ci) * 9 + t] = nd.wg[((size_t)co * gi + ci) * 9 + t];
+}
+
 extern "C" int i2v_net_add_conv_preact(i2v_handle h, int net, const i2v_conv_desc* d, const float* weight,
                                        const float* scale, const float* shift, const float* pre_scale,
                                        const float* pre_shift) {
@@ -277,6 +316,13 @@ extern "C" int i2v_net_plan(i2v_handle h, int net, const int* hook_tensors, int 
     for (Node& nd : n.nodes) {
         if (nd.type != 0) continue;
         if (upload(n, nd.shift, &nd.shift_d)) return 1;
+        nd.gconv = nd.groups > 1 && gconv_enabled();
+        if (nd.gconv) {             // compact operands only: the dense packing (groups times the floats) is never made
+            if (nd.cd.src == n.input) return fail("a grouped convolution directly on the input is not planned");
+            if (pack_gconv(n, nd)) return 1;
+            continue;
+        }
+        if (nd.groups > 1) expand_grouped(nd);
         if (pack_fwd(n, nd)) return 1;
         if (nd.preact()) {          // operand-side affine, padded to Kpad with zeros (relu(0*x+0) = 0 for the K tail)
             std::vector<float> ps(nd.fwd.Kpad > nd.fwd.Cdpad ? nd.fwd.Kpad : nd.fwd.Cdpad, 0.f), pt(ps.size(), 0.f);
@@ -285,6 +331,7 @@ extern "C" int i2v_net_plan(i2v_handle h, int net, const int* hook_tensors, int 
         }
         if (nd.cd.src == n.input) { if (pack_img(n, nd)) return 1; }
         else if (pack_bwd(n, nd)) return 1;
+        if (nd.groups > 1) std::vector<float>().swap(nd.w);
     }
     size_t off = 64;            // 256 bytes of slack in front of the first tensor (and behind the last, below): the quad-row
                                 // staging of conv_igemm (MODE 4) reads a few pixels past either end of a source view

@@ -87,6 +87,10 @@ inline int i2v_fastblock_rows(const I2VConvParams& a, const I2VConvParams& b, co
 }
 int k_fastblock(const I2VConvParams& a, const I2VConvParams& b, const I2VConvParams* c, const I2VConvParams* d, i2v_stream_t s);
    // tile configurations valid for p (ids 0..5, +8 = no epilogue prefetch), returns count
+// Grouped 3x3 convolution (I2VGConvParams; i2v_gconv.hip -- product backend only: the engine calls these under -DI2V_HAVE_GCONV, the
+// host simulation runs grouped nodes on the dense route).  k_gconv_plan fills the tiling fields; 0 ok, 1 the shape does not fit.
+int k_gconv_plan(I2VGConvParams* p);
+int k_gconv(const I2VGConvParams& p, i2v_stream_t s);
 int k_pool_fwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool_bwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool3d_fwd(const I2VPoolParams& p, i2v_stream_t s);  // video max pooling (kt/stride_t/pad_t honoured)

@@ -56,6 +56,11 @@ struct Node {
     float* shift_d = nullptr; float* pre_scale_d = nullptr; float* pre_shift_d = nullptr;   // *_d padded to Kpad
     bool preact() const { return !pre_scale.empty(); }
     Packed fwd; std::vector<Packed> bwd;
+    // grouped convolution (i2v_net_add_conv_grouped): `w` above is the block-diagonal DENSE expansion (what the dense route packs and the
+    // host simulation runs), `wg` the compact [cout][cin / groups][3][3] kernel, scale folded.  `gconv`: this plan runs the node on
+    // k_gconv (product build, I2V_GCONV not 0) -- then only the compact operands gw_fwd / gw_bwd (I2VGConvParams::w) are uploaded.
+    int groups = 1; std::vector<float> wg; bool gconv = false;
+    float* gw_fwd = nullptr; float* gw_bwd = nullptr; int gw_tapmask[4] = {0, 0, 0, 0};
     // input gradient of a convolution that reads the network input (class-packed): one launch -- or one per temporal class (pack_img)
     struct ImgGrad {
         Packed P; int blk = 0, sh = 1, blkt = 1;
@@ -67,10 +72,12 @@ struct Node {
     size_t idx_off = 0;                           // maxpool: arg-max bytes, arena offset in floats
 };
 
-enum Kind { L_CONV, L_IMGGRAD, L_POOLF, L_POOLB, L_ADDMASK, L_AVGF, L_AVGB, L_MEMSET, L_POOL3F, L_POOL3B, L_AGEMM, L_SOFTMAX };   // L_IMGGRAD: conv_igemm with class-packed Cd
+enum Kind { L_CONV, L_IMGGRAD, L_POOLF, L_POOLB, L_ADDMASK, L_AVGF, L_AVGB, L_MEMSET, L_POOL3F, L_POOL3B, L_AGEMM, L_SOFTMAX, L_GCONV };   // L_IMGGRAD: conv_igemm with class-packed Cd
+// L_GCONV: a grouped 3x3 node on k_gconv -- `gc` is what the kernel gets; `conv` carries the same views (src, dst, gate, gate_out, mask, Cd, K =
+// 9 x group width) for the address-range analyses and the timing records, which treat it as the convolution launch it is
 struct Launch {
     Kind kind;
-    I2VConvParams conv; I2VPoolParams pool; I2VAddMaskParams am;
+    I2VConvParams conv; I2VPoolParams pool; I2VAddMaskParams am; I2VGConvParams gc;
     I2VAttnGemm ag; I2VSoftmaxRows sm; int sm_rows_per_clip = 0;    // L_AGEMM / L_SOFTMAX (clips are filled in at run time)
     int T = 1;                     // frames per clip of the launch's iteration space (conv launches: conv.Tg)
     bool src_is_input = false;     // conv: src pointer patched with the caller's x
@@ -166,6 +173,8 @@ bool math_bf16x3();
 int pack_fwd(Net& n, Node& nd);
 int pack_bwd(Net& n, Node& nd);
 int pack_img(Net& n, Node& nd);
+bool gconv_enabled();               // grouped nodes run on k_gconv in this plan (else: the dense route)
+int pack_gconv(Net& n, Node& nd);
 
 // i2v_plan.cpp: one pass over the nodes from arena offset `off` for N frames.  Dry: nothing is emitted, *end is where the temporaries
 // end.  Real (the arena allocated): fills n.fwd, n.bwd and n.hook_tmp.  False with *err set when the graph cannot be planned.

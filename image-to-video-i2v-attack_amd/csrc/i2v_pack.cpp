@@ -174,6 +174,53 @@ int pack_bwd(Net& n, Node& nd) {
     return 0;
 }
 
+// Grouped nodes run on k_gconv where the library has it (the product build defines I2V_HAVE_GCONV; the host simulation's one-file
+// build does not) unless I2V_GCONV=0 asks for the dense route: the block-diagonal weight through the packings above.  Read per plan.
+bool gconv_enabled() {
+#ifdef I2V_HAVE_GCONV
+    const char* e = getenv("I2V_GCONV");
+    return !(e && e[0] == '0');
+#else
+    return false;
+#endif
+}
+
+// k_gconv's operands (I2VGConvParams::w).  Forward: [group][ci][tap 3 r + s][co].  Input gradient: per stride-parity class (ph, pw) --
+// the classes of pack_bwd, in its order -- [group][co][slot 3 a + b][ci] with a - 1 = (ph + 1 - r) / stride for the row taps r the class
+// owns (b alike), zeros in the slots it does not; gw_tapmask has a bit per owned slot.
+int pack_gconv(Net& n, Node& nd) {
+    const i2v_conv3d_desc& c = nd.cd;
+    const int G = nd.groups, gw = c.cin / G, st = c.stride;
+    std::vector<float> wf((size_t)G * gw * 9 * gw);
+    for (int g = 0; g < G; ++g)
+        for (int co = 0; co < gw; ++co)
+            for (int ci = 0; ci < gw; ++ci)
+                for (int t = 0; t < 9; ++t)
+                    wf[(((size_t)g * gw + ci) * 9 + t) * gw + co] = nd.wg[(((size_t)(g * gw + co)) * gw + ci) * 9 + t];
+    if (upload(n, wf, &nd.gw_fwd)) return 1;
+    std::vector<float> wb((size_t)st * st * G * gw * 9 * gw, 0.f);
+    for (int ph = 0; ph < st; ++ph)
+        for (int pw = 0; pw < st; ++pw) {
+            const int cls = ph * st + pw;
+            int mask = 0;
+            for (int r = 0; r < 3; ++r) {
+                if (posmod(ph + 1 - r, st)) continue;
+                const int a = floordiv(ph + 1 - r, st) + 1;
+                for (int s = 0; s < 3; ++s) {
+                    if (posmod(pw + 1 - s, st)) continue;
+                    const int b = floordiv(pw + 1 - s, st) + 1;
+                    mask |= 1 << (3 * a + b);
+                    for (int g = 0; g < G; ++g)
+                        for (int co = 0; co < gw; ++co)
+                            for (int ci = 0; ci < gw; ++ci)
+                                wb[((((size_t)cls * G + g) * gw + co) * 9 + 3 * a + b) * gw + ci] = nd.wg[(((size_t)(g * gw + co)) * gw + ci) * 9 + 3 * r + s];
+                }
+            }
+            nd.gw_tapmask[cls] = mask;
+        }
+    return upload(n, wb, &nd.gw_bwd);
+}
+
 // Gradient of the FIRST convolution w.r.t. the image.  GEMM-N would be Cin = 3; instead the output is
 // cut into B x B position blocks (B = stride, or 2 for stride 1) and the B*B*Cin (class, channel)
 // pairs form the Cd axis: out[(ph,pw),ci][i][j] = sum_{co,dh,dw} w'[(co,dh,dw)][(ph,pw),ci] *

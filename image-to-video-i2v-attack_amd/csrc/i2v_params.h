@@ -126,6 +126,28 @@ struct I2VFastBlockParams {
     int32_t delay;                                           // probe (I2V_FB_DELAY): every other block sleeps this many x 127 x 64 clocks first
 };
 
+// Grouped 3x3 / pad-1 convolution (k_gconv, i2v_gconv.hip), forward and input gradient alike, ONE launch whatever the group count:
+//   dst[n][g gw + co][i os + oh0][j os + ow0] = epilogue( sum_{ci < gw, (a, b) in taps} w[cls][g][ci][3 a + b][co] *
+//                                                          src[n][g gw + ci][i S + a - 1][j S + b - 1] )        (zeros outside the plane)
+// over a grid of N x Hg x Wg positions per class.  Forward: one class, S = stride, os = 1, all nine taps, w = the kernel.  Input
+// gradient: S = 1, os = stride, one class per stride parity (oh0, ow0) with the taps that parity owns (`tapmask`, bit 3 a + b) and the
+// transposed, mirrored kernel.  Epilogue: + shift[c], ReLU, then the gate of the produced tensor (1-bit rows `gate`, or the fp32
+// activation `mask`); a forward launch with ReLU writes its own gate rows (`gate_out`: bit n Ho Wo + pixel of row c).
+struct I2VGConvClass { int32_t Hg, Wg, oh0, ow0, tapmask; uint32_t dv_w_m, dv_w_s, dv_hw_m, dv_hw_s; };
+struct I2VGConvParams {
+    const float* src; int64_t src_nstride; int32_t Hs, Ws;
+    const float* w;                      // [ncls][groups][gw][9][gw], scale folded
+    int32_t groups, gw, N, S, ncls;
+    I2VGConvClass cls[4];
+    float* dst; int64_t dst_nstride; int32_t Ho, Wo, os;
+    const float* shift; int32_t relu;
+    uint32_t* gate_out; int32_t gate_out_stride;
+    const uint32_t* gate; int32_t gate_stride;
+    const float* mask; int64_t mask_nstride;
+    int32_t waves, rows, lds_bytes;      // k_gconv_plan: waves per block (64 positions each), staged source rows per channel, LDS bytes
+    uint32_t dv_r_m, dv_r_s;             // exact division by Hs + 2 (the padded rows of a source frame)
+};
+
 struct I2VPoolParams {
     const float* x;    int64_t x_nstride;    int32_t C, Hs, Ws;
     float* y;          int64_t y_nstride;    int32_t Ho, Wo;       // fwd: output; bwd: upstream grad

@@ -139,8 +139,57 @@ struct Planner {
             }
             p.pointwise = (c.kt == 1 && c.stride_t == 1 && c.pad_t == 0 && c.kh == 1 && c.kw == 1 && c.stride == 1 &&
                            c.pad == 0 && (dz.H * dz.W) % 4 == 0 && !compact) ? 1 : 0;
+            if (nd.groups > 1) l.alg_flops_per_frame = 2.0 * P.Hg * P.Wg * (double)P.Cd * P.K / nd.groups;    // dense route of a grouped node: its real products
             emit(n.bwd, l);
         }
+    }
+    // A grouped node as ONE k_gconv launch per pass.  `conv` mirrors the views for the analyses of i2v_tune.cpp and the timing records.
+    bool gconv_launch(const Node& nd, bool backward, int t) {
+#ifdef I2V_HAVE_GCONV
+        const i2v_conv3d_desc& c = nd.cd;
+        const int gw = c.cin / nd.groups, st = c.stride;
+        View s = view(backward ? c.dst : c.src, backward), d = view(backward ? c.src : c.dst, backward);
+        Launch l; l.kind = L_GCONV; l.node = (int)(&nd - n.nodes.data()); l.T = d.T;
+        memset(&l.conv, 0, sizeof l.conv); memset(&l.gc, 0, sizeof l.gc);
+        I2VGConvParams& q = l.gc;
+        q.src = s.p; q.src_nstride = s.nstride; q.Hs = s.H; q.Ws = s.W;
+        q.groups = nd.groups; q.gw = gw;
+        q.dst = d.p; q.dst_nstride = d.nstride; q.Ho = d.H; q.Wo = d.W;
+        if (!backward) {
+            q.w = nd.gw_fwd; q.S = st; q.os = 1; q.ncls = 1;
+            q.cls[0].Hg = d.H; q.cls[0].Wg = d.W; q.cls[0].tapmask = 0x1FF;
+            q.shift = nd.shift_d; q.relu = c.relu;
+            if (c.relu) { int gs = 0; if (uint32_t* g = gate_rows(c.dst, &gs)) { q.gate_out = g; q.gate_out_stride = gs; } }
+        } else {
+            q.w = nd.gw_bwd; q.S = 1; q.os = st; q.ncls = st * st;
+            for (int ph = 0; ph < st; ++ph)
+                for (int pw = 0; pw < st; ++pw) {
+                    I2VGConvClass& k = q.cls[ph * st + pw];
+                    k.Hg = (d.H - ph + st - 1) / st; k.Wg = (d.W - pw + st - 1) / st; k.oh0 = ph; k.ow0 = pw; k.tapmask = nd.gw_tapmask[ph * st + pw];
+                }
+            if (n.tens[t].post_relu) {
+                int gs = 0;
+                if (uint32_t* g = gate_rows(t, &gs)) { q.gate = g; q.gate_stride = gs; }
+                else { View a = view(t, false); q.mask = a.p; q.mask_nstride = a.nstride; }
+            }
+        }
+        if (k_gconv_plan(&q)) { err = "a grouped convolution does not fit k_gconv (plan with I2V_GCONV=0 for the dense route)"; return false; }
+        I2VConvParams& p = l.conv;
+        p.src = q.src; p.src_nstride = q.src_nstride; p.Hs = q.Hs; p.Ws = q.Ws; p.Cs = c.cin;
+        p.dst = q.dst; p.dst_nstride = q.dst_nstride; p.Ho = q.Ho; p.Wo = q.Wo; p.Hg = q.Ho; p.Wg = q.Wo;
+        p.Cd = c.cin; p.Cdpad = c.cin; p.K = p.Kpad = 9 * gw; p.sh = p.sw = q.S; p.osh = p.osw = 1;
+        p.Tg = p.Ts = p.To = p.st = p.ost = 1; p.blkt = 1; p.oct = 1; p.add0_stride = 1;
+        p.shift = q.shift; p.relu = q.relu; p.gate = q.gate; p.gate_stride = q.gate_stride; p.gate_out = q.gate_out; p.gate_out_stride = q.gate_out_stride;
+        p.mask = q.mask; p.mask_nstride = q.mask_nstride;
+        const View o = view(c.dst, false);
+        l.alg_flops_per_frame = 2.0 * o.H * o.W * (double)c.cout * gw * 9;       // the node's real products: the dense count over `groups`
+        emit(backward ? n.bwd : n.fwd, l);
+        return true;
+#else
+        (void)nd; (void)backward; (void)t;
+        err = "this build has no grouped-convolution kernel";
+        return false;
+#endif
     }
     bool is_hook(int t) const { for (int hk : n.hooks) if (hk == t) return true; return false; }
     static bool has_compact(const std::vector<Addend>& A) { for (auto& a : A) if (a.stride != 1) return true; return false; }
@@ -149,6 +198,11 @@ struct Planner {
         left[t]--;
         View g = view(t, true);
         const i2v_conv3d_desc& c = nd.cd;
+        if (nd.gconv) {
+            // a bottleneck's conv1 output has the grouped conv2 as its ONLY consumer: k_gconv's epilogue takes no addends
+            if (left[t] > 0 || !pending[t].empty() || has_alias[t]) { err = "the input of a grouped convolution must have it as its only consumer"; return false; }
+            return gconv_launch(nd, true, t);
+        }
         if (left[t] > 0) {
             bool compact = (c.kt == 1 && c.stride_t == 1 && c.pad_t == 0 && c.kh == 1 && c.kw == 1 && c.stride > 1 && c.pad == 0);
             if (compact) {
@@ -232,6 +286,7 @@ struct Planner {
             Launch l;
             if (nd.type == 0) {
                 const i2v_conv3d_desc& c = nd.cd;
+                if (nd.gconv) { if (!gconv_launch(nd, false, c.dst)) return false; continue; }
                 l.kind = L_CONV; conv_common(l.conv, nd.fwd);
                 l.node = (int)(&nd - n.nodes.data());
                 I2VConvParams& p = l.conv;
@@ -251,6 +306,7 @@ struct Planner {
                                c.pad == 0 && (sb.H * sb.W) % 4 == 0 && c.src != n.input) ? 1 : 0;
                 if (nd.preact()) { p.pre_scale = nd.pre_scale_d; p.pre_shift = nd.pre_shift_d; }
                 if (c.relu) { int st = 0; if (uint32_t* g = gate_rows(c.dst, &st)) { p.gate_out = g; p.gate_out_stride = st; p.gate_out_pix0 = 0; } }
+                if (nd.groups > 1) l.alg_flops_per_frame = 2.0 * d.H * d.W * c.cout * (double)c.cin * c.kh * c.kw / nd.groups;    // dense route of a grouped node: its real products
                 if (nd.fwd.quad) l.alg_flops_per_frame = 2.0 * d.H * d.W * c.cout * (double)c.cin * c.kt * c.kh * c.kw * d.T / p.Tg;   // per GRID frame
             } else if (nd.type == 3) {
                 // S = scale * theta^T phi  ->  P = softmax rows  ->  y = g P^T   (P stays in the arena for the backward pass)

@@ -57,6 +57,7 @@ class ConvNode:
     stride_t: int = 1
     pad_t: int = 0
     dil_t: int = 1
+    groups: int = 1             # grouped convolution (ResNeXt): the weight is (cout, cin // groups, kh, kw)
 
 
 @dataclass
@@ -116,14 +117,15 @@ class Graph:
         return len(self.tensors) - 1
 
     def conv(self, src, cout, k, stride, pad, weight, bias=None, bn=None, relu=True,
-             residual=None, name="", dst_buf=None, dst_c_off=0, pre_bn=None) -> int:
+             residual=None, name="", dst_buf=None, dst_c_off=0, pre_bn=None, groups=1) -> int:
         s = self.tensors[src]
+        assert s.C % groups == 0 and cout % groups == 0, "channels must be divisible by groups"
         Ho = (s.H + 2 * pad - k) // stride + 1
         Wo = (s.W + 2 * pad - k) // stride + 1
         dst = self.new_tensor(cout, Ho, Wo, relu, name, dst_buf, dst_c_off)
         assert pre_bn is None or (k == 1 and stride == 1 and pad == 0), "pre-activation only on 1x1 convs"
         self.nodes.append(ConvNode(src, dst, s.C, cout, k, k, stride, pad, weight, bias, bn,
-                                   relu, residual, pre_bn))
+                                   relu, residual, pre_bn, groups=groups))
         return dst
 
     def maxpool(self, src, k, stride, pad=0, ceil_mode=False, name="", dst_buf=None, dst_c_off=0, op="maxpool") -> int:
@@ -221,7 +223,7 @@ class Graph:
         for nd in self.nodes:
             if nd.op == "conv":
                 d = self.tensors[nd.dst]
-                tot += d.T * d.H * d.W * nd.cout * nd.cin * nd.kt * nd.kh * nd.kw
+                tot += d.T * d.H * d.W * nd.cout * (nd.cin // nd.groups) * nd.kt * nd.kh * nd.kw
             elif nd.op == "attention":          # theta^T phi and g P^T
                 t, k = self.tensors[nd.src], self.tensors[nd.phi]
                 tot += 2 * t.C * (t.T * t.H * t.W) * (k.T * k.H * k.W)
@@ -233,7 +235,7 @@ class Graph:
         for nd in self.nodes:
             if nd.op != "conv":
                 continue
-            out[nd.weight] = (nd.cout, nd.cin, nd.kt, nd.kh, nd.kw) if self.video else (nd.cout, nd.cin, nd.kh, nd.kw)
+            out[nd.weight] = (nd.cout, nd.cin, nd.kt, nd.kh, nd.kw) if self.video else (nd.cout, nd.cin // nd.groups, nd.kh, nd.kw)
             if nd.bias:
                 out[nd.bias] = (nd.cout,)
             if nd.bn:
@@ -250,11 +252,18 @@ def _overlap(a: TensorSpec, b: TensorSpec) -> bool:
 
 
 # ---------------------------------------------------------------------------
-# ResNet v1.5 Bottleneck nets (torchvision `resnet50` / `resnet101`)
+# The torchvision ResNet family: ResNet-18 ... -152, Wide ResNet, ResNeXt (v1.5: the stride sits on the 3x3)
 # ---------------------------------------------------------------------------
-def resnet(layers=(3, 4, 23, 3), width=64, in_hw=(224, 224), arch="resnet101") -> Graph:
-    """Bottleneck ResNet.  Hook d = output of `layer{d}[-1]` (post-ReLU), as in
-    `/root/reference/image_attacks.py:261-262`."""
+def resnet(layers=(3, 4, 23, 3), width=64, in_hw=(224, 224), arch="resnet101", block="bottleneck", groups=1,
+           width_per_group=64) -> Graph:
+    """torchvision `ResNet(block, layers, groups=, width_per_group=)` up to `layer4`.  Hook d = output of `layer{d}[-1]` (post-ReLU),
+    as in `/root/reference/image_attacks.py:261-262`.
+      bottleneck: conv1 1x1 inplanes -> w, conv2 3x3 / stride / `groups` w -> w, conv3 1x1 w -> 4 planes (+ shortcut, ReLU) with
+                  w = int(planes * width_per_group / 64) * groups (Wide ResNet: width_per_group 128; ResNeXt: groups 32);
+      basic:      conv1 3x3 / stride -> BN -> ReLU, conv2 3x3 -> BN (+ shortcut, ReLU), expansion 1.
+    `width` scales every stage (64 for the real nets; the test-size twins use less)."""
+    assert block in ("bottleneck", "basic")
+    expansion = 4 if block == "bottleneck" else 1
     g = Graph(arch, in_hw)
     x = g.new_tensor(3, in_hw[0], in_hw[1], False, "input")
     g.input = x
@@ -266,22 +275,39 @@ def resnet(layers=(3, 4, 23, 3), width=64, in_hw=(224, 224), arch="resnet101") -
         for b in range(nblocks):
             stride = 2 if (b == 0 and li > 0) else 1
             p = f"layer{li + 1}.{b}"
-            a = g.conv(x, planes, 1, 1, 0, f"{p}.conv1.weight", bn=f"{p}.bn1", relu=True,
-                       name=f"{p}.conv1")
-            a = g.conv(a, planes, 3, stride, 1, f"{p}.conv2.weight", bn=f"{p}.bn2", relu=True,
-                       name=f"{p}.conv2")
+            project = stride != 1 or inplanes != planes * expansion
+            if block == "bottleneck":
+                w = int(planes * width_per_group / 64) * groups
+                a = g.conv(x, w, 1, 1, 0, f"{p}.conv1.weight", bn=f"{p}.bn1", relu=True, name=f"{p}.conv1")
+                a = g.conv(a, w, 3, stride, 1, f"{p}.conv2.weight", bn=f"{p}.bn2", relu=True, name=f"{p}.conv2", groups=groups)
+            else:
+                a = g.conv(x, planes, 3, stride, 1, f"{p}.conv1.weight", bn=f"{p}.bn1", relu=True, name=f"{p}.conv1")
             # the projection shortcut is emitted AFTER conv1/conv2: in the reversed (gradient)
             # order its input-gradient is then a pending addend of conv1's, which finalises x
-            if stride != 1 or inplanes != planes * 4:
-                idt = g.conv(x, planes * 4, 1, stride, 0, f"{p}.downsample.0.weight",
+            if project:
+                idt = g.conv(x, planes * expansion, 1, stride, 0, f"{p}.downsample.0.weight",
                              bn=f"{p}.downsample.1", relu=False, name=f"{p}.downsample")
             else:
                 idt = x
-            x = g.conv(a, planes * 4, 1, 1, 0, f"{p}.conv3.weight", bn=f"{p}.bn3", relu=True,
-                       residual=idt, name=f"{p}.out")
-            inplanes = planes * 4
+            if block == "bottleneck":
+                x = g.conv(a, planes * 4, 1, 1, 0, f"{p}.conv3.weight", bn=f"{p}.bn3", relu=True, residual=idt, name=f"{p}.out")
+            else:
+                x = g.conv(a, planes, 3, 1, 1, f"{p}.conv2.weight", bn=f"{p}.bn2", relu=True, residual=idt, name=f"{p}.out")
+            inplanes = planes * expansion
         g.hooks[li + 1] = x
     return g
+
+
+#: the torchvision names `build` serves through `resnet()`: name -> (block, layers, groups, width_per_group).  `arch` is the name.
+RESNET_FAMILY: Dict[str, Tuple[str, Tuple[int, ...], int, int]] = {
+    "resnet18": ("basic", (2, 2, 2, 2), 1, 64),
+    "resnet34": ("basic", (3, 4, 6, 3), 1, 64),
+    "resnet152": ("bottleneck", (3, 8, 36, 3), 1, 64),
+    "wide_resnet50_2": ("bottleneck", (3, 4, 6, 3), 1, 128),
+    "wide_resnet101_2": ("bottleneck", (3, 4, 23, 3), 1, 128),
+    "resnext50_32x4d": ("bottleneck", (3, 4, 6, 3), 32, 4),
+    "resnext101_32x8d": ("bottleneck", (3, 4, 23, 3), 32, 8),
+}
 
 
 # ---------------------------------------------------------------------------
@@ -1063,6 +1089,9 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return resnet((3, 4, 23, 3), 64, in_hw, "resnet101")
     if model_name == "resnet50":
         return resnet((3, 4, 6, 3), 64, in_hw, "resnet50")
+    if model_name in RESNET_FAMILY:     # extension: the other torchvision ResNets, Wide ResNet and ResNeXt (grouped conv2)
+        block, layers, groups, wpg = RESNET_FAMILY[model_name]
+        return resnet(layers, 64, in_hw, model_name, block, groups, wpg)
     if model_name == "vgg":
         return vgg(VGG16_CFG, in_hw, "vgg16")
     if model_name == "alexnet":
@@ -1090,6 +1119,10 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
 def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
     if model_name in ("resnet", "resnet50"):
         return resnet((2, 1, 2, 1), 8, in_hw, "resnet_tiny")
+    if model_name == "resnext_tiny":        # groups 4, conv2 widths 16 / 32 / 64 / 128: group widths 4, 8, 16, 32; both strides; a 2 x 2 plane
+        return resnet((2, 1, 2, 1), 8, in_hw, "resnext_tiny", "bottleneck", 4, 32)
+    if model_name == "resnet_basic_tiny":
+        return resnet((2, 1, 2, 1), 8, in_hw, "resnet_basic_tiny", "basic")
     if model_name == "vgg":
         cfg = (8, 8, "M", 16, 16, "M", 16, 16, 16, "M", 32, 32, 32, "M", 32, 32, 32, "M")
         return vgg(cfg, in_hw, "vgg_tiny")

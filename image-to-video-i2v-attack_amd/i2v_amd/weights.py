@@ -102,7 +102,7 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         nl = ".nonlocal_block." in nd.weight
         if nl and (".theta." in nd.weight or ".phi." in nd.weight):
             std *= 0.1
-        shape = (nd.cout, nd.cin, nd.kt, nd.kh, nd.kw) if graph.video else (nd.cout, nd.cin, nd.kh, nd.kw)
+        shape = (nd.cout, nd.cin, nd.kt, nd.kh, nd.kw) if graph.video else (nd.cout, nd.cin // nd.groups, nd.kh, nd.kw)
         sd[nd.weight] = torch.randn(*shape, generator=_gen(seed, nd.weight)) * std
         if nd.bias:
             sd[nd.bias] = torch.randn(nd.cout, generator=_gen(seed, nd.bias)) * 0.05
