@@ -148,11 +148,9 @@ extern "C" int i2v_net_set_relu_gain(i2v_handle h, int net, int tensor, float ga
     return 0;
 }
 
-extern "C" int i2v_net_add_conv3d(i2v_handle h, int net, const i2v_conv3d_desc* d, const float* weight,
-                                  const float* scale, const float* shift) {
-    Net* n = get_net(h, net); if (!n) return 1;
+// what every convolution entry checks of a node: the net open, the tensor ids, the channel counts, the geometry against the buffers
+static int check_conv(Net* n, const i2v_conv3d_desc* d) {
     if (n->planned) return fail("net already planned");
-    if (!d || !weight || !scale || !shift) return fail("i2v_net_add_conv: null argument");
     int nt = (int)n->tens.size();
     if (d->src < 0 || d->src >= nt || d->dst < 0 || d->dst >= nt || d->residual >= nt)
         return fail("i2v_net_add_conv: bad tensor id");
@@ -169,6 +167,14 @@ extern "C" int i2v_net_add_conv3d(i2v_handle h, int net, const i2v_conv3d_desc* 
         const Tensor& R = n->tens[d->residual]; const Buffer& rb = n->bufs[R.buf];
         if (R.C != d->cout || rb.H != db.H || rb.W != db.W || rb.T != db.T) return fail("residual shape mismatch");
     }
+    return 0;
+}
+
+extern "C" int i2v_net_add_conv3d(i2v_handle h, int net, const i2v_conv3d_desc* d, const float* weight,
+                                  const float* scale, const float* shift) {
+    Net* n = get_net(h, net); if (!n) return 1;
+    if (!d || !weight || !scale || !shift) return fail("i2v_net_add_conv: null argument");
+    if (check_conv(n, d)) return 1;
     Node nd; nd.type = 0; nd.cd = *d; memset(&nd.pd, 0, sizeof nd.pd);
     size_t per = (size_t)d->cin * d->kt * d->kh * d->kw;
     nd.w.resize((size_t)d->cout * per);
@@ -215,14 +221,39 @@ extern "C" int i2v_net_add_conv_grouped(i2v_handle h, int net, const i2v_conv_de
     return 0;
 }
 
-// the block-diagonal dense weight of a grouped node, for the dense route's packings
+// the block-diagonal dense weight of a grouped (or depthwise: group width 1) node, for the dense route's packings
 static void expand_grouped(Node& nd) {
     const i2v_conv3d_desc& c = nd.cd;
-    const int gi = c.cin / nd.groups, go = c.cout / nd.groups;
-    nd.w.assign((size_t)c.cout * c.cin * 9, 0.f);
+    const int gi = c.cin / nd.groups, go = c.cout / nd.groups, nt = c.kh * c.kw;
+    nd.w.assign((size_t)c.cout * c.cin * nt, 0.f);
     for (int co = 0; co < c.cout; ++co)
         for (int ci = 0; ci < gi; ++ci)
-            for (int t = 0; t < 9; ++t) nd.w[((size_t)co * c.cin + (co / go) * gi + ci) * 9 + t] = nd.wg[((size_t)co * gi + ci) * 9 + t];
+            for (int t = 0; t < nt; ++t) nd.w[((size_t)co * c.cin + (co / go) * gi + ci) * nt + t] = nd.wg[((size_t)co * gi + ci) * nt + t];
+}
+
+// A depthwise k x k convolution (k = 3 or 5).  Only the compact [C][k k] filter is kept: k_dwconv reads it as it is, and the dense
+// route (I2V_DWCONV=0, and the host simulation) expands it block-diagonally -- C times the floats -- only while a plan packs the node.
+extern "C" int i2v_net_add_conv_depthwise(i2v_handle h, int net, const i2v_conv_desc* d, const float* weight,
+                                          const float* scale, const float* shift) {
+    if (!d || !weight || !scale || !shift) return fail("i2v_net_add_conv_depthwise: null argument");
+    if (d->cin != d->cout) return fail("i2v_net_add_conv_depthwise: %d input and %d output channels (a depthwise convolution has as many out as in)", d->cin, d->cout);
+    if (d->kh != d->kw || (d->kh != 3 && d->kh != 5))
+        return fail("i2v_net_add_conv_depthwise: only square 3x3 and 5x5 filters are supported (got %dx%d)", d->kh, d->kw);
+    if (d->pad != d->kh / 2) return fail("i2v_net_add_conv_depthwise: the padding must be k / 2 = %d (got pad %d)", d->kh / 2, d->pad);
+    if (d->stride != 1 && d->stride != 2) return fail("i2v_net_add_conv_depthwise: only stride 1 or 2 is supported (got stride %d)", d->stride);
+    if (d->residual >= 0) return fail("i2v_net_add_conv_depthwise: a residual addend on a depthwise convolution is not supported");
+    Net* n = get_net(h, net); if (!n) return 1;
+    const i2v_conv3d_desc q{d->src, d->dst, d->cin, d->cout, 1, d->kh, d->kw, 1, d->stride, 0, d->pad, 1, d->relu, d->residual};
+    if (check_conv(n, &q)) return 1;
+    const int nt = d->kh * d->kw;
+    Node nd; nd.type = 0; nd.cd = q; memset(&nd.pd, 0, sizeof nd.pd);
+    nd.shift.assign(shift, shift + d->cout);
+    nd.groups = d->cin; nd.dw = d->kh;
+    nd.wg.resize((size_t)d->cout * nt);
+    for (int c = 0; c < d->cout; ++c)
+        for (int t = 0; t < nt; ++t) nd.wg[(size_t)c * nt + t] = weight[(size_t)c * nt + t] * scale[c];
+    n->nodes.push_back(std::move(nd));
+    return 0;
 }
 
 extern "C" int i2v_net_add_conv_preact(i2v_handle h, int net, const i2v_conv_desc* d, const float* weight,
@@ -316,13 +347,19 @@ extern "C" int i2v_net_plan(i2v_handle h, int net, const int* hook_tensors, int 
     for (Node& nd : n.nodes) {
         if (nd.type != 0) continue;
         if (upload(n, nd.shift, &nd.shift_d)) return 1;
-        nd.gconv = nd.groups > 1 && gconv_enabled();
+        nd.gconv = nd.groups > 1 && !nd.dw && gconv_enabled();
+        nd.dwconv = nd.dw && dwconv_enabled();
+        if (nd.dwconv) {            // compact operands only: the dense packing (C times the floats) is never made
+            if (nd.cd.src == n.input) return fail("a depthwise convolution directly on the input is not planned");
+            if (pack_dwconv(n, nd)) return 1;
+            continue;
+        }
         if (nd.gconv) {             // compact operands only: the dense packing (groups times the floats) is never made
             if (nd.cd.src == n.input) return fail("a grouped convolution directly on the input is not planned");
             if (pack_gconv(n, nd)) return 1;
             continue;
         }
-        if (nd.groups > 1) expand_grouped(nd);
+        if (nd.groups > 1 || nd.dw) expand_grouped(nd);
         if (pack_fwd(n, nd)) return 1;
         if (nd.preact()) {          // operand-side affine, padded to Kpad with zeros (relu(0*x+0) = 0 for the K tail)
             std::vector<float> ps(nd.fwd.Kpad > nd.fwd.Cdpad ? nd.fwd.Kpad : nd.fwd.Cdpad, 0.f), pt(ps.size(), 0.f);
@@ -331,7 +368,7 @@ extern "C" int i2v_net_plan(i2v_handle h, int net, const int* hook_tensors, int 
         }
         if (nd.cd.src == n.input) { if (pack_img(n, nd)) return 1; }
         else if (pack_bwd(n, nd)) return 1;
-        if (nd.groups > 1) std::vector<float>().swap(nd.w);
+        if (nd.groups > 1 || nd.dw) std::vector<float>().swap(nd.w);
     }
     size_t off = 64;            // 256 bytes of slack in front of the first tensor (and behind the last, below): the quad-row
                                 // staging of conv_igemm (MODE 4) reads a few pixels past either end of a source view

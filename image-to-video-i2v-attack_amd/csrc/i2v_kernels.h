@@ -91,6 +91,10 @@ int k_fastblock(const I2VConvParams& a, const I2VConvParams& b, const I2VConvPar
 // host simulation runs grouped nodes on the dense route).  k_gconv_plan fills the tiling fields; 0 ok, 1 the shape does not fit.
 int k_gconv_plan(I2VGConvParams* p);
 int k_gconv(const I2VGConvParams& p, i2v_stream_t s);
+// Depthwise 3x3 / 5x5 convolution (I2VDwConvParams; i2v_dwconv.hip -- product backend only, under -DI2V_HAVE_DWCONV; the host
+// simulation runs depthwise nodes on the dense route).  k_dwconv_plan fills the geometry fields; 0 ok, 1 the shape does not fit.
+int k_dwconv_plan(I2VDwConvParams* p);
+int k_dwconv(const I2VDwConvParams& p, i2v_stream_t s);
 int k_pool_fwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool_bwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool3d_fwd(const I2VPoolParams& p, i2v_stream_t s);  // video max pooling (kt/stride_t/pad_t honoured)

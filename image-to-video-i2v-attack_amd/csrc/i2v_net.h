@@ -61,6 +61,10 @@ struct Node {
     // k_gconv (product build, I2V_GCONV not 0) -- then only the compact operands gw_fwd / gw_bwd (I2VGConvParams::w) are uploaded.
     int groups = 1; std::vector<float> wg; bool gconv = false;
     float* gw_fwd = nullptr; float* gw_bwd = nullptr; int gw_tapmask[4] = {0, 0, 0, 0};
+    // depthwise convolution (i2v_net_add_conv_depthwise): groups = C, `dw` the filter size k (0: not depthwise), `wg` the compact [C][k k]
+    // filter, scale folded.  `dwconv`: this plan runs the node on k_dwconv (product build, I2V_DWCONV not 0) with the operands gw_fwd /
+    // gw_bwd ([C][k k] and [class][C][k k] mirrored; gw_tapmask per class); else the dense route expands `wg` into `w` while packing.
+    int dw = 0; bool dwconv = false;
     // input gradient of a convolution that reads the network input (class-packed): one launch -- or one per temporal class (pack_img)
     struct ImgGrad {
         Packed P; int blk = 0, sh = 1, blkt = 1;
@@ -72,12 +76,13 @@ struct Node {
     size_t idx_off = 0;                           // maxpool: arg-max bytes, arena offset in floats
 };
 
-enum Kind { L_CONV, L_IMGGRAD, L_POOLF, L_POOLB, L_ADDMASK, L_AVGF, L_AVGB, L_MEMSET, L_POOL3F, L_POOL3B, L_AGEMM, L_SOFTMAX, L_GCONV };   // L_IMGGRAD: conv_igemm with class-packed Cd
+enum Kind { L_CONV, L_IMGGRAD, L_POOLF, L_POOLB, L_ADDMASK, L_AVGF, L_AVGB, L_MEMSET, L_POOL3F, L_POOL3B, L_AGEMM, L_SOFTMAX, L_GCONV, L_DWCONV };   // L_IMGGRAD: conv_igemm with class-packed Cd
 // L_GCONV: a grouped 3x3 node on k_gconv -- `gc` is what the kernel gets; `conv` carries the same views (src, dst, gate, gate_out, mask, Cd, K =
 // 9 x group width) for the address-range analyses and the timing records, which treat it as the convolution launch it is
+// L_DWCONV: a depthwise node on k_dwconv -- `dc` is what the kernel gets, `conv` mirrors the views in the same way (K = k k)
 struct Launch {
     Kind kind;
-    I2VConvParams conv; I2VPoolParams pool; I2VAddMaskParams am; I2VGConvParams gc;
+    I2VConvParams conv; I2VPoolParams pool; I2VAddMaskParams am; I2VGConvParams gc; I2VDwConvParams dc;
     I2VAttnGemm ag; I2VSoftmaxRows sm; int sm_rows_per_clip = 0;    // L_AGEMM / L_SOFTMAX (clips are filled in at run time)
     int T = 1;                     // frames per clip of the launch's iteration space (conv launches: conv.Tg)
     bool src_is_input = false;     // conv: src pointer patched with the caller's x
@@ -175,6 +180,8 @@ int pack_bwd(Net& n, Node& nd);
 int pack_img(Net& n, Node& nd);
 bool gconv_enabled();               // grouped nodes run on k_gconv in this plan (else: the dense route)
 int pack_gconv(Net& n, Node& nd);
+bool dwconv_enabled();              // depthwise nodes run on k_dwconv in this plan (else: the dense route)
+int pack_dwconv(Net& n, Node& nd);
 
 // i2v_plan.cpp: one pass over the nodes from arena offset `off` for N frames.  Dry: nothing is emitted, *end is where the temporaries
 // end.  Real (the arena allocated): fills n.fwd, n.bwd and n.hook_tmp.  False with *err set when the graph cannot be planned.

@@ -221,6 +221,44 @@ int pack_gconv(Net& n, Node& nd) {
     return upload(n, wb, &nd.gw_bwd);
 }
 
+// Depthwise nodes run on k_dwconv where the library has it (-DI2V_HAVE_DWCONV: the product build) unless I2V_DWCONV=0 asks for the
+// dense route.  Read per plan.
+bool dwconv_enabled() {
+#ifdef I2V_HAVE_DWCONV
+    const char* e = getenv("I2V_DWCONV");
+    return !(e && e[0] == '0');
+#else
+    return false;
+#endif
+}
+
+// k_dwconv's operands (I2VDwConvParams::w).  Forward: the filter as it is, [C][k r + s].  Input gradient: per stride-parity class (ph,
+// pw) -- the classes of pack_bwd, in its order -- [C][slot k a + b] with a - pad = (ph + pad - r) / stride for the row taps r the class
+// owns (b alike): the mirrored filter, zeros in the slots the class does not own; gw_tapmask has a bit per owned slot.
+int pack_dwconv(Net& n, Node& nd) {
+    const i2v_conv3d_desc& c = nd.cd;
+    const int C = c.cin, k = c.kh, pad = c.pad, st = c.stride, nt = k * k;
+    if (upload(n, nd.wg, &nd.gw_fwd)) return 1;
+    std::vector<float> wb((size_t)st * st * C * nt, 0.f);
+    for (int ph = 0; ph < st; ++ph)
+        for (int pw = 0; pw < st; ++pw) {
+            const int cls = ph * st + pw;
+            int mask = 0;
+            for (int r = 0; r < k; ++r) {
+                if (posmod(ph + pad - r, st)) continue;
+                const int a = floordiv(ph + pad - r, st) + pad;
+                for (int s = 0; s < k; ++s) {
+                    if (posmod(pw + pad - s, st)) continue;
+                    const int b = floordiv(pw + pad - s, st) + pad;
+                    mask |= 1 << (k * a + b);
+                    for (int ch = 0; ch < C; ++ch) wb[((size_t)cls * C + ch) * nt + k * a + b] = nd.wg[(size_t)ch * nt + k * r + s];
+                }
+            }
+            nd.gw_tapmask[cls] = mask;
+        }
+    return upload(n, wb, &nd.gw_bwd);
+}
+
 // Gradient of the FIRST convolution w.r.t. the image.  GEMM-N would be Cin = 3; instead the output is
 // cut into B x B position blocks (B = stride, or 2 for stride 1) and the B*B*Cin (class, channel)
 // pairs form the Cd axis: out[(ph,pw),ci][i][j] = sum_{co,dh,dw} w'[(co,dh,dw)][(ph,pw),ci] *

@@ -148,6 +148,28 @@ struct I2VGConvParams {
     uint32_t dv_r_m, dv_r_s;             // exact division by Hs + 2 (the padded rows of a source frame)
 };
 
+// Depthwise k x k convolution (k_dwconv, i2v_dwconv.hip; k = 3 or 5, pad k / 2), forward and input gradient alike, ONE launch:
+//   dst[n][c][i os + oh0][j os + ow0] = epilogue( sum_{(a, b) in taps} w[cls][c][k a + b] * src[n][c][i S + a - pad][j S + b - pad] )
+// (zeros outside the plane; the sum is one fma chain in the order a outer, b inner) over a grid of N x Hg x Wg positions per class.
+// Forward: one class, S = stride, os = 1, all k k taps, w = the filter.  Input gradient: S = 1, os = stride, one class per stride parity
+// (oh0, ow0) with the slots that parity owns (`tapmask`, bit k a + b) of the mirrored filter.  Epilogue as I2VGConvParams.
+struct I2VDwConvClass { int32_t Hg, Wg, oh0, ow0, tapmask; uint32_t dv_w_m, dv_w_s, dv_hw_m, dv_hw_s; };
+struct I2VDwConvParams {
+    const float* src; int64_t src_nstride; int32_t Hs, Ws;
+    const float* w;                      // [ncls][C][k k], scale folded
+    int32_t C, k, N, S, ncls;
+    I2VDwConvClass cls[4];
+    float* dst; int64_t dst_nstride; int32_t Ho, Wo, os;
+    const float* shift; int32_t relu;
+    uint32_t* gate_out; int32_t gate_out_stride;
+    const uint32_t* gate; int32_t gate_stride;
+    const float* mask; int64_t mask_nstride;
+    // k_dwconv_plan: waves per block (64 positions each), staged source rows, floats per staged row, LDS bytes, 16-byte staging
+    int32_t waves, rows, pitch, lds_bytes, v4;
+    uint32_t dv_r_m, dv_r_s;             // exact division by Hs + 2 pad (the padded rows of a source frame)
+    uint32_t dv_u_m, dv_u_s;             // exact division by the staging units of a row (pitch, or pitch / 4 with 16-byte staging)
+};
+
 struct I2VPoolParams {
     const float* x;    int64_t x_nstride;    int32_t C, Hs, Ws;
     float* y;          int64_t y_nstride;    int32_t Ho, Wo;       // fwd: output; bwd: upstream grad

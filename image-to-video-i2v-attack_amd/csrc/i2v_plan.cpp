@@ -191,6 +191,54 @@ struct Planner {
         return false;
 #endif
     }
+    // A depthwise node as ONE k_dwconv launch per pass, in the same way.
+    bool dwconv_launch(const Node& nd, bool backward, int t) {
+#ifdef I2V_HAVE_DWCONV
+        const i2v_conv3d_desc& c = nd.cd;
+        const int st = c.stride, k = c.kh;
+        View s = view(backward ? c.dst : c.src, backward), d = view(backward ? c.src : c.dst, backward);
+        Launch l; l.kind = L_DWCONV; l.node = (int)(&nd - n.nodes.data()); l.T = d.T;
+        memset(&l.conv, 0, sizeof l.conv); memset(&l.dc, 0, sizeof l.dc);
+        I2VDwConvParams& q = l.dc;
+        q.src = s.p; q.src_nstride = s.nstride; q.Hs = s.H; q.Ws = s.W;
+        q.C = c.cin; q.k = k;
+        q.dst = d.p; q.dst_nstride = d.nstride; q.Ho = d.H; q.Wo = d.W;
+        if (!backward) {
+            q.w = nd.gw_fwd; q.S = st; q.os = 1; q.ncls = 1;
+            q.cls[0].Hg = d.H; q.cls[0].Wg = d.W; q.cls[0].tapmask = (1 << (k * k)) - 1;
+            q.shift = nd.shift_d; q.relu = c.relu;
+            if (c.relu) { int gs = 0; if (uint32_t* g = gate_rows(c.dst, &gs)) { q.gate_out = g; q.gate_out_stride = gs; } }
+        } else {
+            q.w = nd.gw_bwd; q.S = 1; q.os = st; q.ncls = st * st;
+            for (int ph = 0; ph < st; ++ph)
+                for (int pw = 0; pw < st; ++pw) {
+                    I2VDwConvClass& kc = q.cls[ph * st + pw];
+                    kc.Hg = (d.H - ph + st - 1) / st; kc.Wg = (d.W - pw + st - 1) / st; kc.oh0 = ph; kc.ow0 = pw; kc.tapmask = nd.gw_tapmask[ph * st + pw];
+                }
+            if (n.tens[t].post_relu) {
+                int gs = 0;
+                if (uint32_t* g = gate_rows(t, &gs)) { q.gate = g; q.gate_stride = gs; }
+                else { View a = view(t, false); q.mask = a.p; q.mask_nstride = a.nstride; }
+            }
+        }
+        if (k_dwconv_plan(&q)) { err = "a depthwise convolution does not fit k_dwconv (plan with I2V_DWCONV=0 for the dense route)"; return false; }
+        I2VConvParams& p = l.conv;
+        p.src = q.src; p.src_nstride = q.src_nstride; p.Hs = q.Hs; p.Ws = q.Ws; p.Cs = c.cin;
+        p.dst = q.dst; p.dst_nstride = q.dst_nstride; p.Ho = q.Ho; p.Wo = q.Wo; p.Hg = q.Ho; p.Wg = q.Wo;
+        p.Cd = c.cin; p.Cdpad = c.cin; p.K = p.Kpad = k * k; p.sh = p.sw = q.S; p.osh = p.osw = 1;
+        p.Tg = p.Ts = p.To = p.st = p.ost = 1; p.blkt = 1; p.oct = 1; p.add0_stride = 1;
+        p.shift = q.shift; p.relu = q.relu; p.gate = q.gate; p.gate_stride = q.gate_stride; p.gate_out = q.gate_out; p.gate_out_stride = q.gate_out_stride;
+        p.mask = q.mask; p.mask_nstride = q.mask_nstride;
+        const View o = view(c.dst, false);
+        l.alg_flops_per_frame = 2.0 * o.H * o.W * (double)c.cout * k * k;        // the node's real products: C k k Ho Wo
+        emit(backward ? n.bwd : n.fwd, l);
+        return true;
+#else
+        (void)nd; (void)backward; (void)t;
+        err = "this build has no depthwise-convolution kernel";
+        return false;
+#endif
+    }
     bool is_hook(int t) const { for (int hk : n.hooks) if (hk == t) return true; return false; }
     static bool has_compact(const std::vector<Addend>& A) { for (auto& a : A) if (a.stride != 1) return true; return false; }
 
@@ -202,6 +250,12 @@ struct Planner {
             // a bottleneck's conv1 output has the grouped conv2 as its ONLY consumer: k_gconv's epilogue takes no addends
             if (left[t] > 0 || !pending[t].empty() || has_alias[t]) { err = "the input of a grouped convolution must have it as its only consumer"; return false; }
             return gconv_launch(nd, true, t);
+        }
+        if (nd.dw) {
+            // the 1x1 expansion's output has the depthwise node as its ONLY consumer: k_dwconv writes the gradient, it never accumulates
+            // (refused on the dense route too, so that a graph plans on both routes or on neither)
+            if (left[t] > 0 || !pending[t].empty() || has_alias[t]) { err = "the input of a depthwise convolution must have it as its only consumer"; return false; }
+            if (nd.dwconv) return dwconv_launch(nd, true, t);
         }
         if (left[t] > 0) {
             bool compact = (c.kt == 1 && c.stride_t == 1 && c.pad_t == 0 && c.kh == 1 && c.kw == 1 && c.stride > 1 && c.pad == 0);
@@ -287,6 +341,7 @@ struct Planner {
             if (nd.type == 0) {
                 const i2v_conv3d_desc& c = nd.cd;
                 if (nd.gconv) { if (!gconv_launch(nd, false, c.dst)) return false; continue; }
+                if (nd.dwconv) { if (!dwconv_launch(nd, false, c.dst)) return false; continue; }
                 l.kind = L_CONV; conv_common(l.conv, nd.fwd);
                 l.node = (int)(&nd - n.nodes.data());
                 I2VConvParams& p = l.conv;

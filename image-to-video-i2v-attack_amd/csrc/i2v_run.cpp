@@ -121,7 +121,7 @@ static double launch_flops(const std::vector<Launch>& L, size_t li, int fb, int 
     const Launch& l = L[li];
     double flops = 0.0;
     if (fb) { for (int j = 0; j < fb; ++j) { const Launch& m = L[li + j]; flops += m.alg_flops_per_frame > 0 ? m.alg_flops_per_frame * frames : 2.0 * frames * m.conv.Hg * m.conv.Wg * (double)m.conv.Cd * m.conv.K; } }
-    else if ((l.kind == L_CONV || l.kind == L_GCONV) && l.alg_flops_per_frame > 0) flops = l.alg_flops_per_frame * frames;     // quad-row packings pad K; a grouped node counts its real products
+    else if ((l.kind == L_CONV || l.kind == L_GCONV || l.kind == L_DWCONV) && l.alg_flops_per_frame > 0) flops = l.alg_flops_per_frame * frames;     // quad-row packings pad K; a grouped node counts its real products
     else if (l.kind == L_CONV) flops = 2.0 * frames * l.conv.Hg * l.conv.Wg * ((double)l.conv.Cd * l.conv.K + (fuse ? (double)L[li + 1].conv.Cd * L[li + 1].conv.K : 0.0));
     else if (l.kind == L_IMGGRAD) flops = l.alg_flops_per_frame * frames;
     else if (l.kind == L_AGEMM) flops = 2.0 * clips * (double)l.ag.Cc * l.ag.M * l.ag.N;
@@ -131,7 +131,7 @@ static double launch_flops(const std::vector<Launch>& L, size_t li, int fb, int 
 // timing kinds: 0 conv fwd, 1 image gradient, 2 pool fwd, 3 pool bwd, 4 addmask, 5 conv input-gradient
 static int launch_timing_kind(const Launch& l, bool backward_pass) {
     switch (l.kind) {
-        case L_CONV: case L_AGEMM: case L_GCONV: return backward_pass ? 5 : 0;
+        case L_CONV: case L_AGEMM: case L_GCONV: case L_DWCONV: return backward_pass ? 5 : 0;
         case L_IMGGRAD: return 1;
         case L_POOLF: case L_AVGF: case L_POOL3F: return 2;
         case L_POOLB: case L_AVGB: case L_POOL3B: return 3;
@@ -193,7 +193,7 @@ struct ListTiming {
         const Launch& l = L[li];
         const int kind = launch_timing_kind(l, backward_pass);
         const double flops = launch_flops(L, li, fb, fuse, frames, clips);
-        const bool conv = l.kind == L_CONV || l.kind == L_IMGGRAD || l.kind == L_GCONV;
+        const bool conv = l.kind == L_CONV || l.kind == L_IMGGRAD || l.kind == L_GCONV || l.kind == L_DWCONV;
         if (h->timing == 2) {
             if (!seg || seg->kind != kind) {
                 close();
@@ -301,6 +301,13 @@ static int run_list(i2v_ctx* h, Net& n, std::vector<Launch>& L, int in_frames, c
                 I2VGConvParams p = l.gc; p.N = frames; CHECK_BE(k_gconv(p, s));
 #else
                 return fail("this build has no grouped-convolution kernel");
+#endif
+            } break;
+            case L_DWCONV: {
+#ifdef I2V_HAVE_DWCONV
+                I2VDwConvParams p = l.dc; p.N = frames; CHECK_BE(k_dwconv(p, s));
+#else
+                return fail("this build has no depthwise-convolution kernel");
 #endif
             } break;
             case L_POOLF: { I2VPoolParams p = l.pool; p.N = frames; CHECK_BE(k_pool_fwd(p, s)); } break;

@@ -27,7 +27,7 @@ void mark_fusable(Net& n) {
     // every memory range a launch reads or writes, with the launch's OWN frame count; `skip_src` / `skip_dst` leave out the operand
     // that legitimately is the intermediate (b's source, a's destination)
     auto touches = [&](const Launch& c, const Range& w, bool skip_src, bool skip_dst) {
-        if (c.kind == L_CONV || c.kind == L_IMGGRAD || c.kind == L_GCONV) {
+        if (c.kind == L_CONV || c.kind == L_IMGGRAD || c.kind == L_GCONV || c.kind == L_DWCONV) {
             const I2VConvParams& q = c.conv;
             const int64_t fs = clips * std::max(1, q.Ts), fo = clips * std::max(1, q.To), dplane = (int64_t)(q.blk > 1 ? q.Cd / (q.blk * q.blk) : q.Cd) * q.Ho * q.Wo;
             return (!skip_src && meet(w, rng(q.src, fs, q.src_nstride, (int64_t)q.Cs * q.Hs * q.Ws))) ||
@@ -197,7 +197,7 @@ void mark_overlap(Net& n) {
         RW o;
         auto rd = [&](const Range& x) { if (x.first) o.r.push_back(x); };
         auto wr = [&](const Range& x) { if (x.first) o.w.push_back(x); };
-        if (c.kind == L_CONV || c.kind == L_IMGGRAD || c.kind == L_GCONV) {
+        if (c.kind == L_CONV || c.kind == L_IMGGRAD || c.kind == L_GCONV || c.kind == L_DWCONV) {
             const I2VConvParams& q = c.conv;
             const int64_t fs = clips * std::max(1, q.Ts), fo = clips * std::max(1, q.To);
             const int64_t dplane = 4ll * (q.blk > 1 ? q.Cd / (q.blk * q.blk) : q.Cd) * q.Ho * q.Wo;

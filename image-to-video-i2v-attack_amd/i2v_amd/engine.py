@@ -364,6 +364,8 @@ class Net:
                     ps, pt = ps.contiguous(), pt.contiguous()
                     _lib.check(capi, capi.i2v_net_add_conv_preact(h, self.id, C.byref(d), _hptr(w), _hptr(scale), _hptr(shift),
                                                                   _hptr(ps), _hptr(pt)))
+                elif getattr(nd, "groups", 1) > 1 and nd.groups == nd.cin == nd.cout:        # depthwise
+                    _lib.check(capi, capi.i2v_net_add_conv_depthwise(h, self.id, C.byref(d), _hptr(w), _hptr(scale), _hptr(shift)))
                 elif getattr(nd, "groups", 1) > 1:
                     _lib.check(capi, capi.i2v_net_add_conv_grouped(h, self.id, C.byref(d), nd.groups, _hptr(w), _hptr(scale), _hptr(shift)))
                 else:

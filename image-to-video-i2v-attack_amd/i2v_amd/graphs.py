@@ -57,7 +57,7 @@ class ConvNode:
     stride_t: int = 1
     pad_t: int = 0
     dil_t: int = 1
-    groups: int = 1             # grouped convolution (ResNeXt): the weight is (cout, cin // groups, kh, kw)
+    groups: int = 1             # grouped convolution (ResNeXt; depthwise: groups == cin == cout): the weight is (cout, cin // groups, kh, kw)
 
 
 @dataclass
@@ -308,6 +308,72 @@ RESNET_FAMILY: Dict[str, Tuple[str, Tuple[int, ...], int, int]] = {
     "resnext50_32x4d": ("bottleneck", (3, 4, 6, 3), 32, 4),
     "resnext101_32x8d": ("bottleneck", (3, 4, 23, 3), 32, 8),
 }
+
+
+# ---------------------------------------------------------------------------
+# torchvision MNASNet (`_version` 2): depthwise-separable inverted residuals
+# ---------------------------------------------------------------------------
+#: name -> alpha.  `arch` and the checkpoint file are the torchvision name.
+MNASNET_MODELS: Dict[str, float] = {"mnasnet0_5": 0.5, "mnasnet0_75": 0.75, "mnasnet1_0": 1.0, "mnasnet1_3": 1.3}
+#: torchvision's stacks `layers.8 .. layers.13`: (kernel, stride, expansion, repeats)
+MNASNET_STACKS = ((3, 2, 3, 3), (5, 2, 3, 3), (5, 2, 6, 3), (3, 1, 6, 2), (5, 2, 6, 4), (3, 1, 6, 1))
+#: depth d -> the stack hooked: the last block at ResNet's stride for that depth (4, 8, 16, 32)
+MNASNET_HOOKS = {1: 8, 2: 9, 3: 11, 4: 13}
+
+
+def _round_to_multiple_of(val, divisor, round_up_bias=0.9):
+    new_val = max(divisor, int(val + divisor / 2) // divisor * divisor)
+    return new_val if new_val >= round_up_bias * val else new_val + divisor
+
+
+def mnasnet_depths(alpha: float) -> List[int]:
+    return [_round_to_multiple_of(d * alpha, 8) for d in (32, 16, 24, 40, 80, 96, 192, 320)]
+
+
+def mnasnet(alpha=1.0, in_hw=(224, 224), arch="mnasnet1_0", depths=None, stacks=MNASNET_STACKS) -> Graph:
+    """torchvision `MNASNet(alpha)` up to `layers.13`.  Stem `layers.0-2` 3x3 / 2 + BN + ReLU, `layers.3-5` depthwise 3x3 + BN + ReLU,
+    `layers.6-7` 1x1 + BN (linear); then six stacks of `_InvertedResidual`: 1x1 expand + ReLU, depthwise k x k / stride + ReLU, 1x1
+    project (linear), + the block's input when `in == out and stride == 1`.  Hook d = output of stack `MNASNET_HOOKS[d]` (a linear
+    tensor: `post_relu` false).  `depths` / `stacks` override the widths and the stack table (the test-size twin)."""
+    depths = list(depths) if depths is not None else mnasnet_depths(alpha)
+    g = Graph(arch, in_hw)
+    x = g.new_tensor(3, in_hw[0], in_hw[1], False, "input")
+    g.input = x
+    x = g.conv(x, depths[0], 3, 2, 1, "layers.0.weight", bn="layers.1", relu=True, name="layers.0")
+    x = g.conv(x, depths[0], 3, 1, 1, "layers.3.weight", bn="layers.4", relu=True, name="layers.3", groups=depths[0])
+    x = g.conv(x, depths[1], 1, 1, 0, "layers.6.weight", bn="layers.7", relu=False, name="layers.6")
+    cin = depths[1]
+    hook_of = {v: k for k, v in MNASNET_HOOKS.items()}
+    for si, (k, stride, exp, repeats) in enumerate(stacks):
+        cout = depths[si + 2]
+        for b in range(repeats):
+            p = f"layers.{si + 8}.{b}.layers"
+            s = stride if b == 0 else 1
+            mid = cin * exp
+            a = g.conv(x, mid, 1, 1, 0, f"{p}.0.weight", bn=f"{p}.1", relu=True, name=f"{p}.0")
+            a = g.conv(a, mid, k, s, k // 2, f"{p}.3.weight", bn=f"{p}.4", relu=True, name=f"{p}.3", groups=mid)
+            x = g.conv(a, cout, 1, 1, 0, f"{p}.6.weight", bn=f"{p}.7", relu=False, residual=x if (cin == cout and s == 1) else None,
+                       name=f"layers.{si + 8}.{b}")
+            cin = cout
+        if si + 8 in hook_of:
+            g.hooks[hook_of[si + 8]] = x
+    return g
+
+
+def is_mnasnet_name(model_name: str) -> bool:
+    return model_name in MNASNET_MODELS or model_name.startswith("mnasnet")
+
+
+#: mobile-class families that are not served yet, each with the ingredient it still needs on top of the depthwise kernel
+MOBILE_NOT_SERVED = (("mobilenet", "MobileNetV2 / V3 need a capped ReLU (ReLU6) and hard-swish, with their gates, in the convolution epilogue"),
+                     ("shufflenet", "ShuffleNetV2 needs channel shuffle and split"),
+                     ("efficientnet", "EfficientNet needs SiLU and squeeze-excite"))
+
+
+def mnasnet_named(model_name: str, in_hw=(224, 224)) -> Graph:
+    if model_name not in MNASNET_MODELS:
+        raise ValueError(f"MNASNet surrogate {model_name!r}: not a torchvision MNASNet; served: " + ", ".join(MNASNET_MODELS))
+    return mnasnet(MNASNET_MODELS[model_name], in_hw, model_name)
 
 
 # ---------------------------------------------------------------------------
@@ -1092,6 +1158,11 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
     if model_name in RESNET_FAMILY:     # extension: the other torchvision ResNets, Wide ResNet and ResNeXt (grouped conv2)
         block, layers, groups, wpg = RESNET_FAMILY[model_name]
         return resnet(layers, 64, in_hw, model_name, block, groups, wpg)
+    if is_mnasnet_name(model_name):     # extension: torchvision's MNASNet family (depthwise 3x3 / 5x5 convolutions)
+        return mnasnet_named(model_name, in_hw)
+    for prefix, why in MOBILE_NOT_SERVED:
+        if model_name.startswith(prefix):
+            raise ValueError(f"{model_name!r} is not served: {why}; the mobile-class names served: " + ", ".join(MNASNET_MODELS))
     if model_name == "vgg":
         return vgg(VGG16_CFG, in_hw, "vgg16")
     if model_name == "alexnet":
@@ -1123,6 +1194,9 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return resnet((2, 1, 2, 1), 8, in_hw, "resnext_tiny", "bottleneck", 4, 32)
     if model_name == "resnet_basic_tiny":
         return resnet((2, 1, 2, 1), 8, in_hw, "resnet_basic_tiny", "basic")
+    if model_name == "mnasnet_tiny":        # both filter sizes, both strides, identity blocks, 5x5 filters on 4x4 and 2x2 planes; a last plane of 2 x 2
+        return mnasnet(1.0, in_hw, "mnasnet_tiny", depths=(8, 8, 8, 8, 16, 16, 16, 24),
+                       stacks=((3, 2, 3, 2), (5, 2, 3, 2), (5, 2, 6, 1), (3, 1, 6, 2), (5, 2, 6, 2), (3, 1, 6, 1)))
     if model_name == "vgg":
         cfg = (8, 8, "M", 16, 16, "M", 16, 16, 16, "M", 32, 32, 32, "M", 32, 32, 32, "M")
         return vgg(cfg, in_hw, "vgg_tiny")

@@ -55,6 +55,7 @@ _PROTOS = {
     "i2v_net_set_relu_gain": ([_P, _I, _I, _F], _I),
     "i2v_net_add_conv": ([_P, _I, C.POINTER(ConvDesc), _P, _P, _P], _I),
     "i2v_net_add_conv_grouped": ([_P, _I, C.POINTER(ConvDesc), _I, _P, _P, _P], _I),
+    "i2v_net_add_conv_depthwise": ([_P, _I, C.POINTER(ConvDesc), _P, _P, _P], _I),
     "i2v_net_add_maxpool": ([_P, _I, C.POINTER(PoolDesc)], _I),
     "i2v_net_add_conv_preact": ([_P, _I, C.POINTER(ConvDesc), _P, _P, _P, _P, _P], _I),
     "i2v_net_add_avgpool": ([_P, _I, C.POINTER(PoolDesc)], _I),

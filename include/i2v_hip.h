@@ -77,12 +77,21 @@ int i2v_net_add_conv(i2v_handle h, int net, const i2v_conv_desc* d, const float*
 /* Grouped 3x3 convolution (torchvision ResNeXt's conv2: `nn.Conv2d(width, width, 3, stride, 1, groups=groups)`) + scale/shift [+ ReLU].
  * weight: host [cout][cin / groups][3][3]; output channel co reads input channels (co / (cout / groups)) * (cin / groups) + 0 .. cin / groups - 1.
  * groups == 1 is i2v_net_add_conv.  Refused (i2v_last_error): cin or cout not divisible by groups, anything but 3x3 / pad 1 / stride 1
- * or 2, a residual addend, and a group width (cin / groups == cout / groups) outside {4, 8, 16, 32, 64} -- depthwise is not offered.
+ * or 2, a residual addend, and a group width (cin / groups == cout / groups) outside {4, 8, 16, 32, 64} -- depthwise (group width 1) has an
+ * entry of its own, i2v_net_add_conv_depthwise below.
  * The node's input must have it as its only consumer.  One kernel launch per pass ("gconv_launches" of i2v_backend_stat); the
  * developer switch I2V_GCONV=0 (read when the net is planned) runs the node through the dense convolution path on a block-diagonal
  * weight instead: groups times the products, the yardstick the kernel is measured against. */
 int i2v_net_add_conv_grouped(i2v_handle h, int net, const i2v_conv_desc* d, int groups, const float* weight,
                              const float* scale, const float* shift);
+/* Depthwise k x k convolution (torchvision MNASNet's `nn.Conv2d(C, C, k, stride, k // 2, groups=C)`) + scale/shift [+ ReLU].
+ * weight: host [C][1][k][k]; output channel c reads input channel c only.  Refused (i2v_last_error): cin != cout, kh != kw or k outside
+ * {3, 5}, pad != k / 2, a stride outside {1, 2}, a residual addend.  The node's input must have it as its only consumer (checked when
+ * the net is planned).  One kernel launch per pass ("dwconv_launches" of i2v_backend_stat); the developer switch I2V_DWCONV=0 (read
+ * when the net is planned) runs the node through the dense convolution path on a block-diagonal weight instead: C times the products
+ * and a C x C x k x k packed weight, the yardstick the kernel is measured against. */
+int i2v_net_add_conv_depthwise(i2v_handle h, int net, const i2v_conv_desc* d, const float* weight,
+                               const float* scale, const float* shift);   /* weight: host [C][1][k][k] */
 int i2v_net_add_maxpool(i2v_handle h, int net, const i2v_pool_desc* d);
 /* DenseNet extension (not a backbone the reference can hook; BASELINE.json configs[2] names DenseNet-121):
  * a 1x1/stride-1 convolution that reads relu(x*pre_scale + pre_shift) -- torchvision `_DenseLayer`
