@@ -323,6 +323,39 @@ extern "C" int i2v_net_add_attention(i2v_handle h, int net, const i2v_attn_desc*
     return 0;
 }
 
+// A squeeze-and-excitation node.  fc2's weight is kept transposed, [rd][C]: every sum of the excite kernel then walks coalesced rows.
+extern "C" int i2v_net_add_se(i2v_handle h, int net, const i2v_se_desc* d, const float* W1, const float* b1, const float* W2, const float* b2) {
+    if (!d || !W1 || !b1 || !W2 || !b2) return fail("i2v_net_add_se: null argument");
+    Net* n = get_net(h, net); if (!n) return 1;
+    if (n->planned) return fail("net already planned");
+    const int nt = (int)n->tens.size();
+    if (d->src < 0 || d->src >= nt || d->dst < 0 || d->dst >= nt || d->residual >= nt || d->src == d->dst) return fail("i2v_net_add_se: bad tensor id");
+    const Tensor& S = n->tens[d->src]; const Tensor& D = n->tens[d->dst];
+    const Buffer& sb = n->bufs[S.buf]; const Buffer& db = n->bufs[D.buf];
+    if (S.C != d->C || D.C != d->C) return fail("i2v_net_add_se: C = %d, but src has %d channels and dst %d", d->C, S.C, D.C);
+    if (d->rd < 1) return fail("i2v_net_add_se: rd = %d (the squeezed width must be at least 1)", d->rd);
+    if (d->rd > 8192) return fail("i2v_net_add_se: rd = %d (at most 8192 squeezed channels are supported)", d->rd);
+    if (sb.T != 1 || db.T != 1) return fail("i2v_net_add_se: video tensors (more than one frame per clip) are not supported yet");
+    if (sb.H != db.H || sb.W != db.W) return fail("i2v_net_add_se: src plane %dx%d and dst plane %dx%d differ", sb.H, sb.W, db.H, db.W);
+    if (S.post_relu) return fail("i2v_net_add_se: src must be the linear output of a convolution, not the output of a ReLU");
+    if ((d->relu != 0) != D.post_relu) return fail("i2v_net_add_se: relu = %d, but dst is %sdeclared the output of a ReLU", d->relu, D.post_relu ? "" : "not ");
+    if (d->residual >= 0) {
+        const Tensor& R = n->tens[d->residual]; const Buffer& rb = n->bufs[R.buf];
+        if (R.C != d->C || rb.H != db.H || rb.W != db.W || rb.T != db.T)
+            return fail("i2v_net_add_se: residual shape %dx%dx%d does not match dst %dx%dx%d", R.C, rb.H, rb.W, d->C, db.H, db.W);
+        if (d->residual == d->src || d->residual == d->dst) return fail("i2v_net_add_se: the residual must be a tensor of its own");
+    }
+    Node nd; nd.type = 4; nd.sd = *d; memset(&nd.cd, 0, sizeof nd.cd); memset(&nd.pd, 0, sizeof nd.pd);
+    nd.cd.residual = -1;
+    const size_t C = (size_t)d->C, rd = (size_t)d->rd;
+    nd.se_w1.assign(W1, W1 + rd * C); nd.se_b1.assign(b1, b1 + rd); nd.se_b2.assign(b2, b2 + C);
+    nd.se_w2t.resize(rd * C);
+    for (size_t c = 0; c < C; ++c)
+        for (size_t j = 0; j < rd; ++j) nd.se_w2t[j * C + c] = W2[c * rd + j];
+    n->nodes.push_back(std::move(nd));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // planning
 // ---------------------------------------------------------------------------------------------
@@ -345,6 +378,7 @@ extern "C" int i2v_net_plan(i2v_handle h, int net, const int* hook_tensors, int 
     if (max_frames % Tin) return fail("max_frames=%d is not a multiple of the input's %d frames per clip", max_frames, Tin);
 
     for (Node& nd : n.nodes) {
+        if (nd.type == 4 && (upload(n, nd.se_w1, &nd.se_w1_d) || upload(n, nd.se_b1, &nd.se_b1_d) || upload(n, nd.se_w2t, &nd.se_w2t_d) || upload(n, nd.se_b2, &nd.se_b2_d))) return 1;
         if (nd.type != 0) continue;
         if (upload(n, nd.shift, &nd.shift_d)) return 1;
         nd.gconv = nd.groups > 1 && !nd.dw && gconv_enabled();
@@ -389,6 +423,8 @@ extern "C" int i2v_net_plan(i2v_handle h, int net, const int* hook_tensors, int 
     const bool use_gates = !(gates_env && gates_env[0] == '0');
     for (const Node& nd : n.nodes)
         if (use_gates && nd.type == 0 && nd.cd.relu && !nd.fwd.tpair) n.bufs[n.tens[nd.cd.dst].buf].gated = true;   // (the class-packed epilogue writes no gate words)
+    for (const Node& nd : n.nodes)
+        if (use_gates && nd.type == 4 && nd.sd.relu) n.bufs[n.tens[nd.sd.dst].buf].gated = true;   // (the scale launch writes the rows)
     for (Buffer& b : n.bufs) {
         if (!b.gated) continue;
         const size_t pix = N / Tin * b.T * b.H * b.W;
@@ -405,6 +441,12 @@ extern "C" int i2v_net_plan(i2v_handle h, int net, const int* hook_tensors, int 
         if (nd.type == 3) {
             const Buffer& tb = n.bufs[n.tens[nd.ad.theta].buf]; const Buffer& pb = n.bufs[n.tens[nd.ad.phi].buf];
             nd.p_off = off; off = align_up(off + N / Tin * ((size_t)tb.T * tb.H * tb.W) * ((size_t)pb.T * pb.H * pb.W), 64);
+        }
+    for (Node& nd : n.nodes)
+        if (nd.type == 4) {     // m, h, s (forward to backward) and t, dm / HW (backward): (4 C + rd) floats per frame, each vector on a 256-byte boundary
+            const size_t C = (size_t)nd.sd.C, rd = (size_t)nd.sd.rd;
+            nd.se_off = off; nd.se_floats = 4 * align_up(N * C, 64) + align_up(N * rd, 64);
+            off += nd.se_floats;
         }
     std::string err;
     size_t end = 0;

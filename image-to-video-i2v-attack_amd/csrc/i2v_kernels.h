@@ -95,6 +95,13 @@ int k_gconv(const I2VGConvParams& p, i2v_stream_t s);
 // simulation runs depthwise nodes on the dense route).  k_dwconv_plan fills the geometry fields; 0 ok, 1 the shape does not fit.
 int k_dwconv_plan(I2VDwConvParams* p);
 int k_dwconv(const I2VDwConvParams& p, i2v_stream_t s);
+// Squeeze-and-excitation node (I2VSeParams; i2v_se.hip -- product backend only, under -DI2V_HAVE_SE; without it the engine units run
+// the node as scalar host code, i2v_se_host.h).  k_se_plan fills the division fields; 0 ok, 1 the shape does not fit.  Each of the
+// three runs forward or backward by p.backward.
+int k_se_plan(I2VSeParams* p);
+int k_se_squeeze(const I2VSeParams& p, i2v_stream_t s);
+int k_se_excite(const I2VSeParams& p, i2v_stream_t s);
+int k_se_scale(const I2VSeParams& p, i2v_stream_t s);
 int k_pool_fwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool_bwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool3d_fwd(const I2VPoolParams& p, i2v_stream_t s);  // video max pooling (kt/stride_t/pad_t honoured)

@@ -44,11 +44,18 @@ struct Packed {               // one implicit-GEMM operand set
 };
 
 struct Node {
-    int type;                 // 0 conv, 1 maxpool, 2 avgpool, 3 attention core (non-local block)
+    int type;                 // 0 conv, 1 maxpool, 2 avgpool, 3 attention core (non-local block), 4 squeeze-and-excitation
+    // type 4 (i2v_net_add_se): fc1's weight [rd][C] and bias, fc2's weight TRANSPOSED [rd][C] and bias, host and uploaded; `se_off`: the
+    // node's per-frame vectors in the arena -- m [N][C], h [N][rd], s [N][C] (forward to backward), t [N][C], dm / HW [N][C] (backward)
+    i2v_se_desc sd{};
+    std::vector<float> se_w1, se_b1, se_w2t, se_b2;
+    float* se_w1_d = nullptr; float* se_b1_d = nullptr; float* se_w2t_d = nullptr; float* se_b2_d = nullptr;
+    size_t se_off = 0, se_floats = 0;
     i2v_attn_desc ad{};       // type 3
     size_t p_off = 0;         // type 3: the attention matrix P [clips][M][N] (kept for the input-gradient pass), arena offset
-    int src0() const { return type == 0 ? cd.src : type == 3 ? ad.theta : pd.src; }
-    int dst0() const { return type == 0 ? cd.dst : type == 3 ? ad.dst : pd.dst; }
+    int src0() const { return type == 0 ? cd.src : type == 3 ? ad.theta : type == 4 ? sd.src : pd.src; }
+    int dst0() const { return type == 0 ? cd.dst : type == 3 ? ad.dst : type == 4 ? sd.dst : pd.dst; }
+    int residual0() const { return type == 0 ? cd.residual : type == 4 ? sd.residual : -1; }
     i2v_conv3d_desc cd; i2v_pool3d_desc pd;        // image nodes are stored as kt = 1 video nodes
     std::vector<float> w;     // [cout][cin][kt][kh][kw] with scale folded
     std::vector<float> shift;
@@ -76,18 +83,23 @@ struct Node {
     size_t idx_off = 0;                           // maxpool: arg-max bytes, arena offset in floats
 };
 
-enum Kind { L_CONV, L_IMGGRAD, L_POOLF, L_POOLB, L_ADDMASK, L_AVGF, L_AVGB, L_MEMSET, L_POOL3F, L_POOL3B, L_AGEMM, L_SOFTMAX, L_GCONV, L_DWCONV };   // L_IMGGRAD: conv_igemm with class-packed Cd
+enum Kind { L_CONV, L_IMGGRAD, L_POOLF, L_POOLB, L_ADDMASK, L_AVGF, L_AVGB, L_MEMSET, L_POOL3F, L_POOL3B, L_AGEMM, L_SOFTMAX, L_GCONV, L_DWCONV,
+            L_SE_SQUEEZE, L_SE_EXCITE, L_SE_SCALE };   // L_IMGGRAD: conv_igemm with class-packed Cd
 // L_GCONV: a grouped 3x3 node on k_gconv -- `gc` is what the kernel gets; `conv` carries the same views (src, dst, gate, gate_out, mask, Cd, K =
 // 9 x group width) for the address-range analyses and the timing records, which treat it as the convolution launch it is
 // L_DWCONV: a depthwise node on k_dwconv -- `dc` is what the kernel gets, `conv` mirrors the views in the same way (K = k k)
+// L_SE_*: the three launches of a squeeze-and-excitation node per pass (`se`; se.backward tells the pass).  No pass that matches on
+// L_CONV sees them; the address-range analyses of i2v_tune.cpp read their views (x, g, r, dst, the node's vectors) from `se`
 struct Launch {
     Kind kind;
-    I2VConvParams conv; I2VPoolParams pool; I2VAddMaskParams am; I2VGConvParams gc; I2VDwConvParams dc;
+    I2VConvParams conv; I2VPoolParams pool; I2VAddMaskParams am; I2VGConvParams gc; I2VDwConvParams dc; I2VSeParams se;
     I2VAttnGemm ag; I2VSoftmaxRows sm; int sm_rows_per_clip = 0;    // L_AGEMM / L_SOFTMAX (clips are filled in at run time)
     int T = 1;                     // frames per clip of the launch's iteration space (conv launches: conv.Tg)
     bool src_is_input = false;     // conv: src pointer patched with the caller's x
     bool img_accumulate = false;   // L_IMGGRAD of a second convolution reading the input (two-pathway stems): gx += ...
     float* ms_ptr = nullptr; size_t ms_floats_per_frame = 0;   // L_MEMSET
+    float* se_vec = nullptr; size_t se_vec_floats = 0;   // L_SE_*: the node's per-frame vectors (one block, Node::se_off, se_floats)
+    double se_bytes_per_frame = 0; // L_SE_*: algorithmic bytes
     bool ms_gx = false;            // L_MEMSET of the caller's gradient output (skipped when accumulating)
     double alg_flops_per_frame = 0; // L_IMGGRAD: algorithmic (not class-padded) flops
     // conv launches: the autotuner's tile configuration (conv.cfg encoding) per batch bucket b = clips in (max >> (b + 1), max >> b];

@@ -170,6 +170,31 @@ struct I2VDwConvParams {
     uint32_t dv_u_m, dv_u_s;             // exact division by the staging units of a row (pitch, or pitch / 4 with 16-byte staging)
 };
 
+// Squeeze-and-excitation node (k_se_squeeze / k_se_excite / k_se_scale, i2v_se.hip; the same arithmetic as scalar host code in
+// i2v_se_host.h), three launches per pass over N frames of C planes of HW positions:
+//   forward   squeeze  m[n][c] = inv_hw * sum_p x[n][c][p]
+//             excite   h[n][j] = relu(b1[j] + sum_c w1[j][c] m[n][c]);  s[n][c] = 1 / (1 + exp(-(b2[c] + sum_j w2t[j][c] h[n][j])))
+//             scale    dst[n][c][p] = act(x[n][c][p] * s[n][c] + r[n][c][p])                  (r optional; act = ReLU or identity)
+//   backward  squeeze  t[n][c] = sum_p g[n][c][p] * x[n][c][p]
+//             excite   dz2 = (t * s) * (1 - s);  dh[j] = sum_c w2t[j][c] dz2[c] where h[j] > 0, else 0;  dmh[c] = inv_hw * sum_j w1[j][c] dh[j]
+//             scale    dst[n][c][p] = g[n][c][p] * s[n][c] + dmh[n][c]                        (dst: the gradient of x, written, never accumulated)
+// Order of every sum (it depends on HW, C and rd alone): a plane sum gives element e to lane (e / 4) % 64, each lane adds its elements
+// in increasing e from 0.f (the product g x rounded first), then the 64 lanes fold as v[l] += v[l + o] for o = 32, 16, .. 1; a sum over c gives c to lane c % 64, each lane
+// one fma chain in increasing c from 0.f, the same fold, then + the bias; a sum over j is one fma chain j = 0 .. rd - 1 from 0.f, then + the bias.
+// A forward scale launch with ReLU writes dst's gate rows (`gate_out`: bit n HW + p of row c) itself.
+struct I2VSeParams {
+    const float* x; int64_t x_nstride;           // the node's source
+    const float* g; int64_t g_nstride;           // backward: the gradient of dst
+    const float* r; int64_t r_nstride;           // forward scale: the residual, or null
+    float* dst; int64_t dst_nstride;             // scale: forward the node's output, backward the gradient of x
+    const float *w1, *b1, *w2t, *b2;             // [rd][C], [rd], [rd][C] (fc2's weight transposed), [C]
+    float *m, *h, *s, *t, *dmh;                  // [N][C], [N][rd], [N][C], [N][C], [N][C]
+    int32_t N, C, rd, HW, relu, backward;
+    float inv_hw;                                // 1.f / HW
+    uint32_t* gate_out; int32_t gate_out_stride;
+    uint32_t dv_hw_m, dv_hw_s;                   // exact division by HW (k_se_plan)
+};
+
 struct I2VPoolParams {
     const float* x;    int64_t x_nstride;    int32_t C, Hs, Ws;
     float* y;          int64_t y_nstride;    int32_t Ho, Wo;       // fwd: output; bwd: upstream grad

@@ -1,5 +1,8 @@
 // The planner: a net's nodes as a forward and an input-gradient launch list (see the file header of i2v_engine.cpp).
 #include "i2v_net.h"
+#ifndef I2V_HAVE_SE
+#include "i2v_se_host.h"
+#endif
 
 #include <string.h>
 
@@ -239,6 +242,48 @@ struct Planner {
         return false;
 #endif
     }
+    // A squeeze-and-excitation node as its three launches of one pass.  Forward: x = the source, dst = the node's output (its gate rows
+    // written by the scale launch).  Backward: g = the gradient of the output as the arena holds it, dst = the gradient of the source.
+    bool se_launches(const Node& nd, bool backward) {
+        const i2v_se_desc& d = nd.sd;
+        const View x = view(d.src, false);
+        Launch l; l.node = (int)(&nd - n.nodes.data()); l.T = x.T;
+        memset(&l.conv, 0, sizeof l.conv); memset(&l.se, 0, sizeof l.se);
+        I2VSeParams& q = l.se;
+        const size_t C = (size_t)d.C, vc = align_up(N * C, 64), vr = align_up(N * (size_t)d.rd, 64);
+        float* vec = base() + nd.se_off;
+        q.x = x.p; q.x_nstride = x.nstride;
+        q.w1 = nd.se_w1_d; q.b1 = nd.se_b1_d; q.w2t = nd.se_w2t_d; q.b2 = nd.se_b2_d;
+        q.m = vec; q.h = vec + vc; q.s = vec + vc + vr; q.t = vec + 2 * vc + vr; q.dmh = vec + 3 * vc + vr;
+        q.C = d.C; q.rd = d.rd; q.HW = x.H * x.W; q.backward = backward ? 1 : 0;
+        l.se_vec = vec; l.se_vec_floats = nd.se_floats;
+        if (!backward) {
+            const View o = view(d.dst, false);
+            q.dst = o.p; q.dst_nstride = o.nstride; q.relu = d.relu;
+            if (d.residual >= 0) { const View r = view(d.residual, false); q.r = r.p; q.r_nstride = r.nstride; }
+            if (d.relu) { int gs = 0; if (uint32_t* gr = gate_rows(d.dst, &gs)) { q.gate_out = gr; q.gate_out_stride = gs; } }
+        } else {
+            const View g = view(d.dst, true), gx = view(d.src, true);
+            q.g = g.p; q.g_nstride = g.nstride; q.dst = gx.p; q.dst_nstride = gx.nstride;
+        }
+#ifdef I2V_HAVE_SE
+        if (k_se_plan(&q)) { err = "a squeeze-and-excitation node does not fit its kernels"; return false; }
+#else
+        if (se_host::plan(&q)) { err = "a squeeze-and-excitation node does not fit"; return false; }
+#endif
+        std::vector<Launch>& L = backward ? n.bwd : n.fwd;
+        const double plane = (double)C * q.HW;
+        // algorithmic bytes per frame: squeeze reads the plane (both planes backward); excite the two matrices and the vectors; scale
+        // reads the plane (+ the residual) and writes one (+ the gate bits)
+        l.kind = L_SE_SQUEEZE; l.alg_flops_per_frame = (backward ? 2.0 : 1.0) * plane; l.se_bytes_per_frame = 4.0 * ((backward ? 2.0 : 1.0) * plane + C);
+        emit(L, l);
+        l.kind = L_SE_EXCITE; l.alg_flops_per_frame = 4.0 * C * d.rd; l.se_bytes_per_frame = 4.0 * (2.0 * C * d.rd + 3.0 * C + 2.0 * d.rd);
+        emit(L, l);
+        l.kind = L_SE_SCALE; l.alg_flops_per_frame = 2.0 * plane;
+        l.se_bytes_per_frame = 4.0 * (2.0 * plane + 2.0 * C + ((!backward && q.r) ? plane : 0.0)) + (q.gate_out ? plane / 8.0 : 0.0);
+        emit(L, l);
+        return true;
+    }
     bool is_hook(int t) const { for (int hk : n.hooks) if (hk == t) return true; return false; }
     static bool has_compact(const std::vector<Addend>& A) { for (auto& a : A) if (a.stride != 1) return true; return false; }
 
@@ -320,6 +365,12 @@ struct Planner {
                     if (accum[n.tens[t].buf]) { err = "attention over a dense (accumulating) buffer is not supported"; return false; }
                     left[t]++;
                 }
+            } else if (nd.type == 4) {
+                for (int t : {nd.sd.src, nd.sd.residual}) {
+                    if (t < 0) continue;
+                    if (accum[n.tens[t].buf]) { err = "squeeze-and-excitation over a dense (accumulating) buffer is not supported"; return false; }
+                    left[t]++;
+                }
             } else {
                 if (accum[n.tens[nd.pd.src].buf]) { err = "pooling directly from a dense (accumulating) buffer is not supported"; return false; }
                 left[nd.pd.src]++;
@@ -338,6 +389,7 @@ struct Planner {
         // ---------------- forward ----------------
         for (const Node& nd : n.nodes) {
             Launch l;
+            if (nd.type == 4) { if (!se_launches(nd, false)) return false; continue; }
             if (nd.type == 0) {
                 const i2v_conv3d_desc& c = nd.cd;
                 if (nd.gconv) { if (!gconv_launch(nd, false, c.dst)) return false; continue; }
@@ -401,7 +453,7 @@ struct Planner {
             int t = n.hooks[hk];
             bool consumed = false;
             for (const Node& nd : n.nodes) {
-                int srcs[3] = {nd.src0(), nd.type == 0 ? nd.cd.residual : nd.type == 3 ? nd.ad.phi : -1, nd.type == 3 ? nd.ad.g : -1};
+                int srcs[3] = {nd.src0(), nd.type == 3 ? nd.ad.phi : nd.residual0(), nd.type == 3 ? nd.ad.g : -1};
                 for (int s : srcs) if (s >= 0 && overlaps(n.tens[s], n.tens[t])) consumed = true;
             }
             if (consumed || accum[n.tens[t].buf]) { View g = view(t, true); hook_tmp[hk] = temp(nf(g.T) * g.C * g.H * g.W); }
@@ -490,6 +542,18 @@ struct Planner {
                     p.pointwise = ((dz.H * dz.W) % 4 == 0) ? 1 : 0;
                     emit(n.bwd, l);
                 } else if (!contribute_conv(c.src, nd, dz)) return false;
+            } else if (nd.type == 4) {
+                const i2v_se_desc& q = nd.sd;
+                // the residual's share is G itself: the alias a convolution with a residual hands on (its finalising launch adds it)
+                if (q.residual >= 0 && !contribute_alias(q.residual, dz)) return false;
+                // the node WRITES the gradient of its source and never accumulates: nothing else may contribute to it
+                const int t = q.src;
+                left[t]--;
+                if (left[t] > 0 || !pending[t].empty() || has_alias[t] || is_hook(t)) {
+                    err = "the source of a squeeze-and-excitation node (tensor " + std::to_string(t) + ") must have the node as its only consumer";
+                    return false;
+                }
+                if (!se_launches(nd, true)) return false;
             } else if (nd.type == 3) {
                 // dY = dz.  dP = dY^T g;  dg = dY P;  dS = P o (dP - rowsum(dP o P));  dtheta = phi dS^T;  dphi = theta dS
                 for (int t : {nd.ad.theta, nd.ad.phi, nd.ad.g})

@@ -1,5 +1,8 @@
 // The executor: a planned launch list on a stream, its timing instrumentation, and the read-back entries.
 #include "i2v_net.h"
+#ifndef I2V_HAVE_SE
+#include "i2v_se_host.h"         // (the host simulation's one-file build: the squeeze-and-excitation node as scalar code)
+#endif
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -125,6 +128,7 @@ static double launch_flops(const std::vector<Launch>& L, size_t li, int fb, int 
     else if (l.kind == L_CONV) flops = 2.0 * frames * l.conv.Hg * l.conv.Wg * ((double)l.conv.Cd * l.conv.K + (fuse ? (double)L[li + 1].conv.Cd * L[li + 1].conv.K : 0.0));
     else if (l.kind == L_IMGGRAD) flops = l.alg_flops_per_frame * frames;
     else if (l.kind == L_AGEMM) flops = 2.0 * clips * (double)l.ag.Cc * l.ag.M * l.ag.N;
+    else if (l.kind == L_SE_SQUEEZE || l.kind == L_SE_EXCITE || l.kind == L_SE_SCALE) flops = l.alg_flops_per_frame * frames;
     return flops;
 }
 
@@ -136,6 +140,7 @@ static int launch_timing_kind(const Launch& l, bool backward_pass) {
         case L_POOLF: case L_AVGF: case L_POOL3F: return 2;
         case L_POOLB: case L_AVGB: case L_POOL3B: return 3;
         case L_ADDMASK: case L_MEMSET: case L_SOFTMAX: return 4;
+        case L_SE_SQUEEZE: case L_SE_EXCITE: case L_SE_SCALE: return 4;        // (elementwise and reductions: with the add / mask launches)
     }
     return 4;
 }
@@ -200,7 +205,7 @@ struct ListTiming {
                 seg = timing_begin(h, kind, 0.0, s, seg);
                 if (seg) seg->count = 0;
             }
-            if (seg) { seg->flops += flops; seg->count += 1; if (conv) seg->bytes += launch_bytes(L, li, fb, fuse, frames, clips, accumulate); }
+            if (seg) { seg->flops += flops; seg->count += 1; if (conv) seg->bytes += launch_bytes(L, li, fb, fuse, frames, clips, accumulate); else seg->bytes += l.se_bytes_per_frame * frames; }
             return prev = nullptr;
         }
         TimedLaunch* const tl = prev = timing_begin(h, kind, flops, s, prev);
@@ -212,6 +217,11 @@ struct ListTiming {
             const I2VAttnGemm& q = l.ag;
             tl->Cd = q.Cc; tl->K = q.form == 1 ? q.Cc : (q.form == 2 ? q.N : q.M); tl->HWg = q.form == 2 ? q.M : q.N; tl->frames = frames; tl->pw = 10 + q.form;
             tl->bytes = 4.0 * clips * ((double)q.M * q.N + (double)q.Cc * q.M + (double)q.Cc * q.N);
+        }
+        if (tl && (l.kind == L_SE_SQUEEZE || l.kind == L_SE_EXCITE || l.kind == L_SE_SCALE)) {      // (dump fields: channels, squeezed width, positions, 20 + stage + 3 x backward)
+            tl->Cd = l.se.C; tl->K = l.se.rd; tl->HWg = l.se.HW; tl->frames = frames;
+            tl->pw = 20 + (l.kind == L_SE_SQUEEZE ? 0 : l.kind == L_SE_EXCITE ? 1 : 2) + 3 * l.se.backward;
+            tl->bytes = l.se_bytes_per_frame * frames;
         }
         return tl;
     }
@@ -310,6 +320,15 @@ static int run_list(i2v_ctx* h, Net& n, std::vector<Launch>& L, int in_frames, c
                 return fail("this build has no depthwise-convolution kernel");
 #endif
             } break;
+#ifdef I2V_HAVE_SE
+            case L_SE_SQUEEZE: { I2VSeParams p = l.se; p.N = frames; CHECK_BE(k_se_squeeze(p, s)); } break;
+            case L_SE_EXCITE: { I2VSeParams p = l.se; p.N = frames; CHECK_BE(k_se_excite(p, s)); } break;
+            case L_SE_SCALE: { I2VSeParams p = l.se; p.N = frames; CHECK_BE(k_se_scale(p, s)); } break;
+#else               // (no such kernels in this build: the same node as scalar code on the backend's memory, which is host memory here)
+            case L_SE_SQUEEZE: { I2VSeParams p = l.se; p.N = frames; if (se_host::squeeze(p)) return fail("squeeze-and-excitation: squeeze failed"); } break;
+            case L_SE_EXCITE: { I2VSeParams p = l.se; p.N = frames; if (se_host::excite(p)) return fail("squeeze-and-excitation: excite failed"); } break;
+            case L_SE_SCALE: { I2VSeParams p = l.se; p.N = frames; if (se_host::scale(p)) return fail("squeeze-and-excitation: scale failed"); } break;
+#endif
             case L_POOLF: { I2VPoolParams p = l.pool; p.N = frames; CHECK_BE(k_pool_fwd(p, s)); } break;
             // A 1 x k x k window with temporal stride st over Ts = st*To frames is the image pooling kernel on every
             // st-th frame (frame stride * st); its backward leaves the skipped frames zero.

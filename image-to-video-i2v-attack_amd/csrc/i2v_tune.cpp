@@ -42,6 +42,12 @@ void mark_fusable(Net& n) {
         }
         if (c.kind == L_MEMSET) return meet(w, rng(c.ms_ptr, 1, 0, (int64_t)c.ms_floats_per_frame * clips * std::max(1, c.T)));
         if (c.kind == L_AGEMM || c.kind == L_SOFTMAX) return true;     // attention launches address whole matrices: not analysed, such nets are not fused
+        if (c.kind == L_SE_SQUEEZE || c.kind == L_SE_EXCITE || c.kind == L_SE_SCALE) {      // every view of the node, whichever of its launches this is
+            const I2VSeParams& q = c.se;
+            const int64_t fr = clips * std::max(1, c.T), pl = (int64_t)q.C * q.HW;
+            return meet(w, rng(q.x, fr, q.x_nstride, pl)) || meet(w, rng(q.g, fr, q.g_nstride, pl)) || meet(w, rng(q.r, fr, q.r_nstride, pl)) ||
+                   meet(w, rng(q.dst, fr, q.dst_nstride, pl)) || meet(w, rng(c.se_vec, 1, 0, (int64_t)c.se_vec_floats));
+        }
         const I2VPoolParams& q = c.pool;
         const int64_t fr = clips * std::max(std::max(1, c.T), std::max(q.Ts, q.To)), pin = (int64_t)q.C * q.Hs * q.Ws, pout = (int64_t)q.C * q.Ho * q.Wo;
         return meet(w, rng(q.x, fr, q.x_nstride, pin)) || meet(w, rng(q.gx, fr, q.gx_nstride, pin)) || meet(w, rng(q.y, fr, q.y_nstride, pout)) ||
@@ -214,6 +220,16 @@ void mark_overlap(Net& n) {
             if (c.ms_gx) wr(GX); else wr(rng(c.ms_ptr, 1, 0, 4ll * (int64_t)c.ms_floats_per_frame * clips * std::max(1, c.T)));
         } else if (c.kind == L_AGEMM || c.kind == L_SOFTMAX) {
             o.barrier = true;
+        } else if (c.kind == L_SE_SQUEEZE || c.kind == L_SE_EXCITE || c.kind == L_SE_SCALE) {
+            const I2VSeParams& q = c.se;
+            const int64_t fr = clips * std::max(1, c.T), pl = 4ll * q.C * q.HW;
+            const Range vec = rng(c.se_vec, 1, 0, 4ll * (int64_t)c.se_vec_floats);     // (the node's vectors: read and written by its launches only)
+            rd(vec); wr(vec);
+            if (c.kind != L_SE_EXCITE) { rd(rng(q.x, fr, 4 * q.x_nstride, pl)); rd(rng(q.g, fr, 4 * q.g_nstride, pl)); }
+            if (c.kind == L_SE_SCALE) {
+                rd(rng(q.r, fr, 4 * q.r_nstride, pl)); wr(rng(q.dst, fr, 4 * q.dst_nstride, pl));
+                wr(rng(q.gate_out, 1, 0, 4ll * q.C * q.gate_out_stride));
+            }
         } else {
             const I2VPoolParams& q = c.pool;
             const int64_t fr = clips * std::max(std::max(1, c.T), std::max(q.Ts, q.To)), pin = 4ll * q.C * q.Hs * q.Ws, pout = 4ll * q.C * q.Ho * q.Wo;

@@ -370,6 +370,13 @@ class Net:
                     _lib.check(capi, capi.i2v_net_add_conv_grouped(h, self.id, C.byref(d), nd.groups, _hptr(w), _hptr(scale), _hptr(shift)))
                 else:
                     _lib.check(capi, capi.i2v_net_add_conv(h, self.id, C.byref(d), _hptr(w), _hptr(scale), _hptr(shift)))
+            elif nd.op == "se":
+                w1 = sd[nd.fc1 + ".weight"].float().cpu().reshape(nd.rd, nd.C).contiguous()
+                w2 = sd[nd.fc2 + ".weight"].float().cpu().reshape(nd.C, nd.rd).contiguous()
+                b1, b2 = sd[nd.fc1 + ".bias"].float().cpu().contiguous(), sd[nd.fc2 + ".bias"].float().cpu().contiguous()
+                d = _lib.SeDesc(self.ten_id[nd.src], self.ten_id[nd.dst], -1 if nd.residual is None else self.ten_id[nd.residual],
+                                nd.C, nd.rd, 1 if nd.relu else 0)
+                _lib.check(capi, capi.i2v_net_add_se(h, self.id, C.byref(d), _hptr(w1), _hptr(b1), _hptr(w2), _hptr(b2)))
             elif nd.op == "attention":
                 d = _lib.AttnDesc(self.ten_id[nd.src], self.ten_id[nd.phi], self.ten_id[nd.g], self.ten_id[nd.dst], float(nd.scale))
                 _lib.check(capi, capi.i2v_net_add_attention(h, self.id, C.byref(d)))

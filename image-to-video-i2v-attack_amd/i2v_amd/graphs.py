@@ -90,6 +90,22 @@ class AttnNode:
 
 
 @dataclass
+class SENode:
+    """Squeeze-and-excitation with the block's shortcut add and final ReLU (`i2v_net_add_se`; timm 0.5.0 `SEModule`):
+    dst = act(src * sigmoid(fc2(relu(fc1(mean_hw src)))) + residual).  `fc1` / `fc2` are state_dict prefixes of 1x1 convolutions
+    with bias: `{fc1}.weight` (rd, C, 1, 1), `{fc2}.weight` (C, rd, 1, 1)."""
+    src: int
+    dst: int
+    C: int
+    rd: int
+    fc1: str
+    fc2: str
+    relu: bool
+    residual: Optional[int] = None
+    op: str = "se"
+
+
+@dataclass
 class Graph:
     arch: str
     in_hw: Tuple[int, int]
@@ -157,6 +173,14 @@ class Graph:
         dst = self.new_tensor(cout, Ho, Wo, relu, name, dst_buf, dst_c_off, T=To)
         self.nodes.append(ConvNode(src, dst, s.C, cout, ks, ks, ss, ps, weight, bias, bn, relu, residual, None,
                                    "conv", kt, st, pt, dil_t))
+        return dst
+
+    def se(self, src, rd, prefix, relu=True, residual=None, name="") -> int:
+        """A squeeze-and-excitation node over `src` (the linear output of a convolution) with keys `{prefix}.fc1.*` / `{prefix}.fc2.*`."""
+        s = self.tensors[src]
+        assert not s.post_relu and s.T == 1 and rd >= 1
+        dst = self.new_tensor(s.C, s.H, s.W, relu, name)
+        self.nodes.append(SENode(src, dst, s.C, rd, f"{prefix}.fc1", f"{prefix}.fc2", relu, residual))
         return dst
 
     def attention(self, theta, phi, gg, name="", scale=1.0) -> int:
@@ -227,12 +251,17 @@ class Graph:
             elif nd.op == "attention":          # theta^T phi and g P^T
                 t, k = self.tensors[nd.src], self.tensors[nd.phi]
                 tot += 2 * t.C * (t.T * t.H * t.W) * (k.T * k.H * k.W)
+            elif nd.op == "se":                 # fc1 and fc2 on the squeezed vector; nothing per position
+                tot += 2 * nd.C * nd.rd
         return tot
 
     def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
         """state_dict key -> shape for every parameter the nodes reference."""
         out = {}
         for nd in self.nodes:
+            if nd.op == "se":
+                out[nd.fc1 + ".weight"], out[nd.fc1 + ".bias"] = (nd.rd, nd.C, 1, 1), (nd.rd,)
+                out[nd.fc2 + ".weight"], out[nd.fc2 + ".bias"] = (nd.C, nd.rd, 1, 1), (nd.C,)
             if nd.op != "conv":
                 continue
             out[nd.weight] = (nd.cout, nd.cin, nd.kt, nd.kh, nd.kw) if self.video else (nd.cout, nd.cin // nd.groups, nd.kh, nd.kw)
@@ -254,14 +283,21 @@ def _overlap(a: TensorSpec, b: TensorSpec) -> bool:
 # ---------------------------------------------------------------------------
 # The torchvision ResNet family: ResNet-18 ... -152, Wide ResNet, ResNeXt (v1.5: the stride sits on the 3x3)
 # ---------------------------------------------------------------------------
+def se_reduced_width(C: int) -> int:
+    """timm's `make_divisible(C / 16, 8, round_limit=0.)`: the squeezed width of `SEModule(C)` with its defaults."""
+    return max(8, int(C / 16 + 4) // 8 * 8)
+
+
 def resnet(layers=(3, 4, 23, 3), width=64, in_hw=(224, 224), arch="resnet101", block="bottleneck", groups=1,
-           width_per_group=64) -> Graph:
+           width_per_group=64, se=False) -> Graph:
     """torchvision `ResNet(block, layers, groups=, width_per_group=)` up to `layer4`.  Hook d = output of `layer{d}[-1]` (post-ReLU),
     as in `/root/reference/image_attacks.py:261-262`.
       bottleneck: conv1 1x1 inplanes -> w, conv2 3x3 / stride / `groups` w -> w, conv3 1x1 w -> 4 planes (+ shortcut, ReLU) with
                   w = int(planes * width_per_group / 64) * groups (Wide ResNet: width_per_group 128; ResNeXt: groups 32);
       basic:      conv1 3x3 / stride -> BN -> ReLU, conv2 3x3 -> BN (+ shortcut, ReLU), expansion 1.
-    `width` scales every stage (64 for the real nets; the test-size twins use less)."""
+    `width` scales every stage (64 for the real nets; the test-size twins use less).
+    `se`: timm's SE-ResNet / SE-ResNeXt -- the block's last convolution + BN stays linear and a squeeze-and-excitation node `{p}.se`
+    (squeezed width `se_reduced_width`) scales it, adds the shortcut and applies the ReLU; the hook is that node's output."""
     assert block in ("bottleneck", "basic")
     expansion = 4 if block == "bottleneck" else 1
     g = Graph(arch, in_hw)
@@ -289,7 +325,13 @@ def resnet(layers=(3, 4, 23, 3), width=64, in_hw=(224, 224), arch="resnet101", b
                              bn=f"{p}.downsample.1", relu=False, name=f"{p}.downsample")
             else:
                 idt = x
-            if block == "bottleneck":
+            if se:
+                if block == "bottleneck":
+                    a = g.conv(a, planes * 4, 1, 1, 0, f"{p}.conv3.weight", bn=f"{p}.bn3", relu=False, name=f"{p}.conv3")
+                else:
+                    a = g.conv(a, planes, 3, 1, 1, f"{p}.conv2.weight", bn=f"{p}.bn2", relu=False, name=f"{p}.conv2")
+                x = g.se(a, se_reduced_width(planes * expansion), f"{p}.se", relu=True, residual=idt, name=f"{p}.out")
+            elif block == "bottleneck":
                 x = g.conv(a, planes * 4, 1, 1, 0, f"{p}.conv3.weight", bn=f"{p}.bn3", relu=True, residual=idt, name=f"{p}.out")
             else:
                 x = g.conv(a, planes, 3, 1, 1, f"{p}.conv2.weight", bn=f"{p}.bn2", relu=True, residual=idt, name=f"{p}.out")
@@ -308,6 +350,41 @@ RESNET_FAMILY: Dict[str, Tuple[str, Tuple[int, ...], int, int]] = {
     "resnext50_32x4d": ("bottleneck", (3, 4, 6, 3), 32, 4),
     "resnext101_32x8d": ("bottleneck", (3, 4, 23, 3), 32, 8),
 }
+
+
+#: timm's SE-ResNets and SE-ResNeXts `build` serves through `resnet(se=True)`: name -> (block, layers, groups, width_per_group).  `arch`
+#: and the checkpoint file are the timm name; the keys are timm's (`layer{i}.{j}.se.fc1.weight` ...).
+SERESNET_FAMILY: Dict[str, Tuple[str, Tuple[int, ...], int, int]] = {
+    "seresnet18": ("basic", (2, 2, 2, 2), 1, 64),
+    "seresnet34": ("basic", (3, 4, 6, 3), 1, 64),
+    "seresnet50": ("bottleneck", (3, 4, 6, 3), 1, 64),
+    "seresnet101": ("bottleneck", (3, 4, 23, 3), 1, 64),
+    "seresnet152": ("bottleneck", (3, 8, 36, 3), 1, 64),
+    "seresnext50_32x4d": ("bottleneck", (3, 4, 6, 3), 32, 4),
+    "seresnext101_32x4d": ("bottleneck", (3, 4, 23, 3), 32, 4),
+    "seresnext101_32x8d": ("bottleneck", (3, 4, 23, 3), 32, 8),
+}
+#: names of the line that are not served, each with what it still needs (matched by prefix, the longest first)
+SE_NOT_SERVED = (("legacy_senet154", "legacy_senet154 needs the grouped 3x3 convolution at group width 8 with a different (three-convolution) stem"),
+                 ("legacy_se", "the legacy_se* nets are the original SENet port, with a block, stem and key layout of their own that is not restated here"),
+                 ("senet", "senet154 needs the grouped 3x3 convolution at group width 8 with a different (three-convolution) stem"))
+
+
+def is_seresnet_name(model_name: str) -> bool:
+    return model_name in SERESNET_FAMILY or model_name.startswith(("seresne", "legacy_se", "senet"))
+
+
+def seresnet_named(model_name: str, in_hw=(224, 224)) -> Graph:
+    if model_name in SERESNET_FAMILY:
+        block, layers, groups, wpg = SERESNET_FAMILY[model_name]
+        return resnet(layers, 64, in_hw, model_name, block, groups, wpg, se=True)
+    why = ""
+    if model_name.startswith("seresne") and model_name.split("_")[0].endswith(("d", "t")) and model_name.split("_")[0][-2].isdigit():
+        why = ": the d / t deep-stem variants need the three-convolution stem and the average-pool downsample"
+    for prefix, reason in SE_NOT_SERVED:
+        if not why and model_name.startswith(prefix):
+            why = ": " + reason
+    raise ValueError(f"{model_name!r} is not served{why}; the squeeze-and-excitation names served: " + ", ".join(SERESNET_FAMILY))
 
 
 # ---------------------------------------------------------------------------
@@ -1158,6 +1235,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
     if model_name in RESNET_FAMILY:     # extension: the other torchvision ResNets, Wide ResNet and ResNeXt (grouped conv2)
         block, layers, groups, wpg = RESNET_FAMILY[model_name]
         return resnet(layers, 64, in_hw, model_name, block, groups, wpg)
+    if is_seresnet_name(model_name):    # extension: timm's SE-ResNet / SE-ResNeXt family (the squeeze-and-excitation node)
+        return seresnet_named(model_name, in_hw)
     if is_mnasnet_name(model_name):     # extension: torchvision's MNASNet family (depthwise 3x3 / 5x5 convolutions)
         return mnasnet_named(model_name, in_hw)
     for prefix, why in MOBILE_NOT_SERVED:
@@ -1194,6 +1273,10 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return resnet((2, 1, 2, 1), 8, in_hw, "resnext_tiny", "bottleneck", 4, 32)
     if model_name == "resnet_basic_tiny":
         return resnet((2, 1, 2, 1), 8, in_hw, "resnet_basic_tiny", "basic")
+    if model_name == "seresnet_tiny":       # resnet_tiny with an SE node per block: C 32 .. 256, rd 8 / 16; planes 16 x 16 .. 2 x 2
+        return resnet((2, 1, 2, 1), 8, in_hw, "seresnet_tiny", se=True)
+    if model_name == "seresnext_tiny":      # resnext_tiny with an SE node per block
+        return resnet((2, 1, 2, 1), 8, in_hw, "seresnext_tiny", "bottleneck", 4, 32, se=True)
     if model_name == "mnasnet_tiny":        # both filter sizes, both strides, identity blocks, 5x5 filters on 4x4 and 2x2 planes; a last plane of 2 x 2
         return mnasnet(1.0, in_hw, "mnasnet_tiny", depths=(8, 8, 8, 8, 16, 16, 16, 24),
                        stacks=((3, 2, 3, 2), (5, 2, 3, 2), (5, 2, 6, 1), (3, 1, 6, 2), (5, 2, 6, 2), (3, 1, 6, 1)))

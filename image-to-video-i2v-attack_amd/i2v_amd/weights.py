@@ -85,12 +85,23 @@ def check_swin_buffers(spec: SwinSpec, sd, where: str) -> None:
 
 
 def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for trained weights, one generator per key.  Convolutions: Kaiming-normal(fan_out); BatchNorms: randomised
+    statistics.  Squeeze-and-excitation nodes (`{p}.se.fc1.*`, `{p}.se.fc2.*`) are drawn so that the gates are neither saturated nor
+    flat: fc1.weight ~ N(0, 4 / C) (the squeezed pre-activations are O(1) for O(1/2) channel means), fc1.bias ~ 0.1 N(0, 1),
+    fc2.weight ~ N(0, 1 / rd), and fc2.bias a random permutation of C points evenly spaced over [-2, 2]: the bias alone spreads the
+    gates over sigmoid(-2) .. sigmoid(2) = 0.12 .. 0.88 whatever the input, and the fc2 term moves each gate with the frame."""
     if isinstance(graph, VitSpec):
         return _vit_synthetic(graph, seed)
     if isinstance(graph, SwinSpec):
         return _swin_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
+        if nd.op == "se":
+            k1, k2 = nd.fc1 + ".weight", nd.fc2 + ".weight"
+            sd[k1] = torch.randn(nd.rd, nd.C, 1, 1, generator=_gen(seed, k1)) * (2.0 / nd.C ** 0.5)
+            sd[nd.fc1 + ".bias"] = torch.randn(nd.rd, generator=_gen(seed, nd.fc1 + ".bias")) * 0.1
+            sd[k2] = torch.randn(nd.C, nd.rd, 1, 1, generator=_gen(seed, k2)) * (1.0 / nd.rd ** 0.5)
+            sd[nd.fc2 + ".bias"] = torch.linspace(-2.0, 2.0, nd.C)[torch.randperm(nd.C, generator=_gen(seed, nd.fc2 + ".bias"))].contiguous()
         if nd.op != "conv":
             continue
         fan_out = nd.cout * nd.kt * nd.kh * nd.kw

@@ -43,7 +43,8 @@ def arg_parse(argv=None, ucf101=False):
                         help="resnet, densenet, squeezenet, vgg, alexnet (added: resnet50, densenet121, densenet161, and timm's plain "
                              "ViT / DeiT names at 224 x 224: " + ", ".join(graphs.VIT_MODELS) + "; and timm's Swin names at 224 x 224: "
                              + ", ".join(graphs.SWIN_MODELS) + "; and torchvision's other ResNets, Wide ResNets and ResNeXts: "
-                             + ", ".join(graphs.RESNET_FAMILY) + "; and torchvision's MNASNets: " + ", ".join(graphs.MNASNET_MODELS) + ")")
+                             + ", ".join(graphs.RESNET_FAMILY) + "; and torchvision's MNASNets: " + ", ".join(graphs.MNASNET_MODELS)
+                             + "; and timm's SE-ResNets / SE-ResNeXts: " + ", ".join(graphs.SERESNET_FAMILY) + ")")
     # additions (not in the reference)
     parser.add_argument("--anno", type=str, default=os.environ.get("I2V_ANNO", ""),
                         help="sample list csv `path,gt_label,clip_index` (the reference's kinetics400_attack_samples.csv, utils.py:29); without it 400 synthetic names with labels 0..399 are used")

@@ -136,6 +136,22 @@ typedef struct {
     float scale;
 } i2v_attn_desc;
 int i2v_net_add_attention(i2v_handle h, int net, const i2v_attn_desc* d);
+/* Squeeze-and-excitation node (timm 0.5.0 `SEModule` where `Bottleneck` / `BasicBlock` put it: behind bn3 / bn2, in front of the
+ * shortcut add and the final ReLU).  Per frame n and channel c over the plane's HW positions:
+ *   m[c] = mean_p src[c][p];  h[j] = relu(b1[j] + sum_c W1[j][c] m[c]);  s[c] = sigmoid(b2[c] + sum_j W2[c][j] h[j]);
+ *   dst[c][p] = act(src[c][p] * s[c] + residual[c][p])                act = ReLU (`relu` != 0) or the identity; residual optional (-1)
+ * W1: host [rd][C] (fc1, a 1x1 convolution with bias b1 [rd]), W2: host [C][rd] (fc2, bias b2 [C]).  `src` is the LINEAR output of the
+ * block's last convolution and the node is its only consumer (checked when the net is planned; the refusal names the tensor): the
+ * node writes src's gradient, it never accumulates into it.  The residual's gradient is dst's, passed on as the same alias a
+ * convolution with a residual passes on.  m, h and s stay in the arena for the input-gradient pass ((2 C + rd) floats per frame).
+ * Refused (i2v_last_error): C not the channel count of src and dst, rd < 1, src and dst planes that differ, a residual of another
+ * shape, a src that is the output of a ReLU, and tensors with more than one frame per clip (video networks: not served yet).
+ * Three kernel launches per pass ("se_launches" of i2v_backend_stat): squeeze, excite, scale. */
+typedef struct {
+    int32_t src, dst, residual;
+    int32_t C, rd, relu;
+} i2v_se_desc;
+int i2v_net_add_se(i2v_handle h, int net, const i2v_se_desc* d, const float* W1, const float* b1, const float* W2, const float* b2);
 /* Frames per clip of a tensor (1 for image networks). */
 int i2v_net_tensor_frames(i2v_handle h, int net, int tensor, int* T);
 /* Freeze the graph: pack weights for forward and input-gradient, plan both passes for up to
