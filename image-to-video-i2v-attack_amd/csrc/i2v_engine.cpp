@@ -491,4 +491,9 @@ extern "C" size_t i2v_net_workspace_bytes(i2v_handle h, int net) {
 #include "i2v_tune.cpp"
 #include "i2v_run.cpp"
 #include "i2v_loop_api.cpp"
+// ... and the ConvNeXt planner on the scalar restatements of the transformer launches it uses (i2v_xf_host.h), so that the planner
+// tests can run it without a GPU.  i2v_xf.h's file-local `fail` would be ambiguous with eng::fail under this unit's using-directives.
+#define fail xf_fail
+#include "i2v_convnext.cpp"
+#undef fail
 #endif

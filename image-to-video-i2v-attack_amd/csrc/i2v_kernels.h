@@ -102,6 +102,11 @@ int k_se_plan(I2VSeParams* p);
 int k_se_squeeze(const I2VSeParams& p, i2v_stream_t s);
 int k_se_excite(const I2VSeParams& p, i2v_stream_t s);
 int k_se_scale(const I2VSeParams& p, i2v_stream_t s);
+// Token-major depthwise 7 x 7 convolution of the ConvNeXt blocks (I2VCnDwParams; i2v_convnext.hip -- product backend only, under
+// -DI2V_HAVE_CONVNEXT; without it the callers run the launch as scalar host code, i2v_convnext_host.h).  k_convnext_dw_plan fills the
+// division fields; 0 ok, 1 the shape does not fit.
+int k_convnext_dw_plan(I2VCnDwParams* p);
+int k_convnext_dw(const I2VCnDwParams& p, i2v_stream_t s);
 int k_pool_fwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool_bwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool3d_fwd(const I2VPoolParams& p, i2v_stream_t s);  // video max pooling (kt/stride_t/pad_t honoured)

@@ -1,5 +1,8 @@
 // The loop kernels' C entries: argument checks in front of one backend call each.  None of them touches a net.
 #include "i2v_net.h"
+#ifndef I2V_HAVE_CONVNEXT
+#include "i2v_convnext_host.h"   // (the host simulation's one-file build: the token-major depthwise launch as scalar code)
+#endif
 
 #include <math.h>
 #include <string.h>
@@ -288,4 +291,21 @@ extern "C" int i2v_aens_reduce_f32(const float* cos, const float* coeffs, int L,
                                    float* weighted, void* stream) {
     BAD_ARG_IF(!cos || !coeffs || !feat_sum || !weighted || L <= 0 || frames <= 0);
     RETURN_BE(k_aens_reduce(cos, coeffs, L, frames, feat_sum, weighted, stream));
+}
+
+// The ConvNeXt block's token-major depthwise 7 x 7 launch on its own (include/i2v_convnext.h): the device kernel where the library has
+// one, the scalar restatement of the same operations in the same order elsewhere.
+extern "C" int i2v_convnext_dw_f32(const float* x, const float* filter, const float* bias, const float* add, float* y, int frames, int H,
+                                   int W, int C, void* stream) {
+    BAD_ARG_IF(!x || !filter || !y || frames <= 0 || H <= 0 || W <= 0 || C <= 0);
+    I2VCnDwParams p; memset(&p, 0, sizeof p);
+    p.x = x; p.w = filter; p.b = bias; p.add = add; p.y = y; p.N = frames; p.H = H; p.W = W; p.C = C;
+#ifdef I2V_HAVE_CONVNEXT
+    if (k_convnext_dw_plan(&p) != 0) return fail("i2v_convnext_dw_f32: the shape does not fit the launch");
+    RETURN_BE(k_convnext_dw(p, stream));
+#else
+    (void)stream;
+    if (convnext_host::plan(&p) != 0 || convnext_host::dw(p) != 0) return fail("i2v_convnext_dw_f32: the shape does not fit the launch");
+    return 0;
+#endif
 }

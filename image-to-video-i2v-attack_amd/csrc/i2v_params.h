@@ -195,6 +195,29 @@ struct I2VSeParams {
     uint32_t dv_hw_m, dv_hw_s;                   // exact division by HW (k_se_plan)
 };
 
+// Depthwise 7 x 7 convolution on token-major tensors (k_convnext_dw, i2v_convnext.hip; the same arithmetic as scalar host code in
+// i2v_convnext_host.h) -- the ConvNeXt block's first layer, forward and input gradient:
+//   y[n][h][w][c] = (sum_{a,b} w[a * 7 + b][c] * x[n][h + a - 3][w + b - 3][c]) + b[c] + add[n][h][w][c]       (zero outside the plane)
+// x, y and add are (N, H, W, C) with channels contiguous; the filter is [49][C], one coalesced row per tap; `b` and `add` are optional.
+// The input gradient is the same launch on the mirrored filter (w'[t] = w[48 - t]) with the output's gradient as x and no bias.
+// Order: each output is ONE fp32 chain acc = fma(w, x, acc) from 0.f over the 49 taps in row-major order (a outer, b inner; a tap
+// outside the plane contributes fma(w, 0.f, acc)), then + b[c], then + add.  It depends on nothing but (H, W).
+struct I2VCnDwParams {
+    const float* x;
+    const float* w;                      // [49][C]
+    const float* b;                      // [C] or null
+    const float* add;                    // (N, H, W, C) or null; may be y itself
+    float* y;
+    int32_t N, H, W, C;
+    // filled by k_convnext_dw_plan
+    int32_t runs;                        // runs of I2V_CNDW_RUN output positions per row: ceil(W / I2V_CNDW_RUN)
+    int32_t vec;                         // 4: a lane owns 4 channels (16-byte accesses; C % 4 == 0, 16-byte aligned arrays); 1: one channel
+    int32_t lanes;                       // channel groups per position: C / vec
+    uint32_t dv_l_m, dv_l_s;             // exact division by lanes
+    uint32_t dv_r_m, dv_r_s;             // exact division by runs
+};
+enum { I2V_CNDW_RUN = 8 };
+
 struct I2VPoolParams {
     const float* x;    int64_t x_nstride;    int32_t C, Hs, Ws;
     float* y;          int64_t y_nstride;    int32_t Ho, Wo;       // fwd: output; bwd: upstream grad

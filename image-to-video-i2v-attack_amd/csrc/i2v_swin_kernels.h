@@ -1,7 +1,11 @@
 // Internal interface of the Swin kernels (i2v_swin.hip) to their planner (i2v_swin.cpp).  The linear layers, the LayerNorm pair and the
 // patchify kernel are the ViT ones (i2v_vit_kernels.h).
 #pragma once
+#ifdef __HIP__
 #include <hip/hip_runtime.h>
+#else
+#include "i2v_hip_stub.h"     // (no HIP: the host simulation's build)
+#endif
 #include <stdint.h>
 
 // Window attention core of one block over qkv (F, H*W, 3*heads*dh), token-major: the grid rolled by (-shift, -shift), cut into ws x ws

@@ -1,7 +1,11 @@
 // Internal interface of the ViT kernels (i2v_vit.hip) to their planner (i2v_vit.cpp).  Both are HIP translation units of the product
 // library only: the CNN planner (i2v_engine.cpp) and its host simulation know nothing of them.
 #pragma once
+#ifdef __HIP__
 #include <hip/hip_runtime.h>
+#else
+#include "i2v_hip_stub.h"     // (no HIP: the host simulation's build)
+#endif
 #include <stdint.h>
 
 enum { VIT_EPI_PLAIN = 0, VIT_EPI_GELU = 1, VIT_EPI_GELU_BWD = 2 };
@@ -10,7 +14,8 @@ enum { VIT_EPI_PLAIN = 0, VIT_EPI_GELU = 1, VIT_EPI_GELU_BWD = 2 };
 //   VIT_EPI_GELU      C = that value (the pre-activation), C2 = gelu(C)
 //   VIT_EPI_GELU_BWD  C = that value * gelu'(H[b](m, n))
 // Batch b = outer * nb_in + inner; operand X's element is X + outer * x_bo + inner * x_bi + row * stride + col * stride.  A must be
-// contiguous along M or K, B along K or N; C, R, C2 and H share C's strides and are contiguous along N.  R may alias C.
+// contiguous along M or K, B along K or N; C, R, C2 and H share C's strides and are contiguous along N.  R may alias C, element for element: the thread that stores C[m][n] is the only one that reads R[m][n], it reads it
+// after the K loop and before the store, and K is never split across blocks -- i2v_convnext.cpp relies on it (x = x + fc2(...) in place).
 struct VitGemm {
     const float* A; int64_t a_bo, a_bi, a_sm, a_sk;
     const float* B; int64_t b_bo, b_bi, b_sk, b_sn;

@@ -2,7 +2,11 @@
 // net's device memory, the weight upload, the hook list with its gradient views, the create wrapper, and the pre-norm block -- seven
 // launches forward, seven backward, with the family's attention step passed in as a callable.  Internal: each planner includes it once.
 #pragma once
+#ifdef __HIP__
 #include <hip/hip_runtime.h>
+#else
+#include "i2v_xf_host.h"      // (no HIP: the host simulation's build)
+#endif
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -26,7 +30,9 @@ int fail(const char* fmt, ...) {
 #define VCHK(expr) do { if ((expr) != 0) return 1; } while (0)
 #define HCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 
-// y (M, N) = x (M, K) W^T (+ bias) (+ residual), W (N, K)
+// y (M, N) = x (M, K) W^T (+ bias) (+ residual), W (N, K).  `residual` may BE y (the ConvNeXt blocks run in place): vit_gemm reads
+// R[m][n] and writes C[m][n] in the one thread that owns the element, after its whole K loop, and never splits K across blocks
+// (i2v_vit_kernels.h states it); x must not overlap y.
 int linear(const float* x, int M, int K, const float* W, const float* bias, int N, const float* residual, float* y, float* gelu_out,
            hipStream_t s) {
     VitGemm g{};

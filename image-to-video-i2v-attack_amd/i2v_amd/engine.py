@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import Graph, SwinSpec, VitSpec
+from .graphs import ConvNextSpec, Graph, SwinSpec, VitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -94,6 +94,21 @@ class Engine:
     def build_swin_net(self, spec: SwinSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "SwinNet":
         """A Swin surrogate (`include/i2v_swin.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
         return self._build(SwinNet, spec, state_dict, list(hook_stages), max_frames)
+
+    def build_convnext_net(self, spec: ConvNextSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "ConvNextNet":
+        """A ConvNeXt surrogate (`include/i2v_convnext.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
+        return self._build(ConvNextNet, spec, state_dict, list(hook_stages), max_frames)
+
+    def convnext_dw(self, x: torch.Tensor, filt: torch.Tensor, bias=None, add=None) -> torch.Tensor:
+        """The ConvNeXt block's depthwise 7 x 7 launch on its own (`i2v_convnext_dw_f32`): x (frames, H, W, C) token-major, filt (49, C),
+        optional bias (C) and addend (frames, H, W, C) -> (frames, H, W, C)."""
+        n, H, W, Cn = x.shape
+        assert tuple(filt.shape) == (49, Cn)
+        y = torch.empty_like(x)
+        _lib.check(self.capi, self.capi.i2v_convnext_dw_f32(_ptr(x, self), _ptr(filt, self), _ptr(bias, self) if bias is not None else None,
+                                                            _ptr(add, self) if add is not None else None, _ptr(y, self), n, H, W, Cn,
+                                                            self.stream()))
+        return y
 
     # ---- measurement ----
     KINDS = ("conv_igemm_fwd", "conv_igemm_imggrad", "pool_fwd", "pool_bwd", "addmask", "conv_igemm_dgrad")
@@ -681,6 +696,30 @@ class SwinNet(TokenNet):
         hs = (C.c_int32 * len(hook_stages))(*hook_stages)
         h = C.c_void_p()
         _lib.check(capi, capi.i2v_swin_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hs, len(hook_stages), max_frames, C.byref(h)))
+        return h
+
+    def hook_shape(self, i):
+        st = self.hook_tensors[i]
+        return (self.graph.tokens(st), self.graph.width(st), 1)
+
+
+class ConvNextNet(TokenNet):
+    """A ConvNeXt surrogate: a hook is the stream after the last block of a stage, before the next stage's downsample, (plane^2 * width)
+    floats per frame, token-major."""
+    _api = "convnext"
+
+    def _create(self, spec: ConvNextSpec, sd, hook_stages, max_frames):
+        eng, capi = self.eng, self.eng.capi
+        ns = min(max(hook_stages) + 1, spec.stages)      # (a hook outside the stages is the library's to refuse)
+        # native order (include/i2v_convnext.h): filters transposed, downsamples as Linears, gamma folded into fc2; kept alive until the upload
+        w = spec.native_arrays(sd, ns)
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
+        pad = lambda v: (C.c_int32 * 4)(*(list(v) + [0] * (4 - len(v))))      # noqa: E731
+        cfg = _lib.ConvNextConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.stages, pad(spec.depths), spec.ln_eps)
+        hs = (C.c_int32 * len(hook_stages))(*hook_stages)
+        h = C.c_void_p()
+        _lib.check(capi, capi.i2v_convnext_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hs, len(hook_stages), max_frames,
+                                                  C.byref(h)))
         return h
 
     def hook_shape(self, i):

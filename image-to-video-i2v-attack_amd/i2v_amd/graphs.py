@@ -1222,6 +1222,191 @@ def swin_tiny(in_hw=(64, 64)) -> SwinSpec:
 
 
 # ---------------------------------------------------------------------------
+# the ConvNeXt surrogates: convolutional, but planned on the transformer stack (include/i2v_convnext.h)
+# ---------------------------------------------------------------------------
+#: timm's 224 x 224, ImageNet-1k ConvNeXt models (stem 4 x 4 / 4, 7 x 7 depthwise blocks, MLP ratio 4): name -> (C, depths).
+CONVNEXT_MODELS: Dict[str, Tuple[int, Tuple[int, ...]]] = {
+    "convnext_tiny": (96, (3, 3, 9, 3)),
+    "convnext_small": (96, (3, 3, 27, 3)),
+    "convnext_base": (128, (3, 3, 27, 3)),
+    "convnext_large": (192, (3, 3, 27, 3)),
+}
+
+
+@dataclass
+class ConvNextSpec:
+    """timm `ConvNeXt`: the stem is a patch x patch convolution with stride patch and bias, then a LayerNorm over
+    channels; stage i is `depths[i]` blocks at width dim * 2^i on a plane of (img / patch) / 2^i squared, with a downsample (LayerNorm
+    over channels, then a 2 x 2 / 2 convolution with bias) in front of every stage but the first.  A block is
+    x + gamma * fc2(GELU(fc1(LN(dwconv7x7(x))))) with LN, fc1, GELU and fc2 per position over channels, LayerNorm eps `ln_eps`, exact
+    GELU, MLP ratio 4.  `hooks`: depth d (1..stages) -> zero-based stage d - 1, whose last block's OUTPUT, before the next stage's
+    downsample, is the hooked feature: plane_i^2 * width_i floats per frame, handed over token-major (row, column, channel)."""
+    arch: str
+    img: int
+    patch: int = 4
+    in_chans: int = 3
+    dim: int = 96
+    depths: Tuple[int, ...] = (3, 3, 9, 3)
+    ln_eps: float = 1e-6
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        self.depths = tuple(self.depths)
+        if not 1 <= len(self.depths) <= 4 or min(self.depths) < 1:
+            raise ValueError(f"{self.arch}: depths {self.depths} must name 1..4 stages of at least one block")
+        if self.dim % 4 or self.patch % 4:
+            raise ValueError(f"{self.arch}: width {self.dim} and stem patch {self.patch} must be multiples of 4")
+        if self.img % (self.patch << (self.stages - 1)):
+            raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame does not halve {self.stages - 1} times behind a "
+                             f"{self.patch} x {self.patch} stem")
+        if not self.hooks:
+            self.hooks = {d: d - 1 for d in range(1, self.stages + 1)}
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def stages(self) -> int:
+        return len(self.depths)
+
+    def grid(self, i: int) -> int:
+        return (self.img // self.patch) >> i
+
+    def width(self, i: int) -> int:
+        return self.dim << i
+
+    def tokens(self, i: int) -> int:
+        return self.grid(i) ** 2
+
+    def hook_dim(self, i: int) -> int:
+        """Floats per frame of the feature hooked at stage i."""
+        return self.tokens(i) * self.width(i)
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based stage whose last block depth `depth` hooks (`whole_module` changes nothing: a stage is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def stem_keys(self) -> List[str]:
+        return ["stem.0.weight", "stem.0.bias", "stem.1.weight", "stem.1.bias"]
+
+    def downsample_keys(self, i: int) -> List[str]:
+        p = f"stages.{i}.downsample."
+        return [p + "0.weight", p + "0.bias", p + "1.weight", p + "1.bias"]
+
+    def block_keys(self, i: int, j: int) -> List[str]:
+        p = f"stages.{i}.blocks.{j}."
+        return [p + k for k in ("conv_dw.weight", "conv_dw.bias", "norm.weight", "norm.bias", "mlp.fc1.weight", "mlp.fc1.bias",
+                                "mlp.fc2.weight", "mlp.fc2.bias", "gamma")]
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block (`norm_pre.*`, `head.*` are not used below a hook)."""
+        C = self.dim
+        out = dict(zip(self.stem_keys(), [(C, self.in_chans, self.patch, self.patch), (C,), (C,), (C,)]))
+        for i in range(self.stages):
+            D = self.width(i)
+            if i > 0:
+                out.update(zip(self.downsample_keys(i), [(D // 2,), (D // 2,), (D, D // 2, 2, 2), (D,)]))
+            for j in range(self.depths[i]):
+                out.update(zip(self.block_keys(i, j), [(D, 1, 7, 7), (D,), (D,), (D,), (4 * D, D), (4 * D,), (D, 4 * D), (D,), (D,)]))
+        return out
+
+    @staticmethod
+    def downsample_linear(w: "torch.Tensor") -> "torch.Tensor":
+        """The (2C, C, 2, 2) weight of a downsample's 2 x 2 / 2 convolution as the Linear (2C, 4C) behind the 2 x 2 gather of the
+        transformer stack, whose quarter q of a gathered row is the position at (row, column) offset (q & 1, q >> 1) of its cell:
+        L[o][q * C + c] = w[o][c][q & 1][q >> 1], i.e. the axes (o, c, dy, dx) reordered to (o, dx, dy, c)."""
+        return w.permute(0, 3, 2, 1).reshape(w.shape[0], -1).contiguous()
+
+    def native_arrays(self, sd, n_stages: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_convnext_create` takes for the first `n_stages` stages, from a timm-layout state dict, as float32 host
+        tensors: the depthwise filters transposed to (49, C), the downsample convolutions as Linears (`downsample_linear`), and `gamma`
+        folded into fc2 -- fc2.weight[o, :] * gamma[o], fc2.bias[o] * gamma[o] --, so that the layer scale costs nothing at run time."""
+        f = lambda k: sd[k].detach().float().cpu()      # noqa: E731
+        out = [f(k).contiguous() for k in self.stem_keys()]
+        for i in range(n_stages):
+            if i > 0:
+                k = self.downsample_keys(i)
+                out += [f(k[0]).contiguous(), f(k[1]).contiguous(), self.downsample_linear(f(k[2])), f(k[3]).contiguous()]
+            for j in range(self.depths[i]):
+                k = self.block_keys(i, j)
+                D, gamma = self.width(i), f(k[8])
+                out += [f(k[0]).reshape(D, 49).t().contiguous()] + [f(x).contiguous() for x in k[1:6]]
+                out += [(f(k[6]) * gamma[:, None]).contiguous(), (f(k[7]) * gamma).contiguous()]
+        return out
+
+    def macs_per_frame(self) -> int:
+        total = self.tokens(0) * self.dim * self.in_chans * self.patch ** 2
+        for i in range(self.stages):
+            T, D = self.tokens(i), self.width(i)
+            total += self.depths[i] * (T * D * 49 + T * D * 8 * D)
+            if i > 0:
+                total += T * D * 2 * D
+        return total
+
+    def workspace_bytes(self, hook_stages: Sequence[int], frames: int) -> int:
+        """Device bytes `i2v_convnext_create` plans for these hooked stages and `frames` frames (the formula of csrc/i2v_convnext.cpp:
+        weights of the stages run, each block's filter twice (the mirrored copy); patches, stem output and its LayerNorm statistics;
+        per stage one stream; per block the depthwise output, the fc1 pre-activation and two statistics per position; per downsample
+        two statistics per position of the stage before; the shared scratch; one gradient view per hook)."""
+        F, ns = frames, max(hook_stages) + 1
+        KP, T0, D0 = self.in_chans * self.patch ** 2, self.tokens(0), self.dim
+        weights = D0 * KP + 3 * D0
+        acts = F * T0 * (KP + D0 + 2)
+        for i in range(ns):
+            D, FT = self.width(i), F * self.tokens(i)
+            if i > 0:
+                weights += 2 * D + 2 * D * D
+                acts += 8 * FT
+            weights += self.depths[i] * (8 * D * D + 49 * D + 8 * D)
+            acts += self.depths[i] * (49 * D + 5 * FT * D + 2 * FT) + FT * D
+        acts += 7 * F * T0 * D0
+        acts += sum(F * self.hook_dim(s) for s in hook_stages)
+        return 4 * (weights + acts)
+
+
+def is_convnext_name(model_name: str) -> bool:
+    """A name of timm's ConvNeXt vocabulary, served (`CONVNEXT_MODELS`) or not: `graphs.build` routes these to `convnext_named`, which
+    refuses the ones that are not offered with a message that lists the served names."""
+    return model_name in CONVNEXT_MODELS or model_name.startswith("convnext")
+
+
+def convnext_named(model_name: str, in_hw=(224, 224)) -> ConvNextSpec:
+    """Any row of `CONVNEXT_MODELS`, at 224 x 224 only.  Refused, each with the reason where there is one: ConvNeXt-V2 (its blocks carry
+    a global response normalisation), the 384 x 384 fine-tunes, the in22k / in22ft1k checkpoints, and names outside the table (xlarge,
+    nano, atto, ...)."""
+    served = "served: " + ", ".join(CONVNEXT_MODELS)
+    if model_name not in CONVNEXT_MODELS:
+        if model_name.startswith("convnextv2"):
+            why = "ConvNeXt-V2 blocks carry a global response normalisation (GRN) that is not built"
+        elif "384" in model_name:
+            why = "the 384 x 384 fine-tunes are not offered (224 x 224 only)"
+        elif "in22ft1k" in model_name:
+            why = "the in22ft1k checkpoints are not offered (the ImageNet-1k models only)"
+        elif "in22k" in model_name:
+            why = "the in22k checkpoints (21841-class heads) are not offered"
+        else:
+            why = "not a model of this table"
+        raise ValueError(f"ConvNeXt surrogate {model_name!r}: {why}; {served}")
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]})")
+    dim, depths = CONVNEXT_MODELS[model_name]
+    return ConvNextSpec(model_name, 224, 4, 3, dim, depths)
+
+
+def convnext_tiny_twin(in_hw=(64, 64)) -> ConvNextSpec:
+    """The same topology at test size ("convnext_test": not timm's `convnext_tiny`): widths 8 / 16 / 32 / 64, depths (2, 1, 2, 1).  A
+    64 x 64 frame gives planes of 16, 8, 4 and 2 squared: the 7 x 7 filter is larger than the last two.  Square frames of a multiple of
+    32 pixels."""
+    if in_hw[0] != in_hw[1] or in_hw[0] % 32:
+        raise ValueError(f"the test-size ConvNeXt takes square frames of a multiple of 32 pixels (got {tuple(in_hw)})")
+    return ConvNextSpec("convnext_test", int(in_hw[0]), 4, 3, 8, (2, 1, 2, 1))
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -1256,6 +1441,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return vit_named(model_name, in_hw)
     if is_swin_name(model_name):        # extension: timm's Swin Transformer family (hierarchical, windowed attention)
         return swin_named(model_name, in_hw)
+    if is_convnext_name(model_name):    # extension: timm's ConvNeXt family (7 x 7 depthwise blocks, planned on the transformer stack)
+        return convnext_named(model_name, in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -1294,4 +1481,6 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return vit_tiny(in_hw, n_prefix, patch)
     if model_name in SWIN_MODELS:
         return swin_tiny(in_hw)
+    if model_name in CONVNEXT_MODELS:
+        return convnext_tiny_twin(in_hw)
     return build(model_name, in_hw)

@@ -181,6 +181,26 @@ _SWIN_PROTOS = {
 SWIN_EXPORTS = tuple(_SWIN_PROTOS)
 
 
+class ConvNextConfig(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("img", "patch", "in_chans", "dim", "stages")] + [("depths", C.c_int32 * 4), ("ln_eps", C.c_float)])
+
+
+# The ConvNeXt surrogates (`include/i2v_convnext.h`): a header of its own, bound on the product library only -- except the depthwise
+# launch on its own, `i2v_convnext_dw_f32`, which the host simulation exports as well (the same operations as scalar host code).
+_CONVNEXT_PROTOS = {
+    "i2v_convnext_create": ([_I, C.POINTER(ConvNextConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    "i2v_convnext_destroy": ([_P], _I),
+    "i2v_convnext_workspace_bytes": ([_P], _L),
+    "i2v_convnext_forward": ([_P, _P, _I, _P], _I),
+    "i2v_convnext_backward": ([_P, _P, _I, _P], _I),
+    "i2v_convnext_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+    "i2v_convnext_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    "i2v_convnext_dw_f32": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
+}
+CONVNEXT_EXPORTS = tuple(_CONVNEXT_PROTOS)
+CONVNEXT_NODE_PROTOS = {"i2v_convnext_dw_f32": _CONVNEXT_PROTOS["i2v_convnext_dw_f32"]}
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
@@ -206,6 +226,7 @@ def load():
         bind(lib, _LOADER_PROTOS)
         bind(lib, _VIT_PROTOS)
         bind(lib, _SWIN_PROTOS)
+        bind(lib, _CONVNEXT_PROTOS)
         _lib = lib
     return _lib
 

@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import Graph, SwinSpec, VitSpec
+from .graphs import ConvNextSpec, Graph, SwinSpec, VitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -64,6 +64,30 @@ def _swin_synthetic(spec: SwinSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _convnext_synthetic(spec: ConvNextSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained ConvNeXt, drawn per key: the stem and downsample convolutions at fan_in^-0.5 (a unit-variance
+    stream stays one), depthwise filters at 1 / 7 (49 taps of unit inputs give unit outputs), fc1 at fan_in^-0.5 and fc2 at
+    0.5 fan_in^-0.5, LayerNorm gains near 1, small biases, and `gamma` spread over 0.1 .. 0.5 with random signs -- far from the ones a
+    forgotten fold would use.  Each block then adds a few tenths to its stream, which stays O(1) through 36 blocks."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.endswith("gamma"):
+            sd[k] = (0.1 + 0.4 * torch.rand(*shp, generator=g)) * (torch.randint(0, 2, shp, generator=g).float() * 2 - 1)
+        elif k.endswith(("norm.weight", "stem.1.weight", "downsample.0.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        elif k.endswith("conv_dw.weight"):
+            sd[k] = torch.randn(*shp, generator=g) / 7.0
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if k.endswith("fc2.weight") else 1.0) * fan_in ** -0.5)
+    return sd
+
+
 def check_swin_buffers(spec: SwinSpec, sd, where: str) -> None:
     """timm's Swin checkpoints carry the buffers `relative_position_index` and `attn_mask`; they are computed from the geometry here
     and never loaded, so one that differs describes another model: refused by key name."""
@@ -94,6 +118,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _vit_synthetic(graph, seed)
     if isinstance(graph, SwinSpec):
         return _swin_synthetic(graph, seed)
+    if isinstance(graph, ConvNextSpec):
+        return _convnext_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":
