@@ -495,5 +495,6 @@ extern "C" size_t i2v_net_workspace_bytes(i2v_handle h, int net) {
 // tests can run it without a GPU.  i2v_xf.h's file-local `fail` would be ambiguous with eng::fail under this unit's using-directives.
 #define fail xf_fail
 #include "i2v_convnext.cpp"
+#include "i2v_mixer.cpp"        // (... and the MLP-Mixer / ResMLP planner, on the same restatements and i2v_mixer_host.h)
 #undef fail
 #endif

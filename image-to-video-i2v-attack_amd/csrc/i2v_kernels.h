@@ -107,6 +107,11 @@ int k_se_scale(const I2VSeParams& p, i2v_stream_t s);
 // division fields; 0 ok, 1 the shape does not fit.
 int k_convnext_dw_plan(I2VCnDwParams* p);
 int k_convnext_dw(const I2VCnDwParams& p, i2v_stream_t s);
+// Token mixing of the MLP-Mixer / ResMLP blocks, forward and input gradient (I2VMixTokParams; i2v_mixer.hip -- product backend only,
+// under -DI2V_HAVE_MIXER; without it the callers run the launch as scalar host code, i2v_mixer_host.h).  k_mixer_tokens_plan picks
+// the channel tile and the LDS bytes; 0 ok, 1 bad arguments or the two tiles do not fit the LDS.
+int k_mixer_tokens_plan(I2VMixTokParams* p);
+int k_mixer_tokens(const I2VMixTokParams& p, i2v_stream_t s);
 int k_pool_fwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool_bwd(const I2VPoolParams& p, i2v_stream_t s);
 int k_pool3d_fwd(const I2VPoolParams& p, i2v_stream_t s);  // video max pooling (kt/stride_t/pad_t honoured)

@@ -3,6 +3,9 @@
 #ifndef I2V_HAVE_CONVNEXT
 #include "i2v_convnext_host.h"   // (the host simulation's one-file build: the token-major depthwise launch as scalar code)
 #endif
+#ifndef I2V_HAVE_MIXER
+#include "i2v_mixer_host.h"      // (... and the token-mixing launch)
+#endif
 
 #include <math.h>
 #include <string.h>
@@ -308,4 +311,44 @@ extern "C" int i2v_convnext_dw_f32(const float* x, const float* filter, const fl
     if (convnext_host::plan(&p) != 0 || convnext_host::dw(p) != 0) return fail("i2v_convnext_dw_f32: the shape does not fit the launch");
     return 0;
 #endif
+}
+
+// The MLP-Mixer / ResMLP token-mixing launch on its own (include/i2v_mixer.h), forward and input gradient: the device kernel where the
+// library has one, the scalar restatement of the same operations in the same order elsewhere.
+static int mixer_tokens_launch(const char* entry, I2VMixTokParams& p, void* stream) {
+#ifdef I2V_HAVE_MIXER
+    if (k_mixer_tokens_plan(&p) != 0)
+        return fail("%s: bad arguments, or the (tokens + hidden) x channel-tile floats do not fit the LDS (S %d, Sh %d, C %d, tile %d)", entry,
+                    p.S, p.Sh, p.C, p.ct);
+    RETURN_BE(k_mixer_tokens(p, stream));
+#else
+    (void)stream;
+    if (mixer_host::plan(&p) != 0 || mixer_host::tokens(p) != 0)
+        return fail("%s: bad arguments, or the (tokens + hidden) x channel-tile floats do not fit the LDS (S %d, Sh %d, C %d, tile %d)", entry,
+                    p.S, p.Sh, p.C, p.ct);
+    return 0;
+#endif
+}
+
+extern "C" int i2v_mixer_tokens_f32(const float* z, const float* residual, float* out, int frames, int S, int Sh, int C, const float* w1,
+                                    const float* b1, const float* w2, const float* b2, const float* in_scale, const float* in_shift,
+                                    const float* out_scale, int channel_tile, void* stream) {
+    BAD_ARG_IF(!z || !residual || !out || !w1 || !b1 || frames <= 0 || S <= 0 || Sh < 0 || C <= 0 || C % 4 != 0 || (Sh > 0 && (!w2 || !b2)) ||
+               (in_scale == nullptr) != (in_shift == nullptr));
+    I2VMixTokParams p; memset(&p, 0, sizeof p);
+    p.z = z; p.r = residual; p.out = out; p.wa = w1; p.ba = b1; p.wb = Sh > 0 ? w2 : nullptr; p.bb = Sh > 0 ? b2 : nullptr;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.out_scale = out_scale; p.F = frames; p.S = S; p.Sh = Sh; p.C = C; p.ct = channel_tile;
+    return mixer_tokens_launch(__func__, p, stream);
+}
+
+extern "C" int i2v_mixer_tokens_bwd_f32(const float* z, const float* g, const float* add, float* dz, int frames, int S, int Sh, int C,
+                                        const float* w1, const float* b1, const float* w2t, const float* w1t, const float* in_scale,
+                                        const float* in_shift, const float* out_scale, int channel_tile, void* stream) {
+    BAD_ARG_IF(!g || !dz || !w2t || frames <= 0 || S <= 0 || Sh < 0 || C <= 0 || C % 4 != 0 || (Sh > 0 && (!z || !w1 || !b1 || !w1t)) ||
+               (in_scale == nullptr) != (in_shift == nullptr));
+    I2VMixTokParams p; memset(&p, 0, sizeof p);
+    p.z = z; p.r = g; p.add0 = add; p.out = dz; p.wa = w1; p.ba = b1; p.wb = w2t; p.wc = Sh > 0 ? w1t : nullptr;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.out_scale = out_scale; p.F = frames; p.S = S; p.Sh = Sh; p.C = C; p.bwd = 1;
+    p.ct = channel_tile;
+    return mixer_tokens_launch(__func__, p, stream);
 }

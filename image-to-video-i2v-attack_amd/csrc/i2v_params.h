@@ -218,6 +218,34 @@ struct I2VCnDwParams {
 };
 enum { I2V_CNDW_RUN = 8 };
 
+// Token mixing of an MLP-Mixer / ResMLP block on token-major tensors (k_mixer_tokens, i2v_mixer.hip; the same arithmetic as scalar host
+// code in i2v_mixer_host.h): two products down the TOKEN axis of each frame, per channel, with the hidden tile kept on chip.
+// With t[s][c] = in_scale[c] * z[f][s][c] + in_shift[c] (t = z without the two arrays):
+//   forward   (bwd = 0)  out = r + out_scale[c] * (wb . gelu(wa . t + ba[row]) + bb[row])             wa (Sh, S), wb (S, Sh)
+//             Sh = 0     out = r + out_scale[c] * (wa . t + ba[row])                                  wa (S, S); no wb, no GELU
+//   backward  (bwd = 1)  out = in_scale[c] * (wc . (gelu'(wa . t + ba[row]) * (wb . (out_scale[c] * r)))) + add0 + add1
+//                        with r the gradient of the forward's output, wb = W2^T (Sh, S) and wc = W1^T (S, Sh): the input gradient
+//             Sh = 0     out = in_scale[c] * (wb . (out_scale[c] * r)) + add0 + add1                  wb = W^T (S, S); z, wa unused
+// Every weight matrix is row-major with the CONTRACTED index contiguous.  z, r, out, add0, add1 are (F, S, C), channels contiguous.
+// Order (the contract of include/i2v_mixer.h): every product element is ONE fp32 chain acc = fma(w[m][k], v[k][c], acc) from 0.f over
+// k = 0 .. K-1 in increasing order, K stepped in pairs: an odd K ends with one fma(0.f, 0.f, acc); then + bias[row]; then GELU (or
+// * gelu'(pre)); then out_scale[c] * v; then r + v (backward: in_scale[c] * v, then add0 + v, then v + add1).  t = fma(in_scale, z,
+// in_shift).  out may be z, r or add0: a workgroup reads its (frame, channel tile) of them before it writes it.
+struct I2VMixTokParams {
+    const float* z;
+    const float* r;
+    const float *add0, *add1;            // backward only, optional
+    float* out;
+    const float *wa, *ba, *wb, *bb, *wc;
+    const float *in_scale, *in_shift;    // (C) each, both or neither
+    const float* out_scale;              // (C) or null
+    int32_t F, S, Sh, C, bwd;
+    // k_mixer_tokens_plan: ct on entry 0 (choose) or a tile to insist on; filled on return
+    int32_t ct;                          // channels per workgroup: 32 or 64
+    int32_t lds_bytes;                   // (S + Sh) * ct * 4: the input tile and the hidden tile
+};
+enum { I2V_MIXTOK_LDS_MAX = 160 * 1024 };
+
 struct I2VPoolParams {
     const float* x;    int64_t x_nstride;    int32_t C, Hs, Ws;
     float* y;          int64_t y_nstride;    int32_t Ho, Wo;       // fwd: output; bwd: upstream grad

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "i2v_be.h"
+#include "i2v_gelu.h"          // gelu_f, gelu_grad_f (shared with i2v_mixer.hip)
 #include "i2v_vit_kernels.h"
 
 namespace {
@@ -27,15 +28,6 @@ __device__ __forceinline__ float4 ld4(const float* p, int lim, bool vec) {
     if (lim > 2) v.z = p[2];
     if (lim > 3) v.w = p[3];
     return v;
-}
-
-__device__ __forceinline__ float gelu_f(float h) {            // 0.5 h (1 + erf(h / sqrt 2)), torch's exact form
-    return __fmul_rn(__fmul_rn(0.5f, h), __fadd_rn(1.f, erff(__fmul_rn(h, 0.70710678118654752f))));
-}
-__device__ __forceinline__ float gelu_grad_f(float h) {       // 0.5 (1 + erf(h / sqrt 2)) + h exp(-h^2 / 2) / sqrt(2 pi)
-    const float cdf = __fmul_rn(0.5f, __fadd_rn(1.f, erff(__fmul_rn(h, 0.70710678118654752f))));
-    const float pdf = __fmul_rn(expf(__fmul_rn(-0.5f, __fmul_rn(h, h))), 0.39894228040143268f);
-    return __fadd_rn(cdf, __fmul_rn(h, pdf));
 }
 
 // AK: A is K-contiguous (a_sk == 1), else M-contiguous (a_sm == 1).  BK: B is K-contiguous (b_sk == 1), else N-contiguous (b_sn == 1).

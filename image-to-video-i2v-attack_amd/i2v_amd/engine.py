@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import ConvNextSpec, Graph, SwinSpec, VitSpec
+from .graphs import ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -109,6 +109,40 @@ class Engine:
                                                             _ptr(add, self) if add is not None else None, _ptr(y, self), n, H, W, Cn,
                                                             self.stream()))
         return y
+
+    def build_mixer_net(self, spec: MixerSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "MixerNet":
+        """An MLP-Mixer / ResMLP surrogate (`include/i2v_mixer.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
+        return self._build(MixerNet, spec, state_dict, list(hook_blocks), max_frames)
+
+    def mixer_tokens(self, z: torch.Tensor, residual: torch.Tensor, w1, b1, w2=None, b2=None, in_scale=None, in_shift=None, out_scale=None,
+                     channel_tile: int = 0) -> torch.Tensor:
+        """The token-mixing launch on its own (`i2v_mixer_tokens_f32`): z, residual (frames, S, C) token-major; w1 (Sh, S), b1 (Sh),
+        w2 (S, Sh), b2 (S) -- or, without w2, the one Linear w1 (S, S), b1 (S) of ResMLP; optional per-channel in_scale / in_shift /
+        out_scale -> residual + out_scale * tokmix(in_scale * z + in_shift), (frames, S, C)."""
+        n, S, Cn = z.shape
+        Sh = 0 if w2 is None else w1.shape[0]
+        assert tuple(w1.shape) == ((Sh, S) if Sh else (S, S)) and (w2 is None or tuple(w2.shape) == (S, Sh))
+        out = torch.empty_like(z)
+        o = lambda t: _ptr(t, self) if t is not None else None      # noqa: E731
+        _lib.check(self.capi, self.capi.i2v_mixer_tokens_f32(_ptr(z, self), _ptr(residual, self), _ptr(out, self), n, S, Sh, Cn, _ptr(w1, self),
+                                                             _ptr(b1, self), o(w2), o(b2), o(in_scale), o(in_shift), o(out_scale),
+                                                             channel_tile, self.stream()))
+        return out
+
+    def mixer_tokens_bwd(self, z, g: torch.Tensor, w1, b1, w2=None, in_scale=None, in_shift=None, out_scale=None, add=None,
+                         channel_tile: int = 0) -> torch.Tensor:
+        """The input gradient of that launch (`i2v_mixer_tokens_bwd_f32`) from g = d(out), plus `add`: the transposed copies the entry
+        wants are made here.  Without w2 (ResMLP) z and b1 are not needed."""
+        n, S, Cn = g.shape
+        Sh = 0 if w2 is None else w1.shape[0]
+        w2t = (w2 if Sh else w1).t().contiguous()
+        w1t = w1.t().contiguous() if Sh else None
+        dz = torch.empty_like(g)
+        o = lambda t: _ptr(t, self) if t is not None else None      # noqa: E731
+        _lib.check(self.capi, self.capi.i2v_mixer_tokens_bwd_f32(o(z if Sh else None), _ptr(g, self), o(add), _ptr(dz, self), n, S, Sh, Cn,
+                                                                 o(w1 if Sh else None), o(b1 if Sh else None), _ptr(w2t, self), o(w1t),
+                                                                 o(in_scale), o(in_shift), o(out_scale), channel_tile, self.stream()))
+        return dz
 
     # ---- measurement ----
     KINDS = ("conv_igemm_fwd", "conv_igemm_imggrad", "pool_fwd", "pool_bwd", "addmask", "conv_igemm_dgrad")
@@ -725,3 +759,25 @@ class ConvNextNet(TokenNet):
     def hook_shape(self, i):
         st = self.hook_tensors[i]
         return (self.graph.tokens(st), self.graph.width(st), 1)
+
+
+class MixerNet(TokenNet):
+    """An MLP-Mixer / ResMLP surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame."""
+    _api = "mixer"
+
+    def _create(self, spec: MixerSpec, sd, hook_blocks, max_frames):
+        eng, capi = self.eng, self.eng.capi
+        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
+        # native order (include/i2v_mixer.h): the stem, then the blocks; ResMLP with its folds made; kept alive until the upload
+        w = spec.native_arrays(sd, nb)
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
+        cfg = _lib.MixerConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.blocks, spec.tokens_hidden, spec.mlp,
+                               1 if spec.kind == "resmlp" else 0, spec.ln_eps)
+        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
+        h = C.c_void_p()
+        _lib.check(capi, capi.i2v_mixer_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames,
+                                               C.byref(h)))
+        return h
+
+    def hook_shape(self, i):
+        return (self.graph.tokens, self.graph.dim, 1)

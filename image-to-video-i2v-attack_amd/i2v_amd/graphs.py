@@ -1407,6 +1407,193 @@ def convnext_tiny_twin(in_hw=(64, 64)) -> ConvNextSpec:
 
 
 # ---------------------------------------------------------------------------
+# the all-MLP surrogates: MLP-Mixer and ResMLP, planned on the transformer stack (include/i2v_mixer.h)
+# ---------------------------------------------------------------------------
+#: timm 0.5.0's `MlpMixer` models at 224 x 224 with ImageNet-1k heads: name -> (kind, patch, dim, blocks).  The distilled ResMLPs are
+#: the same graph as the plain ones: distinct names, distinct checkpoint files.
+MIXER_MODELS: Dict[str, Tuple[str, int, int, int]] = {
+    "mixer_s32_224": ("mixer", 32, 512, 8),
+    "mixer_s16_224": ("mixer", 16, 512, 8),
+    "mixer_b32_224": ("mixer", 32, 768, 12),
+    "mixer_b16_224": ("mixer", 16, 768, 12),
+    "mixer_l32_224": ("mixer", 32, 1024, 24),
+    "mixer_l16_224": ("mixer", 16, 1024, 24),
+    "resmlp_12_224": ("resmlp", 16, 384, 12),
+    "resmlp_24_224": ("resmlp", 16, 384, 24),
+    "resmlp_36_224": ("resmlp", 16, 384, 36),
+    "resmlp_12_distilled_224": ("resmlp", 16, 384, 12),
+    "resmlp_24_distilled_224": ("resmlp", 16, 384, 24),
+    "resmlp_36_distilled_224": ("resmlp", 16, 384, 36),
+}
+
+
+@dataclass
+class MixerSpec:
+    """timm 0.5.0 `MlpMixer`: the stem is a patch x patch convolution with stride patch and bias -- no norm, no
+    prefix token, no pos_embed --, giving `tokens` = (img / patch)^2 tokens of `dim` channels; then `blocks` blocks.
+      kind "mixer"  (`MixerBlock`)  x += mlp_tokens(LN1(x)^T)^T, fc1 (tokens_hidden, tokens), GELU, fc2 (tokens, tokens_hidden), down the
+                                    token axis per channel; x += mlp_channels(LN2(x)), fc1 (mlp, dim), GELU, fc2; LayerNorm eps `ln_eps`
+      kind "resmlp" (`ResBlock`)    x += ls1 * linear_tokens((alpha1 * x + beta1)^T)^T; x += ls2 * mlp_channels(alpha2 * x + beta2);
+                                    `Affine` norms, tokens_hidden = 0
+    Exact GELU.  `hooks`: depth d (1..4) -> zero-based block d * blocks / 4 - 1, whose OUTPUT (the residual stream after it, all tokens)
+    is the hooked feature: tokens * dim floats per frame, token-major."""
+    arch: str
+    img: int
+    patch: int = 16
+    in_chans: int = 3
+    dim: int = 768
+    blocks: int = 12
+    kind: str = "mixer"
+    ln_eps: float = 1e-6
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        if self.kind not in ("mixer", "resmlp"):
+            raise ValueError(f"{self.arch}: kind {self.kind!r} (mixer or resmlp)")
+        if self.img % self.patch or self.patch % 4 or self.dim % 4:
+            raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame, patch {self.patch}, width {self.dim}: the patch must divide "
+                             "the frame, and patch and width must be multiples of 4")
+        if self.blocks % 4:
+            raise ValueError(f"{self.arch}: {self.blocks} blocks: depths 1..4 hook blocks d * blocks / 4 - 1")
+        if not self.hooks:
+            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def tokens(self) -> int:
+        return (self.img // self.patch) ** 2
+
+    @property
+    def tokens_hidden(self) -> int:
+        """Width of the token MLP's hidden layer (timm's mlp_ratio[0] = 0.5 of dim); 0 for ResMLP, whose token mixing is one Linear."""
+        return self.dim // 2 if self.kind == "mixer" else 0
+
+    @property
+    def mlp(self) -> int:
+        return 4 * self.dim
+
+    def hook_dim(self, i: int = 0) -> int:
+        """Floats per frame of the feature hooked at block i (the same for every block)."""
+        return self.tokens * self.dim
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def block_keys(self, i: int) -> List[str]:
+        p = f"blocks.{i}."
+        if self.kind == "mixer":
+            names = ("norm1.weight", "norm1.bias", "mlp_tokens.fc1.weight", "mlp_tokens.fc1.bias", "mlp_tokens.fc2.weight",
+                     "mlp_tokens.fc2.bias", "norm2.weight", "norm2.bias", "mlp_channels.fc1.weight", "mlp_channels.fc1.bias",
+                     "mlp_channels.fc2.weight", "mlp_channels.fc2.bias")
+        else:
+            names = ("ls1", "ls2", "norm1.alpha", "norm1.beta", "linear_tokens.weight", "linear_tokens.bias", "norm2.alpha", "norm2.beta",
+                     "mlp_channels.fc1.weight", "mlp_channels.fc1.bias", "mlp_channels.fc2.weight", "mlp_channels.fc2.bias")
+        return [p + k for k in names]
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block, in timm's order (`norm.*` and `head.*` lie behind
+        every hook and are not used)."""
+        D, S, Sh, H = self.dim, self.tokens, self.tokens_hidden, self.mlp
+        out = {"stem.proj.weight": (D, self.in_chans, self.patch, self.patch), "stem.proj.bias": (D,)}
+        if self.kind == "mixer":
+            shapes = [(D,), (D,), (Sh, S), (Sh,), (S, Sh), (S,), (D,), (D,), (H, D), (H,), (D, H), (D,)]
+        else:
+            shapes = [(D,), (D,), (1, 1, D), (1, 1, D), (S, S), (S,), (1, 1, D), (1, 1, D), (H, D), (H,), (D, H), (D,)]
+        for i in range(self.blocks):
+            out.update(zip(self.block_keys(i), shapes))
+        return out
+
+    def native_arrays(self, sd, n_blocks: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_mixer_create` takes for the first `n_blocks` blocks, from a timm-layout state dict, as float32 host tensors.
+        MLP-Mixer: the stem and each block's twelve arrays as they lie.  ResMLP, nine per block: alpha1, beta1 and ls1 as (dim) arrays
+        for the token launch, linear_tokens as it lies, then mlp_channels.fc1 with `norm2` folded in (column c times alpha2[c]; bias
+        plus weight . beta2) and mlp_channels.fc2 with `ls2` folded in (row o and bias element o times ls2[o]): the affine and the layer
+        scale of the channel half cost nothing at run time.  The folds are made in float64."""
+        f = lambda k: sd[k].detach().float().cpu()      # noqa: E731
+        out = [f("stem.proj.weight").contiguous(), f("stem.proj.bias").contiguous()]
+        for i in range(n_blocks):
+            k = self.block_keys(i)
+            if self.kind == "mixer":
+                out += [f(x).contiguous() for x in k]
+                continue
+            ls1, ls2, a1, b1, a2, b2 = (f(x).reshape(-1) for x in (k[0], k[1], k[2], k[3], k[6], k[7]))
+            w1, c1, w2, c2 = (f(x).double() for x in k[8:12])
+            out += [a1.contiguous(), b1.contiguous(), ls1.contiguous(), f(k[4]).contiguous(), f(k[5]).contiguous()]
+            out += [(w1 * a2.double()[None, :]).float().contiguous(), (c1 + w1 @ b2.double()).float().contiguous()]
+            out += [(w2 * ls2.double()[:, None]).float().contiguous(), (c2 * ls2.double()).float().contiguous()]
+        return out
+
+    def macs_per_frame(self) -> int:
+        S, D, Sh, H = self.tokens, self.dim, self.tokens_hidden, self.mlp
+        token = 2 * S * Sh * D if Sh else S * S * D
+        return S * D * self.in_chans * self.patch ** 2 + self.blocks * (token + 2 * S * D * H)
+
+    def workspace_bytes(self, hook_blocks: Sequence[int], frames: int) -> int:
+        """Device bytes `i2v_mixer_create` plans for these hooked blocks and `frames` frames (the formula of csrc/i2v_mixer.cpp).
+        MLP-Mixer: the weights of the blocks run, each block's two token weights once more (the transposed copies); patches; per block
+        its mid stream, its output, the fc1 pre-activation and four statistics per token; the first block's input; the shared scratch
+        (two streams, one more for the running gradient, one MLP-wide); one gradient view per hook.  ResMLP: the folded weights, the
+        token weight twice; patches; one stream; per block the fc1 pre-activation; scratch (one MLP-wide, the running gradient); per
+        hook a copy of the stream and a gradient view."""
+        D, S, Sh, H, nb = self.dim, self.tokens, self.tokens_hidden, self.mlp, max(hook_blocks) + 1
+        KP, FT, nh = self.in_chans * self.patch ** 2, frames * self.tokens, len(hook_blocks)
+        weights = D * KP + D
+        if self.kind == "mixer":
+            weights += nb * (4 * D + 2 * Sh * S + Sh + S + 2 * D * H + H + D + 2 * S * Sh)
+            acts = FT * KP + nb * (2 * FT * D + FT * H + 4 * FT) + FT * D + (3 * FT * D + FT * H)
+        else:
+            weights += nb * (3 * D + S * S + S + 2 * D * H + H + D + S * S)
+            acts = FT * KP + nb * FT * H + FT * D + (FT * H + FT * D) + nh * FT * D
+        return 4 * (weights + acts + nh * FT * D)
+
+
+def is_mixer_name(model_name: str) -> bool:
+    """A name of timm's all-MLP vocabulary (`mlp_mixer.py`), served (`MIXER_MODELS`) or not: `graphs.build` routes these to
+    `mixer_named`, which refuses the ones that are not offered with a message that lists the served names."""
+    return model_name in MIXER_MODELS or model_name.startswith(("mixer_", "resmlp_", "gmixer_", "gmlp_"))
+
+
+def mixer_named(model_name: str, in_hw=(224, 224)) -> MixerSpec:
+    """Any row of `MIXER_MODELS`, at 224 x 224 only.  Refused, each with the reason: the in21k / in22ft1k / miil / dino checkpoints,
+    `resmlp_big_24_*` (patch 8), the gated models (`gmixer_*`, `gmlp_*`), and names outside the table."""
+    served = "served: " + ", ".join(MIXER_MODELS)
+    if model_name not in MIXER_MODELS:
+        if any(t in model_name for t in ("_in21k", "_in22ft1k", "_miil", "_dino")):
+            why = ("the in21k / in22ft1k / miil / dino checkpoints carry other label sets or expect other pre-processing and are not "
+                   "offered (the ImageNet-1k models only)")
+        elif model_name.startswith("resmlp_big_24_"):
+            why = "resmlp_big_24 cuts 8 x 8 patches (784 tokens): the token tile is not planned for it"
+        elif model_name.startswith(("gmixer_", "gmlp_")):
+            why = "the gated models (gMixer's SiLU-gated units, gMLP's spatial gating unit) are not built"
+        else:
+            why = "not a model of this table"
+        raise ValueError(f"MLP-Mixer / ResMLP surrogate {model_name!r}: {why}; {served}")
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}): its token-mixing weights "
+                         "fix the number of tokens")
+    kind, patch, dim, blocks = MIXER_MODELS[model_name]
+    return MixerSpec(model_name, 224, patch, 3, dim, blocks, kind)
+
+
+def mixer_tiny_twin(kind: str = "mixer", patch: int = 16, in_hw=(64, 64)) -> MixerSpec:
+    """The same topology at test size: dim 32, 8 blocks, so depths 1..4 hook blocks 1, 3, 5, 7; square frames of a multiple of 32 pixels,
+    whose size fixes the token count and with it the token weights.  At 64 x 64 -- "mixer_test": patch 16, 16 tokens, token hidden
+    width 16; "mixer_test_patch32": 4 tokens; "resmlp_test": the ResMLP twin, patch 32, 4 tokens.  None of them is a row of
+    `MIXER_MODELS`."""
+    if in_hw[0] != in_hw[1] or in_hw[0] % 32:
+        raise ValueError(f"the test-size MLP-Mixer / ResMLP take square frames of a multiple of 32 pixels (got {tuple(in_hw)})")
+    arch = "resmlp_test" if kind == "resmlp" else "mixer_test" + ("_patch32" if patch == 32 else "")
+    return MixerSpec(arch, int(in_hw[0]), patch, 3, 32, 8, kind)
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -1443,6 +1630,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return swin_named(model_name, in_hw)
     if is_convnext_name(model_name):    # extension: timm's ConvNeXt family (7 x 7 depthwise blocks, planned on the transformer stack)
         return convnext_named(model_name, in_hw)
+    if is_mixer_name(model_name):       # extension: timm's all-MLP models, MLP-Mixer and ResMLP (token mixing down the token axis)
+        return mixer_named(model_name, in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -1483,4 +1672,7 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return swin_tiny(in_hw)
     if model_name in CONVNEXT_MODELS:
         return convnext_tiny_twin(in_hw)
+    if model_name in MIXER_MODELS:      # one twin per kind: the Mixer one follows the name's patch, the ResMLP one has 4 tokens
+        kind, patch, _, _ = MIXER_MODELS[model_name]
+        return mixer_tiny_twin(kind, patch if kind == "mixer" else 32, in_hw)
     return build(model_name, in_hw)

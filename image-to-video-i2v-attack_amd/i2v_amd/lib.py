@@ -201,6 +201,27 @@ CONVNEXT_EXPORTS = tuple(_CONVNEXT_PROTOS)
 CONVNEXT_NODE_PROTOS = {"i2v_convnext_dw_f32": _CONVNEXT_PROTOS["i2v_convnext_dw_f32"]}
 
 
+class MixerConfig(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("img", "patch", "in_chans", "dim", "blocks", "tokens_hidden", "mlp", "kind")] + [("ln_eps", C.c_float)])
+
+
+# The all-MLP surrogates, MLP-Mixer and ResMLP (`include/i2v_mixer.h`): a header of its own, kept apart from EXPORTS.  The host
+# simulation exports all of it: the planner runs there on scalar restatements, and so does the token-mixing launch on its own.
+_MIXER_PROTOS = {
+    "i2v_mixer_create": ([_I, C.POINTER(MixerConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    "i2v_mixer_destroy": ([_P], _I),
+    "i2v_mixer_workspace_bytes": ([_P], _L),
+    "i2v_mixer_forward": ([_P, _P, _I, _P], _I),
+    "i2v_mixer_backward": ([_P, _P, _I, _P], _I),
+    "i2v_mixer_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+    "i2v_mixer_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    "i2v_mixer_tokens_f32": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P], _I),
+    "i2v_mixer_tokens_bwd_f32": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P], _I),
+}
+MIXER_EXPORTS = tuple(_MIXER_PROTOS)
+MIXER_NODE_PROTOS = {k: _MIXER_PROTOS[k] for k in ("i2v_mixer_tokens_f32", "i2v_mixer_tokens_bwd_f32")}
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
@@ -227,6 +248,7 @@ def load():
         bind(lib, _VIT_PROTOS)
         bind(lib, _SWIN_PROTOS)
         bind(lib, _CONVNEXT_PROTOS)
+        bind(lib, _MIXER_PROTOS)
         _lib = lib
     return _lib
 

@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import ConvNextSpec, Graph, SwinSpec, VitSpec
+from .graphs import ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -88,6 +88,32 @@ def _convnext_synthetic(spec: ConvNextSpec, seed: int) -> Dict[str, torch.Tensor
     return sd
 
 
+def _mixer_synthetic(spec: MixerSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained MLP-Mixer / ResMLP, drawn per key: Linears (the stem as one) at fan_in^-0.5, the second Linear of
+    an MLP at 0.5 fan_in^-0.5, LayerNorm gains near 1, small biases.  ResMLP's `ls1` / `ls2` are spread over 0.1 .. 0.4 with random
+    signs, `alpha` over 0.5 .. 1.5 and `beta` ~ 0.3 N(0, 1): far from timm's initial 1e-4 / 1 / 0 and from the ones and zeros a
+    forgotten fold would use."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.endswith((".ls1", ".ls2")):
+            sd[k] = (0.1 + 0.3 * torch.rand(*shp, generator=g)) * (torch.randint(0, 2, shp, generator=g).float() * 2 - 1)
+        elif k.endswith(".alpha"):
+            sd[k] = 0.5 + torch.rand(*shp, generator=g)
+        elif k.endswith(".beta"):
+            sd[k] = 0.3 * torch.randn(*shp, generator=g)
+        elif k.endswith(("norm1.weight", "norm2.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if k.endswith("fc2.weight") else 1.0) * fan_in ** -0.5)
+    return sd
+
+
 def check_swin_buffers(spec: SwinSpec, sd, where: str) -> None:
     """timm's Swin checkpoints carry the buffers `relative_position_index` and `attn_mask`; they are computed from the geometry here
     and never loaded, so one that differs describes another model: refused by key name."""
@@ -120,6 +146,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _swin_synthetic(graph, seed)
     if isinstance(graph, ConvNextSpec):
         return _convnext_synthetic(graph, seed)
+    if isinstance(graph, MixerSpec):
+        return _mixer_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":

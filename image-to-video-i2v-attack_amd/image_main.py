@@ -45,7 +45,8 @@ def arg_parse(argv=None, ucf101=False):
                              + ", ".join(graphs.SWIN_MODELS) + "; and torchvision's other ResNets, Wide ResNets and ResNeXts: "
                              + ", ".join(graphs.RESNET_FAMILY) + "; and torchvision's MNASNets: " + ", ".join(graphs.MNASNET_MODELS)
                              + "; and timm's SE-ResNets / SE-ResNeXts: " + ", ".join(graphs.SERESNET_FAMILY) + "; and timm's ConvNeXts at 224 x 224: "
-                             + ", ".join(graphs.CONVNEXT_MODELS) + ")")
+                             + ", ".join(graphs.CONVNEXT_MODELS) + "; and timm's MLP-Mixers and ResMLPs at 224 x 224: "
+                             + ", ".join(graphs.MIXER_MODELS) + ")")
     # additions (not in the reference)
     parser.add_argument("--anno", type=str, default=os.environ.get("I2V_ANNO", ""),
                         help="sample list csv `path,gt_label,clip_index` (the reference's kinetics400_attack_samples.csv, utils.py:29); without it 400 synthetic names with labels 0..399 are used")
@@ -80,7 +81,8 @@ def arg_parse(argv=None, ucf101=False):
         # hooked blocks / stages
         for is_name, named, hooked in ((graphs.is_vit_name, graphs.vit_named, "blocks {}"),
                                        (graphs.is_swin_name, graphs.swin_named, "the last block of stages {}"),
-                                       (graphs.is_convnext_name, graphs.convnext_named, "the last block of stages {}")):
+                                       (graphs.is_convnext_name, graphs.convnext_named, "the last block of stages {}"),
+                                       (graphs.is_mixer_name, graphs.mixer_named, "blocks {}")):
             if not is_name(args.direction_image_model):
                 continue
             try:
