@@ -211,31 +211,47 @@ __device__ __forceinline__ void conv_vec_rows(const PT& p, const int i, const in
 }
 
 #define I2V_FROW(r) (MF16 ? 4 * lk + (r) : ((r) & 3) + 8 * ((r) >> 2) + 4 * lk)
+// ... and its first half: one pass of a block's accumulators (`acc`: the TP fragments of every wave) transposed into the LDS tile `Cs`
+// ([rows][BP], a barrier on either side), where a lane then finds 4 consecutive pixels of a channel row.  The shortcut-pair kernel
+// (i2v_conv_scpair.hip) takes its first sum through it as well.
+template <int BP, int WP, bool MF16, int TP, typename ACC>
+__device__ __forceinline__ void conv_acc_to_rows(ACC (&acc)[TP], float (*const Cs)[BP]) {
+    constexpr int FR = MF16 ? 16 : 32, NR = MF16 ? 4 : 16;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wd = wave / WP, wpx = wave % WP;
+    const int l31 = MF16 ? (lane & 15) : (lane & 31), lk = MF16 ? (lane >> 4) : (lane >> 5);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < TP; ++j)
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            Cs[wd * FR + I2V_FROW(r)][wpx * (BP / WP) + j * FR + l31] = acc[j][r];
+    __syncthreads();
+}
 template <int BD, int BP, int WD, int WP, bool PREF, bool MF16, bool FUSE, typename ACC, typename PT>
 __device__ __forceinline__ void conv_vec_epilogue(const PT& p, ACC (&acc)[BD / WD / (MF16 ? 16 : 32)][BP / WP / (MF16 ? 16 : 32)], const int cd0,
                                                   const int64_t px0, float* const smem, const float4* const pre0, const unsigned* const pregw,
                                                   float* const mid) {
-    constexpr int FR = MF16 ? 16 : 32, NR = MF16 ? 4 : 16, TD = BD / WD / FR, TP = BP / WP / FR;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wd = wave / WP, wpx = wave % WP;
-    const int l31 = MF16 ? (lane & 15) : (lane & 31), lk = MF16 ? (lane >> 4) : (lane >> 5);
+    constexpr int FR = MF16 ? 16 : 32, TD = BD / WD / FR;
+    const int t = threadIdx.x;
     // Dense output (grid == output plane, plane % 4 == 0): transpose the accumulators through LDS so
     // that each lane owns 4 consecutive pixels of one channel; addends, gate and result then move as
     // 16-byte accesses, 512 contiguous bytes per channel row.
     float (*Cs)[BP] = reinterpret_cast<float (*)[BP]>(smem);
 #pragma unroll
     for (int i = 0; i < TD; ++i) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < TP; ++j)
-#pragma unroll
-            for (int r = 0; r < NR; ++r)
-                Cs[wd * FR + I2V_FROW(r)][wpx * (BP / WP) + j * FR + l31] = acc[i][j][r];
-        __syncthreads();
+        conv_acc_to_rows<BP, WP, MF16>(acc[i], Cs);
         conv_vec_rows<BD, BP, WD, PREF, MF16, FUSE>(p, i, cd0, px0, Cs, t, pre0, pregw, mid);
     }
 }
 #undef I2V_FROW
+
+// XCD-aware remap: consecutive logical tiles (same pixel tile, neighbouring channel tiles) share one XCD's L2 instead of being dealt
+// round-robin over the 8 XCDs (bijective form): block `bid` of `nwg` -> logical tile.
+__device__ __forceinline__ int conv_xcd_lid(const int bid, const int nwg) {
+    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
 
 // One tile of the implicit GEMM.  `bid` of `nwg` blocks share `n_cd_tiles` channel tiles per pixel tile, the first pixel tile
 // starting at pixel `px_base` (a launch may be cut into regions with different tile shapes, conv_igemm_tail below).
@@ -244,10 +260,15 @@ __device__ __forceinline__ void conv_vec_epilogue(const PT& p, ACC (&acc)[BD / W
 // MFMA.  Those are what a block that is alone on its CU (an under-filled launch: a single 32-frame clip leaves the 14x14 layers
 // with 1.5 tiles per CU) cannot hide behind a neighbour.  Costs LDS (64x64: 32 KB, 5 resident blocks), so it is one more
 // configuration of the autotuner (bit 6), for launches whose chunk count is a multiple of CPB.
+//
+// conv_tile_loop is the tile's first half: operand staging and the K loop of the tile at (cd0, px0), which leaves the finished sums in
+// `acc` (MFMA accumulator layout) and, for PREF, the prefetched first addend / gate words in `pre0` / `pregw`.  conv_tile below is that
+// loop plus the epilogue; the shortcut-pair kernel (i2v_conv_scpair.hip) runs the loop twice for one output tile.
 template <int BD, int BP, int WD, int WP, int MODE, bool PREF, bool PRE = false, bool VID = false, bool MF16 = false, int HWM = 0, int CPB = 1, int FUSE = 0, int BF3 = 0>
-__device__ __forceinline__ void conv_tile(const I2VConvParams& p, const int n_cd_tiles, const int bid, const int nwg, const int64_t px_base,
-                                          float* const smem, I2V_PROBE_T& probe, const int probe_slot, const int prio_arg = I2V_PRIO_LEVELS,
-                                          float* const mid = nullptr) {
+__device__ __forceinline__ void conv_tile_loop(const I2VConvParams& p, const int cd0, const int64_t px0, const int nwg, float* const smem, I2V_PROBE_T& probe,
+                                               const int probe_slot, const int prio_arg,
+                                               typename std::conditional<MF16, f32x4, f32x16>::type (&acc)[BD / WD / (MF16 ? 16 : 32)][BP / WP / (MF16 ? 16 : 32)],
+                                               float4 (&pre0)[PREF ? WD * (MF16 ? 16 : 32) / (1024 / BP) : 1], unsigned (&pregw)[PREF ? WD * (MF16 ? 16 : 32) / (1024 / BP) : 1]) {
 #if defined(__HIP_DEVICE_COMPILE__)      // buffer-resource types and LDS-DMA builtins exist only in the device pass
     constexpr int KC = I2V_KC;
     constexpr int FR = MF16 ? 16 : 32;                       // fragment edge
@@ -287,14 +308,6 @@ __device__ __forceinline__ void conv_tile(const I2VConvParams& p, const int n_cd
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wd = wave / WP, wpx = wave % WP;
-
-    // XCD-aware remap: consecutive logical tiles (same pixel tile, neighbouring channel tiles) share
-    // one XCD's L2 instead of being dealt round-robin over the 8 XCDs (bijective form).
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int cd_tile = lid % n_cd_tiles;
-    const int64_t px0 = px_base + (int64_t)(lid / n_cd_tiles) * BP;
-    const int cd0 = cd_tile * BD;
 
     const int HWg = p.Hg * p.Wg;
     const int64_t P = (int64_t)p.N * HWg;
@@ -425,9 +438,8 @@ __device__ __forceinline__ void conv_tile(const I2VConvParams& p, const int n_cd
     // Only the first addend and the 1-bit gate word are prefetched (20 registers): a second addend or an fp32 mask
     // (I2V_GATES=0) is read in the epilogue itself.  Prefetching all four cost 48 more registers and one third of the
     // resident blocks -- on launches that are HBM-bound and live on bytes in flight.
-    float4 pre0[PREF ? E_NQ : 1];
-    unsigned pregw[PREF ? E_NQ : 1];                       // 1-bit gates: the word holding this lane's 4 bits
-    if (PREF) {
+    static_assert(!PREF || E_NQ == WD * (MF16 ? 16 : 32) / (1024 / BP), "pre0 / pregw (the caller's): one entry per row a lane owns");
+    if (PREF) {                                            // (pregw, 1-bit gates: the word holding this lane's 4 bits)
         const int e_c4 = t % E_C4, e_rbase = t / E_C4;
         const int64_t e_pp = px0 + (int64_t)e_c4 * 4;
         const bool e_ok = e_pp < P;
@@ -489,8 +501,6 @@ __device__ __forceinline__ void conv_tile(const I2VConvParams& p, const int n_cd
         out[2] = __builtin_bit_cast(bf8, (u4){q3[0], q3[1], q3[2], q3[3]});
     };
     (void)bf3_split_frag;
-    typedef typename std::conditional<MF16, f32x4, f32x16>::type acc_t;
-    acc_t acc[TD][TP];
 #pragma unroll
     for (int a = 0; a < TD; ++a)
 #pragma unroll
@@ -502,7 +512,6 @@ __device__ __forceinline__ void conv_tile(const I2VConvParams& p, const int n_cd
     // fragment coordinates of this lane: column (pixel) inside a fragment, K row inside a k-step, and the
     // accumulator register -> fragment row map  (32x32x2: row = (r&3) + 8(r>>2) + 4(l>>5);  16x16x4: row = 4(l>>4) + r)
     const int l31 = MF16 ? (lane & 15) : (lane & 31), lk = MF16 ? (lane >> 4) : (lane >> 5);
-#define I2V_FROW(r) (MF16 ? 4 * lk + (r) : ((r) & 3) + 8 * ((r) >> 2) + 4 * lk)
     // ---- main loop: two LDS buffers, ONE barrier per K chunk, software-pipelined inside the wave -------------
     // An fp32 MFMA holds its SIMD for 64 (32x32x2) / 32 (16x16x4) cycles, so everything else a wave has to do
     // for a chunk is issued in the shadow of its own MFMAs instead of in front of them:
@@ -916,7 +925,32 @@ __device__ __forceinline__ void conv_tile(const I2VConvParams& p, const int n_cd
 #undef I2V_CHUNK_VB
     if (prio_hi > 0) __builtin_amdgcn_s_setprio(0);
     probe.loop_end(probe_slot);
+#endif
+}
 
+template <int BD, int BP, int WD, int WP, int MODE, bool PREF, bool PRE = false, bool VID = false, bool MF16 = false, int HWM = 0, int CPB = 1, int FUSE = 0, int BF3 = 0>
+__device__ __forceinline__ void conv_tile(const I2VConvParams& p, const int n_cd_tiles, const int bid, const int nwg, const int64_t px_base,
+                                          float* const smem, I2V_PROBE_T& probe, const int probe_slot, const int prio_arg = I2V_PRIO_LEVELS,
+                                          float* const mid = nullptr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int FR = MF16 ? 16 : 32, NR = MF16 ? 4 : 16, TD = BD / WD / FR, TP = BP / WP / FR;
+    const int lid = conv_xcd_lid(bid, nwg);
+    const int cd_tile = lid % n_cd_tiles;
+    const int64_t px0 = px_base + (int64_t)(lid / n_cd_tiles) * BP;
+    const int cd0 = cd_tile * BD;
+
+    constexpr int E_NQ = WD * FR / (1024 / BP);
+    float4 pre0[PREF ? E_NQ : 1];
+    unsigned pregw[PREF ? E_NQ : 1];
+    typename std::conditional<MF16, f32x4, f32x16>::type acc[TD][TP];
+    conv_tile_loop<BD, BP, WD, WP, MODE, PREF, PRE, VID, MF16, HWM, CPB, FUSE, BF3>(p, cd0, px0, nwg, smem, probe, probe_slot, prio_arg, acc, pre0, pregw);
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wd = wave / WP, wpx = wave % WP;
+    const int l31 = MF16 ? (lane & 15) : (lane & 31), lk = MF16 ? (lane >> 4) : (lane >> 5);
+    const int HWg = p.Hg * p.Wg;
+    const int64_t P = (int64_t)p.N * HWg;
+#define I2V_FROW(r) (MF16 ? 4 * lk + (r) : ((r) & 3) + 8 * ((r) >> 2) + 4 * lk)
     // ---- epilogue: shift, addends, ReLU, gradient gate, NCHW store ----
     const int HoWo = p.Ho * p.Wo;
     if (p.vec_epilogue) {

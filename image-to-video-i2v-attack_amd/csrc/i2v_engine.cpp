@@ -478,6 +478,18 @@ extern "C" int i2v_net_fusion_info(i2v_handle h, int net, int32_t out[4]) {
     return 0;
 }
 
+extern "C" int i2v_net_scpair_info(i2v_handle h, int net, int32_t out[4]) {
+    Net* n = get_net(h, net); if (!n) return 1;
+    if (!n->planned || !out) return fail("i2v_net_scpair_info: net not planned");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    int k = 0;
+    for (const std::vector<Launch>* L : {&n->fwd, &n->bwd}) {
+        for (const Launch& l : *L) { out[k] += l.sc_ok ? 1 : 0; out[2 + k] += (l.sc_ok && l.sc_b[0]) ? 1 : 0; }
+        ++k;
+    }
+    return 0;
+}
+
 extern "C" size_t i2v_net_workspace_bytes(i2v_handle h, int net) {
     Net* n = get_net(h, net); if (!n) return 0;
     return n->arena_floats * sizeof(float) + n->weight_bytes;

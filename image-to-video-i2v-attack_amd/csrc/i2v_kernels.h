@@ -49,6 +49,26 @@ inline bool i2v_conv_pair_fusable(const I2VConvParams& a, const I2VConvParams& b
     return true;
 }
 int k_conv_fused(const I2VConvParams& a, const I2VConvParams& b, int halo, i2v_stream_t s);
+// Shortcut pair (i2v_conv_scpair.hip; on a backend without it -- no -DI2V_HAVE_SCPAIR -- the two launches one after the other,
+// i2v_scpair_host.h): `a` a 1x1 convolution whose output is nothing but `b`'s plain addend (a first bottleneck's projection shortcut
+// under its expand convolution; backward, one input gradient under the next), `b` the pointwise convolution that adds it.  One launch
+// runs a's K loop and b's K loop for the same 64x64 output tile, keeps y = acc_a + a.shift on chip and hands it to b's epilogue in
+// add0's place: the same two fmaf chains and the same additions in the same order as the two launches, and a.dst is never written.
+// The structural rule, shared by every backend, on PREPPED parameters (conv_prep: vec_epilogue and temporal derived):
+inline bool i2v_conv_scpair_ok(const I2VConvParams& a, const I2VConvParams& b) {
+    for (const I2VConvParams* q : {&a, &b})
+        if (q->temporal || q->quad || q->pre_scale || q->gate_scale || q->blk > 1 || q->blkt > 1 || q->bf3) return false;
+    // a: ONE tap per source channel -- pointwise, or a tap-uniform packing with K == Cs (the 1x1 of a strided shortcut; the loop follows the
+    // k-table, wherever that tap lies) -- and an epilogue that is `+ shift` alone
+    if (!(a.pointwise || (a.tap_uniform && a.K == a.Cs && a.Kpad == a.K))) return false;
+    if (a.relu || a.mask || a.gate || a.gate_out || a.add0 || a.add1) return false;
+    if (a.osh != 1 || a.osw != 1 || a.oh0 || a.ow0 || a.Hg != a.Ho || a.Wg != a.Wo) return false;
+    if (!b.pointwise || !b.vec_epilogue) return false;
+    if (a.N != b.N || a.Hg != b.Hg || a.Wg != b.Wg || a.Cd != b.Cd || a.Ho != b.Ho || a.Wo != b.Wo) return false;
+    return a.dst && b.add0 == a.dst && b.add0_stride == 1 && b.add0_nstride == a.dst_nstride;
+}
+int k_conv_scpair_ok(const I2VConvParams& a, const I2VConvParams& b);
+int k_conv_scpair(const I2VConvParams& a, const I2VConvParams& b, i2v_stream_t s);
 int k_conv_candidates(const I2VConvParams& p, int* out);
 // Fused fast-pathway block (I2VFastBlockParams; i2v_fastblock.hip): `a`, `b` and -- forward -- `c` (+ `d`, the projection shortcut, or
 // null) are the PREPPED parameters of the separate launches it replaces; backward: c == d == null.  The structural rule below is shared

@@ -117,6 +117,13 @@ struct Launch {
     int node = -1;                 // conv launches: the graph node they belong to
     int fb_ok = 0;
     int fb_b[4] = {0, 0, 0, 0};
+    // Shortcut pair (k_conv_scpair): this 1x1 launch's output is nothing but the plain addend of the pointwise launch sc_ok entries
+    // further down its list, it is independent of what lies between, and nothing else touches that memory (mark_fusable).  Where
+    // sc_b[bucket] is set (1 without the autotuner; with it, where the pair measured faster than the two launches) the executor passes
+    // over this launch and runs the pair as ONE kernel in its consumer's place: the intermediate is never stored.
+    int sc_ok = 0;
+    int sc_b[4] = {0, 0, 0, 0};
+    bool sc_private = false;       // nothing but the consumer ever touches the intermediate's memory (a tensor's own view, not scratch that is overwritten later)
     // Launch overlap (mark_overlap, round 6): a convolution launch that does not depend on its predecessors back to launch ov_after
     // (-1: on nothing in its list) may run on the net's SIDE stream, issued right after launch ov_after, while the main stream goes on;
     // ov_join is the first later launch that touches what it writes or reads (list size: none in this list) and waits for it.
@@ -212,6 +219,9 @@ int conv_run(const Launch& l, int frames, const float* x, float* gx, int accumul
 bool fused_fits(const Launch& a, const Launch& b, int frames);
 int fused_run(const Launch& a, const Launch& b, int frames, const float* x, int halo, i2v_stream_t s);
 int fast_run(const std::vector<Launch>& L, size_t li, int frames, const float* x, i2v_stream_t s);
+bool sc_pair_ok(const Launch& a, const Launch& b);            // the structural rule on the prepped parameters of two launches of one list
+bool sc_fits(const Launch& a, const Launch& b, int frames);
+int sc_run(const Launch& a, const Launch& b, int frames, i2v_stream_t s);
 extern long long g_overlap_launches;        // launches issued on a side stream (mark_overlap): a relaxed counter, diagnostics only
 
 #pragma GCC visibility pop

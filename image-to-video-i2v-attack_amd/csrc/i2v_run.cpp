@@ -3,6 +3,9 @@
 #ifndef I2V_HAVE_SE
 #include "i2v_se_host.h"         // (the host simulation's one-file build: the squeeze-and-excitation node as scalar code)
 #endif
+#ifndef I2V_HAVE_SCPAIR
+#include "i2v_scpair_host.h"     // (... and the shortcut pair as its two launches)
+#endif
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -51,6 +54,37 @@ int fused_run(const Launch& a, const Launch& b, int frames, const float* x, int 
         p->src_span_bytes = (int32_t)(((int64_t)frames * p->Ts / p->Tg - 1) * p->src_nstride * 4 + (int64_t)p->Cs * p->Hs * p->Ws * 4);
     }
     CHECK_BE(k_conv_fused(pa, pb, halo, s));
+    return 0;
+}
+
+// The shortcut pair: `a` (a 1x1 convolution) and `b` (the pointwise convolution whose plain addend is a's output) as ONE launch that
+// never stores that output; only for pairs mark_fusable admitted.  A pair whose sources would have to be sliced runs as two launches.
+static void sc_prep(const Launch& a, const Launch& b, int frames, I2VConvParams* pa, I2VConvParams* pb) {
+    *pa = conv_prep(a, nullptr, nullptr, 0); *pb = conv_prep(b, nullptr, nullptr, 0);
+    for (I2VConvParams* p : {pa, pb}) {
+        p->N = frames;
+        p->src_span_bytes = (int32_t)(((int64_t)frames * p->Ts / p->Tg - 1) * p->src_nstride * 4 + (int64_t)p->Cs * p->Hs * p->Ws * 4);
+    }
+}
+bool sc_pair_ok(const Launch& a, const Launch& b) {
+    if (a.kind != L_CONV || b.kind != L_CONV || a.src_is_input || b.src_is_input || a.T != b.T) return false;
+    I2VConvParams pa, pb;
+    sc_prep(a, b, a.T, &pa, &pb);
+#ifdef I2V_HAVE_SCPAIR
+    return k_conv_scpair_ok(pa, pb) != 0;
+#else
+    return scpair_host::ok(pa, pb) != 0;
+#endif
+}
+bool sc_fits(const Launch& a, const Launch& b, int frames) { return fused_fits(a, b, frames); }
+int sc_run(const Launch& a, const Launch& b, int frames, i2v_stream_t s) {
+    I2VConvParams pa, pb;
+    sc_prep(a, b, frames, &pa, &pb);
+#ifdef I2V_HAVE_SCPAIR
+    CHECK_BE(k_conv_scpair(pa, pb, s));
+#else
+    if (scpair_host::run(pa, pb, s)) return fail("shortcut pair: the two launches do not form a pair");
+#endif
     return 0;
 }
 
@@ -120,9 +154,11 @@ static TimedLaunch* timing_begin(i2v_ctx* h, int kind, double flops, i2v_stream_
 
 // What the timing instrumentation records about a launch -- or about the fused group it leads: `fb` launches of L from li as one fused
 // fast-pathway block, `fuse`: li and li + 1 as one fused pair.  Only computed while launches are being timed.
-static double launch_flops(const std::vector<Launch>& L, size_t li, int fb, int fuse, int frames, int clips) {
+// `sc`: the launch leads a shortcut pair -- L[sc] (earlier in the list) runs inside it; -1: none.
+static double launch_flops(const std::vector<Launch>& L, size_t li, int fb, int fuse, int sc, int frames, int clips) {
     const Launch& l = L[li];
     double flops = 0.0;
+    if (sc >= 0) return 2.0 * frames * l.conv.Hg * l.conv.Wg * ((double)l.conv.Cd * l.conv.K + (double)L[sc].conv.Cd * L[sc].conv.K);
     if (fb) { for (int j = 0; j < fb; ++j) { const Launch& m = L[li + j]; flops += m.alg_flops_per_frame > 0 ? m.alg_flops_per_frame * frames : 2.0 * frames * m.conv.Hg * m.conv.Wg * (double)m.conv.Cd * m.conv.K; } }
     else if ((l.kind == L_CONV || l.kind == L_GCONV || l.kind == L_DWCONV) && l.alg_flops_per_frame > 0) flops = l.alg_flops_per_frame * frames;     // quad-row packings pad K; a grouped node counts its real products
     else if (l.kind == L_CONV) flops = 2.0 * frames * l.conv.Hg * l.conv.Wg * ((double)l.conv.Cd * l.conv.K + (fuse ? (double)L[li + 1].conv.Cd * L[li + 1].conv.K : 0.0));
@@ -147,7 +183,7 @@ static int launch_timing_kind(const Launch& l, bool backward_pass) {
 
 // ALGORITHMIC bytes of a convolution launch (or the fused group it leads): every operand once -- the source view, the packed weights,
 // the output, each epilogue addend, and the ReLU gate (fp32 activation, or 1 bit per element) -- whatever the tiling re-reads
-static double launch_bytes(const std::vector<Launch>& L, size_t li, int fb, int fuse, int frames, int clips, int accumulate) {
+static double launch_bytes(const std::vector<Launch>& L, size_t li, int fb, int fuse, int sc, int frames, int clips, int accumulate) {
     const Launch& l = L[li];
     const I2VConvParams& q = l.conv;
     const double out = (double)frames * q.Hg * q.Wg * q.Cd;
@@ -179,6 +215,10 @@ static double launch_bytes(const std::vector<Launch>& L, size_t li, int fb, int 
         if (r.gate) b += out2 / 8.0;
         if (r.gate_out) b += out2 / 8.0;
     }
+    if (sc >= 0) {    // + the shortcut half: its source and weights; its output, this launch's add0, is neither written nor read
+        const I2VConvParams& r = L[sc].conv;
+        b += 4.0 * ((double)clips * r.Ts * r.Cs * r.Hs * r.Ws + (double)r.K * r.Cd) - 4.0 * out;
+    }
     return b;
 }
 
@@ -194,10 +234,10 @@ struct ListTiming {
     TimedLaunch* seg = nullptr;         // segment mode: the open segment
 
     // the entry whose stop event is due right behind the launch (mode 1), or null
-    TimedLaunch* open(const std::vector<Launch>& L, size_t li, int fb, int fuse, int frames, int clips, int accumulate) {
+    TimedLaunch* open(const std::vector<Launch>& L, size_t li, int fb, int fuse, int sc, int frames, int clips, int accumulate) {
         const Launch& l = L[li];
         const int kind = launch_timing_kind(l, backward_pass);
-        const double flops = launch_flops(L, li, fb, fuse, frames, clips);
+        const double flops = launch_flops(L, li, fb, fuse, sc, frames, clips);
         const bool conv = l.kind == L_CONV || l.kind == L_IMGGRAD || l.kind == L_GCONV || l.kind == L_DWCONV;
         if (h->timing == 2) {
             if (!seg || seg->kind != kind) {
@@ -205,13 +245,13 @@ struct ListTiming {
                 seg = timing_begin(h, kind, 0.0, s, seg);
                 if (seg) seg->count = 0;
             }
-            if (seg) { seg->flops += flops; seg->count += 1; if (conv) seg->bytes += launch_bytes(L, li, fb, fuse, frames, clips, accumulate); else seg->bytes += l.se_bytes_per_frame * frames; }
+            if (seg) { seg->flops += flops; seg->count += 1; if (conv) seg->bytes += launch_bytes(L, li, fb, fuse, sc, frames, clips, accumulate); else seg->bytes += l.se_bytes_per_frame * frames; }
             return prev = nullptr;
         }
         TimedLaunch* const tl = prev = timing_begin(h, kind, flops, s, prev);
         if (tl && conv) {
             tl->Cd = l.conv.Cd; tl->K = l.conv.K; tl->HWg = l.conv.Hg * l.conv.Wg; tl->frames = frames; tl->pw = l.conv.pointwise;
-            tl->bytes = launch_bytes(L, li, fb, fuse, frames, clips, accumulate);
+            tl->bytes = launch_bytes(L, li, fb, fuse, sc, frames, clips, accumulate);
         }
         if (tl && l.kind == L_AGEMM) {                  // (dump fields: channels, reduction length, output columns, 10 + product form)
             const I2VAttnGemm& q = l.ag;
@@ -278,23 +318,42 @@ static int run_list(i2v_ctx* h, Net& n, std::vector<Launch>& L, int in_frames, c
     const bool overlap = !h->timing && n.side && !side.at.empty() && in_frames <= n.ov_max_frames;
     if (overlap) n.ov_used = 0;
     if (overlap && side.issue(-1)) return 1;
+    // does launch k lead a fused group (pair or fast-pathway block) at this call's size?
+    auto leads_group = [&](size_t k) { return L[k].kind == L_CONV && ((L[k].fuse_ok && L[k].fuse_b[bucket]) || (L[k].fb_ok && L[k].fb_b[bucket])); };
+    int sc_from = -1; size_t sc_at = 0;                  // a deferred shortcut launch and the consumer it runs with
     for (size_t li = 0; li < L.size(); ++li) {
         Launch& l = L[li];
         const int frames = clips * l.T;                  // frames this launch iterates over
         const size_t li0 = li;
         if (overlap && l.ov_after != -2) continue;       // hoisted: already issued on the side stream
+        // the shortcut of a pair (mark_fusable / autotune): passed over here, it runs inside ONE kernel with its consumer sc_ok entries on
+        // -- unless a launch in between leads a fused group of its own, or launches are being hoisted to the side stream (whose issue
+        // points are list positions)
+        if (l.kind == L_CONV && l.sc_ok && l.sc_b[bucket] && !overlap && sc_from < 0 && li + l.sc_ok < L.size() && frames * l.conv.Hg * l.conv.Wg > 0 &&
+            sc_fits(l, L[li + l.sc_ok], frames)) {
+            bool clear = !leads_group(li);
+            for (size_t k = li + 1; k <= li + l.sc_ok && clear; ++k) clear = !leads_group(k);
+            if (clear) { sc_from = (int)li; sc_at = li + l.sc_ok; continue; }
+        }
+        const int sc = (sc_from >= 0 && li == sc_at) ? sc_from : -1;
+        if (sc >= 0) sc_from = -1;
         // this 3x3 launch and the pointwise launch behind it as ONE kernel (mark_fusable / autotune): the next entry is skipped
         const int fuse = (l.kind == L_CONV && l.fuse_ok && li + 1 < L.size() && frames * l.conv.Hg * l.conv.Wg > 0 && fused_fits(l, L[li + 1], frames))
                              ? l.fuse_b[bucket] : 0;
         // this launch and the next fb_ok - 1 as ONE fused fast-pathway block (mark_fusable / autotune): those entries are skipped
         const int fb = (l.kind == L_CONV && l.fb_ok && li + l.fb_ok <= L.size() && frames * l.conv.Hg * l.conv.Wg > 0) ? l.fb_b[bucket] * l.fb_ok : 0;
         if (overlap && side.join((int)li + (fb ? fb - 1 : fuse ? 1 : 0))) return 1;
-        TimedLaunch* const tl = h->timing ? timing.open(L, li, fb, fuse, frames, clips, accumulate) : nullptr;
+        TimedLaunch* const tl = h->timing ? timing.open(L, li, fb, fuse, sc, frames, clips, accumulate) : nullptr;
         struct Stop { TimedLaunch* t; i2v_stream_t s; ~Stop() { if (t) be_event_record(t->stop, s); } } stop{tl, s};
         switch (l.kind) {
             case L_CONV:
             case L_IMGGRAD: {
                 if (frames * l.conv.Hg * l.conv.Wg == 0) break;
+                if (sc >= 0) {      // (the consumer's tuned configuration carries the streaming-store bit the pair was timed with)
+                    if (l.cfg_b[bucket]) l.conv.cfg = l.cfg_b[bucket];
+                    if (sc_run(L[sc], l, frames, s)) return 1;
+                    break;
+                }
                 if (fuse) { if (fused_run(l, L[li + 1], frames, x, fuse == 2, s)) return 1; ++li; break; }
                 if (fb) {
                     const int rc = fast_run(L, li, frames, x, s);
@@ -489,6 +548,21 @@ extern "C" int i2v_net_read_tensor(i2v_handle h, int net, int tensor, int which,
                     return fail("i2v_net_read_tensor: this tensor is an intermediate of a fused fast-pathway block and is never stored "
                                 "(plan with I2V_FASTBLOCK=0 to read it)");
             }
+        }
+    // ... and the output of a shortcut that runs inside a pair (k_conv_scpair).  The forward one is produced on demand -- the launch
+    // itself, from its source as the forward pass left it: exactly the values the separate launch stores -- because callers read whole
+    // networks back activation by activation; a gradient view is refused like the others.
+    for (const std::vector<Launch>* L : {&n->fwd, &n->bwd})
+        for (const Launch& l : *L) {
+            if (l.kind != L_CONV || !l.sc_ok || !(l.sc_b[0] | l.sc_b[1] | l.sc_b[2] | l.sc_b[3])) continue;
+            if ((&l)[l.sc_ok].conv.dst == l.conv.dst) continue;       // (added in place: the view holds the consumer's result)
+            const float* lo = l.conv.dst; const float* hi = lo + (int64_t)(n->maxN / n->Tin() * std::max(1, l.conv.To) - 1) * l.conv.dst_nstride + (int64_t)l.conv.Cd * l.conv.Ho * l.conv.Wo;
+            const float* vlo = v.p; const float* vhi = v.p + (int64_t)(frames - 1) * v.nstride + (int64_t)v.C * v.H * v.W;
+            if (!(vlo < hi && lo < vhi)) continue;
+            if (L == &n->bwd || which != 0 || !l.sc_private)
+                return fail("i2v_net_read_tensor: this tensor is the shortcut output of a fused first bottleneck (shortcut pair) and is never stored "
+                            "(plan with I2V_SCPAIR=0 to read it)");
+            if (conv_run(l, frames / std::max(1, v.T) * l.T, nullptr, nullptr, 0, stream)) return 1;
         }
     size_t row = (size_t)v.C * v.H * v.W * sizeof(float);
     CHECK_BE(be_d2d_2d(out, row, v.p, (size_t)v.nstride * sizeof(float), row, frames, stream));

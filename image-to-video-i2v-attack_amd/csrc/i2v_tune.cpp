@@ -163,6 +163,59 @@ void mark_fusable(Net& n) {
                     if ((*L)[i].fb_ok) fprintf(stderr, "[i2v fastblock] %s launch %zu: group of %d (Cs %d -> %d mid channels, %dx%d)\n", L == &n.fwd ? "fwd" : "bwd", i, (*L)[i].fb_ok,
                                                (*L)[i].conv.Cs, (*L)[i].conv.Cd, (*L)[i].conv.Hg, (*L)[i].conv.Wg);
     }
+    // ---- shortcut pairs (k_conv_scpair): a 1x1 launch whose output is nothing but the plain addend of a pointwise launch further down ----
+    // Forward, a first bottleneck's projection shortcut under its expand convolution; backward, wherever one input gradient is only the
+    // next one's addend on the same grid (the stride-1 first bottleneck: the shortcut's input gradient under conv1's).  The pair never
+    // stores the intermediate, so nothing -- launch of either list, hook, in-place gain -- may look at that memory while the two launches
+    // would have kept a's output in it (spelled out below).  The shortcut need not be adjacent to its consumer: the executor runs it in the consumer's place, which is the same
+    // schedule with the shortcut moved down -- admitted only if it is independent of every launch it passes (the test of the swap above).
+    {
+        const bool sc_off = [] { const char* e = getenv("I2V_SCPAIR"); return e && e[0] == '0'; }();      // (read per plan: tests and A/B runs compare both)
+        for (std::vector<Launch>* L : {&n.fwd, &n.bwd}) {
+            for (Launch& l : *L) { l.sc_ok = 0; l.sc_private = false; for (int bk = 0; bk < 4; ++bk) l.sc_b[bk] = 0; }
+            for (size_t i = 0; !sc_off && i + 1 < L->size(); ++i) {
+                Launch& a = (*L)[i];
+                if (a.kind != L_CONV || a.src_is_input || a.conv.add0 || a.conv.relu) continue;
+                for (size_t j = i + 1; j < L->size() && j <= i + 3; ++j) {
+                    const Launch& b = (*L)[j];
+                    if (b.kind != L_CONV || b.conv.add0 != a.conv.dst) continue;
+                    if (!sc_pair_ok(a, b)) break;
+                    const Range w = dst_of(a);
+                    // The pair differs from the two launches in what `w` holds from a's place in the list on, until something overwrites
+                    // it: nothing may look at it there.  Not the launches passed; not b through another operand; after b, in list order,
+                    // no launch may read it before one has overwritten all of it (b itself, where an input gradient adds IN PLACE; the
+                    // next user of a scratch view) -- and while it is live no hook and no launch of the other list may touch it at all.
+                    auto conv_kind = [](const Launch& c) { return c.kind == L_CONV || c.kind == L_IMGGRAD || c.kind == L_GCONV || c.kind == L_DWCONV; };
+                    auto reads = [&](const Launch& c) { return touches(c, w, false, conv_kind(c)); };
+                    auto covers = [&](const Launch& c) { return conv_kind(c) && c.conv.dst && dst_of(c).first <= w.first && dst_of(c).second >= w.second; };
+                    Launch b_rest = b; b_rest.conv.add0 = nullptr;          // b without the operand that legitimately is the intermediate
+                    bool other = reads(b_rest), dead = covers(b);
+                    for (size_t k = i + 1; k < j && !other; ++k) other |= touches((*L)[k], w, false, false);
+                    for (size_t k = j + 1; k < L->size() && !other && !dead; ++k) {
+                        if (reads((*L)[k])) other = true;
+                        else if (covers((*L)[k])) dead = true;
+                        else other = touches((*L)[k], w, false, false);
+                    }
+                    if (!dead) {
+                        for (auto& hk : hooked) other |= meet(hk, w);
+                        for (const Launch& c : (L == &n.fwd ? n.bwd : n.fwd)) other = other || touches(c, w, false, false);
+                    }
+                    bool dep = false;                                       // ... and of the launches it passes: they write nothing it reads
+                    for (size_t k = i + 1; k < j && !dep; ++k) {
+                        const Launch& m = (*L)[k];
+                        const I2VConvParams& pa = a.conv; const I2VConvParams& pm = m.conv;
+                        dep = (m.kind != L_CONV && m.kind != L_GCONV && m.kind != L_DWCONV) || m.src_is_input || touches(a, dst_of(m), false, false) ||
+                              (pm.gate_out && (pm.gate_out == pa.gate || pm.gate_out == pa.gate_out)) || (pa.gate_out && (pa.gate_out == pm.gate || pa.gate_out == pm.gate_out));
+                    }
+                    if (!other && !dep) { a.sc_ok = (int)(j - i); a.sc_private = !dead; for (int bk = 0; bk < 4; ++bk) a.sc_b[bk] = 1; }
+                    if (getenv("I2V_FUSE_DEBUG"))
+                        fprintf(stderr, "[i2v scpair] %s launches %zu + %zu (K %d + %d -> Cd %d, %dx%d): other_reader=%d dependent=%d\n", L == &n.fwd ? "fwd" : "bwd", i, j,
+                                a.conv.K, b.conv.K, b.conv.Cd, b.conv.Hg, b.conv.Wg, (int)other, (int)dep);
+                    break;
+                }
+            }
+        }
+    }
     // without the autotuner (I2V_AUTOTUNE=0: tests, tools) a pair is fused only on request: I2V_FORCE_FUSE = 1 (plain) / 2 (halo where it applies)
     const char* force = getenv("I2V_FORCE_FUSE");
     const int f = force ? atoi(force) : 0;
@@ -448,6 +501,36 @@ int tune_pairs(Net& n, Probe& pr, int max_clips) {
     return 0;
 }
 
+// Shortcut pairs, per batch bucket: the two launches on their tuned tiles against the pair as one kernel, three timed runs each; the
+// faster stays.  (No handicap for the single launch as in tune_pairs: the pair removes memory traffic, it is not a wash that only a
+// tool's per-dispatch overhead decides.)
+int tune_scpairs(Net& n, Probe& pr, int max_clips) {
+    for (std::vector<Launch>* L : {&n.fwd, &n.bwd})
+        for (size_t i = 0; i < L->size(); ++i) {
+            Launch& a = (*L)[i];
+            if (!a.sc_ok || i + a.sc_ok >= L->size()) continue;
+            Launch& b = (*L)[i + a.sc_ok];
+            const int rc = for_each_bucket(max_clips, a.conv.Tg, [&](int bk, int lf) -> int {
+                if (lf * a.conv.Hg * a.conv.Wg == 0 || !sc_fits(a, b, lf)) return 0;
+                const int ca = a.conv.cfg, cb = b.conv.cfg;
+                if (a.cfg_b[bk]) a.conv.cfg = a.cfg_b[bk];
+                if (b.cfg_b[bk]) b.conv.cfg = b.cfg_b[bk];
+                float t_sep = 0.f, t_pair = 0.f;
+                const int rc = pr.time([&] { return conv_run(a, lf, pr.x, pr.gx, 0, nullptr) || conv_run(b, lf, pr.x, pr.gx, 0, nullptr); }, 3, &t_sep) ||
+                               pr.time([&] { return sc_run(a, b, lf, nullptr); }, 3, &t_pair);
+                a.conv.cfg = ca; b.conv.cfg = cb;
+                if (rc) return 1;
+                a.sc_b[bk] = t_pair < t_sep ? 1 : 0;
+                if (getenv("I2V_FUSE_DEBUG"))
+                    fprintf(stderr, "[i2v scpair] %s launches %zu + %zu (K %d + %d -> Cd %d, %dx%d) at %d frames: separate %.1f us, pair %.1f us -> %s\n", list_name(n, L), i,
+                            i + a.sc_ok, a.conv.K, b.conv.K, b.conv.Cd, b.conv.Hg, b.conv.Wg, lf, 1e3f * t_sep, 1e3f * t_pair, a.sc_b[bk] ? "pair" : "separate");
+                return 0;
+            });
+            if (rc) return 1;
+        }
+    return 0;
+}
+
 }  // namespace
 
 // Plan-time autotuning ("measure, don't guess"): every convolution launch of both passes is timed with each
@@ -465,6 +548,7 @@ int autotune(Net& n) {
         const bool on_device = strncmp(be_name(), "hip", 3) == 0;
         rc = tune_tiles(n, pr, max_clips);
         if (!rc && on_device) rc = tune_fastblocks(n, pr, max_clips);
+        if (!rc && on_device) rc = tune_scpairs(n, pr, max_clips);
         // Pairs are opt-in (I2V_FUSE=1) since round 5: the fused kernel loses 7-35 % on every pair at the headline size and wins 1-2 % on three
         // pairs at 32 frames (profiles/r4_fuse_pairs.txt) -- not worth up to 9 probe launches per pair and bucket in every plan, nor a plan that
         // depends on the process environment (a profiling tool's per-dispatch overhead flatters the single launch).

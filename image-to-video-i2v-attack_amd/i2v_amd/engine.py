@@ -481,6 +481,13 @@ class Net:
         _lib.check(self.eng.capi, self.eng.capi.i2v_net_fusion_info(self.eng.h, self.id, out))
         return tuple(int(v) for v in out)
 
+    def scpair_info(self):
+        """(admitted forward pairs, admitted backward pairs, forward pairs run as one launch, backward pairs run as one launch) of the
+        planned launch lists (`i2v_net_scpair_info`): a projection shortcut + the expand convolution that adds it as one launch."""
+        out = (C.c_int32 * 4)()
+        _lib.check(self.eng.capi, self.eng.capi.i2v_net_scpair_info(self.eng.h, self.id, out))
+        return tuple(int(v) for v in out)
+
     def forward(self, x: torch.Tensor):
         _lib.check(self.eng.capi, self.eng.capi.i2v_net_forward(self.eng.h, self.id, _ptr(x, self.eng), x.shape[0], self.eng.stream()))
 

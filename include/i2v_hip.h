@@ -164,6 +164,12 @@ size_t i2v_net_workspace_bytes(i2v_handle h, int net);
  * gradients): out[0..1] = pairs that qualify in the forward / backward launch list, out[2..3] = pairs the plan-time autotuner
  * (or I2V_FORCE_FUSE) fused at the planned batch size.  Diagnostics; results never depend on it. */
 int i2v_net_fusion_info(i2v_handle h, int net, int32_t out[4]);
+/* Shortcut pairs of a planned net (a 1x1 convolution whose output is nothing but the plain addend of a pointwise convolution -- a first
+ * bottleneck's projection shortcut under its expand convolution, `identity = self.downsample(x); out += identity` of
+ * `torchvision.models.resnet.Bottleneck.forward`; backward, one input gradient under the next -- as ONE launch that never stores that
+ * output): out[0..1] = pairs the planner admits in the forward / backward launch list (none with I2V_SCPAIR=0 in the environment
+ * while planning), out[2..3] = pairs that run as one launch at the planned batch size.  Diagnostics; results never depend on it. */
+int i2v_net_scpair_info(i2v_handle h, int net, int32_t out[4]);
 
 /* ---- backbone execution ----------------------------------------------------------------
  * `_ = self.model(x)` up to the deepest hook (image_attacks.py:318,334).  x: (frames,3,H,W). */
