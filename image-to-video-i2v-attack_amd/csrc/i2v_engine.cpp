@@ -459,6 +459,7 @@ extern "C" int i2v_net_plan(i2v_handle h, int net, const int* hook_tensors, int 
     mark_fusable(n);
     if (autotune(n)) return 1;
     mark_overlap(n);
+    record_unstored(n);
     // planning works on the null stream (uploads, arena clears, tuning probes); the caller may execute the net on any
     // stream, including non-blocking ones that do not order against it
     CHECK_BE(be_stream_sync(nullptr));

@@ -7,9 +7,11 @@
 
 #include <stdint.h>
 
+#include <algorithm>
 #include <deque>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace eng {
@@ -89,7 +91,7 @@ enum Kind { L_CONV, L_IMGGRAD, L_POOLF, L_POOLB, L_ADDMASK, L_AVGF, L_AVGB, L_ME
 // 9 x group width) for the address-range analyses and the timing records, which treat it as the convolution launch it is
 // L_DWCONV: a depthwise node on k_dwconv -- `dc` is what the kernel gets, `conv` mirrors the views in the same way (K = k k)
 // L_SE_*: the three launches of a squeeze-and-excitation node per pass (`se`; se.backward tells the pass).  No pass that matches on
-// L_CONV sees them; the address-range analyses of i2v_tune.cpp read their views (x, g, r, dst, the node's vectors) from `se`
+// L_CONV sees them; the address-range analysis (access_of, i2v_tune.cpp) reads their views (x, g, r, dst, the node's vectors) from `se`
 struct Launch {
     Kind kind;
     I2VConvParams conv; I2VPoolParams pool; I2VAddMaskParams am; I2VGConvParams gc; I2VDwConvParams dc; I2VSeParams se;
@@ -138,6 +140,43 @@ inline int cfg_bucket(int clips, int max_clips) {
 
 struct Addend { const float* p; int64_t nstride; int stride, H, W; };
 
+// Address-range analysis: what the plan-time passes that fuse, move or hoist launches ask about memory.  A range is [first, second) in
+// BYTES; a null operand has none and meets nothing.  extent: `frames` frames `stride` bytes apart, the last one `plane` bytes long (a
+// view of a wider buffer ends with its own channels, not with the frame stride).
+typedef std::pair<const char*, const char*> Range;
+inline Range extent(const void* p, int64_t frames, int64_t stride, int64_t plane) {
+    const char* c = (const char*)p;
+    return c ? Range(c, c + (frames > 0 ? (frames - 1) * stride : 0) + std::max<int64_t>(plane, 1)) : Range(nullptr, nullptr);
+}
+inline bool meets(const Range& a, const Range& b) { return a.first && b.first && a.first < b.second && b.first < a.second; }
+// What ONE launch reads and writes at the planned clip count (access_of, i2v_tune.cpp: the only place that lists the operands of each
+// Kind).  barrier: not analysed (attention launches address whole matrices) -- reads, writes and conflicts with everything.
+struct Access { std::vector<Range> r, w; bool barrier = false; };
+inline int reads(const Access& a, const Range& x) {         // through how many operands (a consumer reads its producer's output through ONE)
+    int c = a.barrier ? 1 : 0;
+    for (const Range& q : a.r) c += meets(q, x) ? 1 : 0;
+    return c;
+}
+inline bool writes(const Access& a, const Range& x) {
+    for (const Range& q : a.w) if (meets(q, x)) return true;
+    return a.barrier;
+}
+inline bool covers(const Access& a, const Range& x) {       // one output overwrites ALL of x: what x held is dead
+    for (const Range& q : a.w) if (x.first && q.first <= x.first && q.second >= x.second) return true;
+    return false;
+}
+inline bool conflict(const Access& a, const Access& b) {    // one writes what the other reads or writes: they may neither swap nor overlap
+    if (a.barrier || b.barrier) return true;
+    for (const Range& x : a.w) if (reads(b, x) || writes(b, x)) return true;
+    for (const Range& x : b.w) if (reads(a, x)) return true;
+    return false;
+}
+
+// A range that a planned group never stores (record_unstored): reading it back would hand out stale arena contents.
+// group: 0 the intermediate of a fused 3x3 -> pointwise pair, 1 an intermediate of a fused fast-pathway block, 2 the output of a shortcut
+// that runs inside a shortcut pair; remake: the launch of Net::fwd that reproduces a group-2 range on demand, -1: none (refused)
+struct Unstored { Range bytes; int group; int remake; };
+
 struct Net {
     std::vector<Buffer> bufs; std::vector<Tensor> tens; std::vector<Node> nodes;
     int input = -1; std::vector<int> hooks; int maxN = 0; bool planned = false;
@@ -153,6 +192,7 @@ struct Net {
     // launches to issue right after main launch p (index p + 1; index 0: at the start of the list)
     i2v_stream_t side = nullptr; std::vector<void*> ov_ev; size_t ov_used = 0;
     std::vector<std::vector<int>> ov_at[2]; int ov_max_frames = 0;
+    std::vector<Unstored> unstored;         // what i2v_net_read_tensor cannot simply copy out (record_unstored, at the end of the plan)
 };
 
 // `chain`: the launch follows the previous timed launch back to back on the same stream (same launch list), so its
@@ -208,10 +248,14 @@ struct View { float* p; int64_t nstride; int C, H, W; int T = 1; };
 View view_of(Net& n, int t, bool grad);
 bool plan_pass(Net& n, bool dry, size_t off, size_t N, size_t* end, std::string* err);
 
-// i2v_tune.cpp: what may run fused or on the side stream, and which tile configuration each convolution launch runs
+// i2v_tune.cpp: what may run fused or on the side stream, and which tile configuration each convolution launch runs -- the first two
+// decided from access_of's read and write sets of every launch (`clips`: the planned clip count)
+Access access_of(const Launch& l, int64_t clips);
+Range conv_dst(const Launch& l, int64_t clips);        // the output of a convolution launch, as access_of lists it
 void mark_fusable(Net& n);
 void mark_overlap(Net& n);
 int autotune(Net& n);
+void record_unstored(Net& n);       // Net::unstored from the finished marks and the autotuner's choices
 
 // i2v_run.cpp: one launch (or fused group) of a planned list, as the executor and the autotuner's probes issue it
 I2VConvParams conv_prep(const Launch& l, const float* x, float* gx, int accumulate);

@@ -37,22 +37,19 @@ I2VConvParams conv_prep(const Launch& l, const float* x, float* gx, int accumula
     return p;
 }
 
+// what a launch over `frames` grid frames addresses of its source, first byte to last (32-bit buffer offsets: it has to stay < 2 GiB)
+static int64_t src_span_bytes(const I2VConvParams& p, int frames) {
+    return ((int64_t)frames * p.Ts / p.Tg - 1) * p.src_nstride * 4 + (int64_t)p.Cs * p.Hs * p.Ws * 4;
+}
+
 // The fused pair: `a` (3x3) and `b` (the pointwise convolution over a's output) as ONE launch; only for pairs mark_fusable admitted.
 // A pair whose source would have to be sliced (>= 2 GiB spans) is not fused (the caller falls back to two launches).
 bool fused_fits(const Launch& a, const Launch& b, int frames) {
-    for (const Launch* l : {&a, &b}) {
-        const I2VConvParams& p = l->conv;
-        const int64_t span = ((int64_t)frames * p.Ts / p.Tg - 1) * p.src_nstride * 4 + (int64_t)p.Cs * p.Hs * p.Ws * 4;
-        if (span >= (1ll << 31)) return false;
-    }
-    return true;
+    return src_span_bytes(a.conv, frames) < (1ll << 31) && src_span_bytes(b.conv, frames) < (1ll << 31);
 }
 int fused_run(const Launch& a, const Launch& b, int frames, const float* x, int halo, i2v_stream_t s) {
     I2VConvParams pa = conv_prep(a, x, nullptr, 0), pb = conv_prep(b, x, nullptr, 0);
-    for (I2VConvParams* p : {&pa, &pb}) {
-        p->N = frames;
-        p->src_span_bytes = (int32_t)(((int64_t)frames * p->Ts / p->Tg - 1) * p->src_nstride * 4 + (int64_t)p->Cs * p->Hs * p->Ws * 4);
-    }
+    for (I2VConvParams* p : {&pa, &pb}) { p->N = frames; p->src_span_bytes = (int32_t)src_span_bytes(*p, frames); }
     CHECK_BE(k_conv_fused(pa, pb, halo, s));
     return 0;
 }
@@ -61,10 +58,7 @@ int fused_run(const Launch& a, const Launch& b, int frames, const float* x, int 
 // never stores that output; only for pairs mark_fusable admitted.  A pair whose sources would have to be sliced runs as two launches.
 static void sc_prep(const Launch& a, const Launch& b, int frames, I2VConvParams* pa, I2VConvParams* pb) {
     *pa = conv_prep(a, nullptr, nullptr, 0); *pb = conv_prep(b, nullptr, nullptr, 0);
-    for (I2VConvParams* p : {pa, pb}) {
-        p->N = frames;
-        p->src_span_bytes = (int32_t)(((int64_t)frames * p->Ts / p->Tg - 1) * p->src_nstride * 4 + (int64_t)p->Cs * p->Hs * p->Ws * 4);
-    }
+    for (I2VConvParams* p : {pa, pb}) { p->N = frames; p->src_span_bytes = (int32_t)src_span_bytes(*p, frames); }
 }
 bool sc_pair_ok(const Launch& a, const Launch& b) {
     if (a.kind != L_CONV || b.kind != L_CONV || a.src_is_input || b.src_is_input || a.T != b.T) return false;
@@ -525,45 +519,24 @@ extern "C" int i2v_net_read_tensor(i2v_handle h, int net, int tensor, int which,
     if (tensor < 0 || tensor >= (int)n->tens.size() || tensor == n->input) return fail("bad tensor id");
     View v = view_of(*n, tensor, which != 0);
     if (frames <= 0 || frames > n->maxN / n->Tin() * v.T) return fail("bad frame count");
-    // The intermediate of a fused pair (k_conv_fused) is never stored: reading it back would hand out stale arena contents.
-    for (const std::vector<Launch>* L : {&n->fwd, &n->bwd})
-        for (const Launch& l : *L) {
-            if (l.kind != L_CONV || !l.fuse_ok || !(l.fuse_b[0] | l.fuse_b[1] | l.fuse_b[2] | l.fuse_b[3])) continue;
-            const float* lo = l.conv.dst; const float* hi = lo + (int64_t)(n->maxN / n->Tin() * std::max(1, l.conv.To) - 1) * l.conv.dst_nstride + (int64_t)l.conv.Cd * l.conv.Ho * l.conv.Wo;
-            const float* vlo = v.p; const float* vhi = v.p + (int64_t)(frames - 1) * v.nstride + (int64_t)v.C * v.H * v.W;
-            if (vlo < hi && lo < vhi)
-                return fail("i2v_net_read_tensor: this tensor is the intermediate of a fused 3x3 -> pointwise pair and is never stored "
-                            "(plan without I2V_FUSE / I2V_FORCE_FUSE to read it)");
-        }
-    // ... and so are the intermediates of a fused fast-pathway block (k_fastblock): every member's output but the last
-    for (const std::vector<Launch>* L : {&n->fwd, &n->bwd})
-        for (size_t i = 0; i < L->size(); ++i) {
-            const Launch& l = (*L)[i];
-            if (l.kind != L_CONV || !l.fb_ok || !(l.fb_b[0] | l.fb_b[1] | l.fb_b[2] | l.fb_b[3])) continue;
-            for (int j = 0; j + 1 < l.fb_ok && i + j < L->size(); ++j) {
-                const I2VConvParams& q = (*L)[i + j].conv;
-                const float* lo = q.dst; const float* hi = lo + (int64_t)(n->maxN / n->Tin() * std::max(1, q.To) - 1) * q.dst_nstride + (int64_t)q.Cd * q.Ho * q.Wo;
-                const float* vlo = v.p; const float* vhi = v.p + (int64_t)(frames - 1) * v.nstride + (int64_t)v.C * v.H * v.W;
-                if (vlo < hi && lo < vhi)
-                    return fail("i2v_net_read_tensor: this tensor is an intermediate of a fused fast-pathway block and is never stored "
-                                "(plan with I2V_FASTBLOCK=0 to read it)");
-            }
-        }
-    // ... and the output of a shortcut that runs inside a pair (k_conv_scpair).  The forward one is produced on demand -- the launch
-    // itself, from its source as the forward pass left it: exactly the values the separate launch stores -- because callers read whole
-    // networks back activation by activation; a gradient view is refused like the others.
-    for (const std::vector<Launch>* L : {&n->fwd, &n->bwd})
-        for (const Launch& l : *L) {
-            if (l.kind != L_CONV || !l.sc_ok || !(l.sc_b[0] | l.sc_b[1] | l.sc_b[2] | l.sc_b[3])) continue;
-            if ((&l)[l.sc_ok].conv.dst == l.conv.dst) continue;       // (added in place: the view holds the consumer's result)
-            const float* lo = l.conv.dst; const float* hi = lo + (int64_t)(n->maxN / n->Tin() * std::max(1, l.conv.To) - 1) * l.conv.dst_nstride + (int64_t)l.conv.Cd * l.conv.Ho * l.conv.Wo;
-            const float* vlo = v.p; const float* vhi = v.p + (int64_t)(frames - 1) * v.nstride + (int64_t)v.C * v.H * v.W;
-            if (!(vlo < hi && lo < vhi)) continue;
-            if (L == &n->bwd || which != 0 || !l.sc_private)
-                return fail("i2v_net_read_tensor: this tensor is the shortcut output of a fused first bottleneck (shortcut pair) and is never stored "
-                            "(plan with I2V_SCPAIR=0 to read it)");
-            if (conv_run(l, frames / std::max(1, v.T) * l.T, nullptr, nullptr, 0, stream)) return 1;
-        }
+    // What a fused group never stores (Net::unstored, recorded once by the plan) cannot be read back: the arena holds stale contents
+    // there.  A forward shortcut that runs inside a pair is produced on demand instead -- the launch itself, from its source as the
+    // forward pass left it: exactly the values the separate launch stores -- because callers read whole networks back activation by
+    // activation; a gradient view, a backward pair and a shortcut into scratch that is reused are refused like the others.
+    static const char* const never_stored[3] = {
+        "i2v_net_read_tensor: this tensor is the intermediate of a fused 3x3 -> pointwise pair and is never stored "
+        "(plan without I2V_FUSE / I2V_FORCE_FUSE to read it)",
+        "i2v_net_read_tensor: this tensor is an intermediate of a fused fast-pathway block and is never stored "
+        "(plan with I2V_FASTBLOCK=0 to read it)",
+        "i2v_net_read_tensor: this tensor is the shortcut output of a fused first bottleneck (shortcut pair) and is never stored "
+        "(plan with I2V_SCPAIR=0 to read it)"};
+    const Range want = extent(v.p, frames, 4 * v.nstride, 4ll * v.C * v.H * v.W);
+    for (const Unstored& u : n->unstored) {
+        if (!meets(u.bytes, want)) continue;
+        if (u.remake < 0 || which != 0) return fail("%s", never_stored[u.group]);
+        const Launch& l = n->fwd[u.remake];
+        if (conv_run(l, frames / std::max(1, v.T) * l.T, nullptr, nullptr, 0, stream)) return 1;
+    }
     size_t row = (size_t)v.C * v.H * v.W * sizeof(float);
     CHECK_BE(be_d2d_2d(out, row, v.p, (size_t)v.nstride * sizeof(float), row, frames, stream));
     return 0;

@@ -9,87 +9,112 @@
 
 namespace eng {
 
+// The shared analysis: every pass below that merges launches, moves one past another or runs one beside its neighbours asks the same
+// question of memory, and access_of is the ONE place that lists the operands of each Kind -- data operands, 1-bit gate rows, arg-max
+// bytes, an SE node's vectors -- with the launch's OWN frame count at the planned clip count; the caller's gradient tensor, whose
+// address no plan knows, is one opaque range.  A new Kind is taught to this function and to nothing else.
+Range conv_dst(const Launch& l, int64_t clips) {
+    const I2VConvParams& q = l.conv;
+    return extent(q.dst, clips * std::max(1, q.To), 4 * q.dst_nstride, 4ll * (q.blk > 1 ? q.Cd / (q.blk * q.blk) : q.Cd) * q.Ho * q.Wo);
+}
+Access access_of(const Launch& c, int64_t clips) {
+    static const char gx_tag[16] = {0};          // stands for the caller's gradient tensor (every launch that touches it conflicts with every other)
+    const Range GX(gx_tag, gx_tag + 16);
+    Access o;
+    auto rd = [&](const Range& x) { if (x.first) o.r.push_back(x); };
+    auto wr = [&](const Range& x) { if (x.first) o.w.push_back(x); };
+    if (c.kind == L_CONV || c.kind == L_IMGGRAD || c.kind == L_GCONV || c.kind == L_DWCONV) {
+        const I2VConvParams& q = c.conv;
+        const int64_t fs = clips * std::max(1, q.Ts), fo = clips * std::max(1, q.To);
+        const int64_t dplane = 4ll * (q.blk > 1 ? q.Cd / (q.blk * q.blk) : q.Cd) * q.Ho * q.Wo;
+        if (!c.src_is_input) rd(extent(q.src, fs, 4 * q.src_nstride, 4ll * q.Cs * q.Hs * q.Ws));
+        rd(extent(q.add0, fo, 4 * q.add0_nstride, dplane)); rd(extent(q.add1, fo, 4 * q.add1_nstride, dplane)); rd(extent(q.mask, fo, 4 * q.mask_nstride, dplane));
+        rd(extent(q.gate, 1, 0, 4ll * q.Cd * q.gate_stride)); wr(extent(q.gate_out, 1, 0, 4ll * q.Cd * q.gate_out_stride));
+        if (c.kind == L_IMGGRAD) { wr(GX); rd(GX); } else wr(conv_dst(c, clips));
+    } else if (c.kind == L_ADDMASK) {
+        const int64_t fr = clips * std::max(1, c.T), pl = 4ll * c.am.C * c.am.HW;
+        wr(extent(c.am.out, fr, 4 * c.am.out_nstride, pl));
+        for (int i = 0; i < 3; ++i) rd(extent(c.am.a[i], fr, 4 * c.am.a_nstride[i], pl));
+        rd(extent(c.am.mask, fr, 4 * c.am.mask_nstride, pl)); rd(extent(c.am.gate, 1, 0, 4ll * c.am.C * c.am.gate_stride));
+    } else if (c.kind == L_MEMSET) {
+        if (c.ms_gx) wr(GX); else wr(extent(c.ms_ptr, 1, 0, 4ll * (int64_t)c.ms_floats_per_frame * clips * std::max(1, c.T)));
+    } else if (c.kind == L_AGEMM || c.kind == L_SOFTMAX) {
+        o.barrier = true;
+    } else if (c.kind == L_SE_SQUEEZE || c.kind == L_SE_EXCITE || c.kind == L_SE_SCALE) {
+        const I2VSeParams& q = c.se;
+        const int64_t fr = clips * std::max(1, c.T), pl = 4ll * q.C * q.HW;
+        const Range vec = extent(c.se_vec, 1, 0, 4ll * (int64_t)c.se_vec_floats);     // (the node's vectors: read and written by its launches only)
+        rd(vec); wr(vec);
+        if (c.kind != L_SE_EXCITE) { rd(extent(q.x, fr, 4 * q.x_nstride, pl)); rd(extent(q.g, fr, 4 * q.g_nstride, pl)); }
+        if (c.kind == L_SE_SCALE) {
+            rd(extent(q.r, fr, 4 * q.r_nstride, pl)); wr(extent(q.dst, fr, 4 * q.dst_nstride, pl));
+            wr(extent(q.gate_out, 1, 0, 4ll * q.C * q.gate_out_stride));
+        }
+    } else {
+        const I2VPoolParams& q = c.pool;
+        const int64_t fr = clips * std::max(std::max(1, c.T), std::max(q.Ts, q.To)), pin = 4ll * q.C * q.Hs * q.Ws, pout = 4ll * q.C * q.Ho * q.Wo;
+        const Range idx = extent(q.idx, 1, 0, fr * (int64_t)q.C * q.Ho * q.Wo);
+        const bool fwd = c.kind == L_POOLF || c.kind == L_POOL3F || c.kind == L_AVGF;
+        if (fwd) { rd(extent(q.x, fr, 4 * q.x_nstride, pin)); wr(extent(q.y, fr, 4 * q.y_nstride, pout)); wr(idx); }
+        else { rd(extent(q.x, fr, 4 * q.x_nstride, pin)); rd(extent(q.y, fr, 4 * q.y_nstride, pout)); rd(extent(q.yact, fr, 4 * q.yact_nstride, pout)); rd(idx);
+               wr(extent(q.gx, fr * std::max(1, q.stride_t), 4 * q.gx_nstride, pin)); }
+    }
+    return o;
+}
+static std::vector<Access> access_of(const std::vector<Launch>& L, int64_t clips) {
+    std::vector<Access> acc; acc.reserve(L.size());
+    for (const Launch& l : L) acc.push_back(access_of(l, clips));
+    return acc;
+}
+
+// Groups that run as ONE kernel and never store what passes between their members: fused pairs, fused fast-pathway blocks, shortcut
+// pairs.  A group qualifies only if NOTHING else looks at that memory: no other launch of either list (which also rules out
+// I2V_GATES=0, whose backward pass reads fp32 activations, and the in-place ReLU gain of i2v_net_set_relu_gain), no hook, and not
+// the network input.  Conservative: any overlap of address ranges counts.  The access sets of both lists are computed once, up here,
+// and follow the launches where a pass swaps two (only where conflict() says that neither sees what the other writes).
 // Fused pairs (k_conv_fused): launch i a 3x3 convolution, launch i + 1 the pointwise convolution that reads its output -- a
-// bottleneck's conv2 -> conv3 in the forward list, the input gradients of conv2 -> conv1 in the backward list.  The fused kernel
-// never stores the intermediate, so the pair qualifies only if NOTHING else touches that memory: no other launch of either list
-// (as source, addend, mask, destination -- which also rules out I2V_GATES=0, whose backward pass reads fp32 activations, and the
-// in-place ReLU gain of i2v_net_set_relu_gain), no hook, and not the network input.  Conservative: any overlap of address ranges counts.
+// bottleneck's conv2 -> conv3 in the forward list, the input gradients of conv2 -> conv1 in the backward list.
 void mark_fusable(Net& n) {
     const int64_t frames = n.maxN, clips = n.maxN / n.Tin();
-    typedef std::pair<const float*, const float*> Range;
-    // extent of an operand: `fr` frames of stride `ns`, the last one `plane` floats long (a view of a wider buffer ends with its own
-    // channels, not with the frame stride); null operands have no extent
-    auto rng = [](const void* q, int64_t fr, int64_t ns, int64_t plane) {
-        const float* f = (const float*)q;
-        return f ? Range(f, f + (fr > 0 ? (fr - 1) * ns : 0) + std::max<int64_t>(plane, 1)) : Range(nullptr, nullptr);
-    };
-    auto meet = [](const Range& a, const Range& b) { return a.first && b.first && a.first < b.second && b.first < a.second; };
-    // every memory range a launch reads or writes, with the launch's OWN frame count; `skip_src` / `skip_dst` leave out the operand
-    // that legitimately is the intermediate (b's source, a's destination)
-    auto touches = [&](const Launch& c, const Range& w, bool skip_src, bool skip_dst) {
-        if (c.kind == L_CONV || c.kind == L_IMGGRAD || c.kind == L_GCONV || c.kind == L_DWCONV) {
-            const I2VConvParams& q = c.conv;
-            const int64_t fs = clips * std::max(1, q.Ts), fo = clips * std::max(1, q.To), dplane = (int64_t)(q.blk > 1 ? q.Cd / (q.blk * q.blk) : q.Cd) * q.Ho * q.Wo;
-            return (!skip_src && meet(w, rng(q.src, fs, q.src_nstride, (int64_t)q.Cs * q.Hs * q.Ws))) ||
-                   meet(w, rng(q.add0, fo, q.add0_nstride, dplane)) || meet(w, rng(q.add1, fo, q.add1_nstride, dplane)) ||
-                   meet(w, rng(q.mask, fo, q.mask_nstride, dplane)) || (!skip_dst && meet(w, rng(q.dst, fo, q.dst_nstride, dplane)));
-        }
-        if (c.kind == L_ADDMASK) {
-            const int64_t fr = clips * std::max(1, c.T), pl = (int64_t)c.am.C * c.am.HW;
-            return meet(w, rng(c.am.out, fr, c.am.out_nstride, pl)) || meet(w, rng(c.am.a[0], fr, c.am.a_nstride[0], pl)) ||
-                   meet(w, rng(c.am.a[1], fr, c.am.a_nstride[1], pl)) || meet(w, rng(c.am.a[2], fr, c.am.a_nstride[2], pl)) ||
-                   meet(w, rng(c.am.mask, fr, c.am.mask_nstride, pl));
-        }
-        if (c.kind == L_MEMSET) return meet(w, rng(c.ms_ptr, 1, 0, (int64_t)c.ms_floats_per_frame * clips * std::max(1, c.T)));
-        if (c.kind == L_AGEMM || c.kind == L_SOFTMAX) return true;     // attention launches address whole matrices: not analysed, such nets are not fused
-        if (c.kind == L_SE_SQUEEZE || c.kind == L_SE_EXCITE || c.kind == L_SE_SCALE) {      // every view of the node, whichever of its launches this is
-            const I2VSeParams& q = c.se;
-            const int64_t fr = clips * std::max(1, c.T), pl = (int64_t)q.C * q.HW;
-            return meet(w, rng(q.x, fr, q.x_nstride, pl)) || meet(w, rng(q.g, fr, q.g_nstride, pl)) || meet(w, rng(q.r, fr, q.r_nstride, pl)) ||
-                   meet(w, rng(q.dst, fr, q.dst_nstride, pl)) || meet(w, rng(c.se_vec, 1, 0, (int64_t)c.se_vec_floats));
-        }
-        const I2VPoolParams& q = c.pool;
-        const int64_t fr = clips * std::max(std::max(1, c.T), std::max(q.Ts, q.To)), pin = (int64_t)q.C * q.Hs * q.Ws, pout = (int64_t)q.C * q.Ho * q.Wo;
-        return meet(w, rng(q.x, fr, q.x_nstride, pin)) || meet(w, rng(q.gx, fr, q.gx_nstride, pin)) || meet(w, rng(q.y, fr, q.y_nstride, pout)) ||
-               meet(w, rng(q.yact, fr, q.yact_nstride, pout));
-    };
+    std::vector<Launch>* const lists[2] = {&n.fwd, &n.bwd};
+    std::vector<Access> acc[2] = {access_of(n.fwd, clips), access_of(n.bwd, clips)};
     std::vector<Range> hooked;
     for (size_t h = 0; h < n.hooks.size(); ++h) {
         View a = view_of(n, n.hooks[h], false), g = view_of(n, n.hooks[h], true);
-        hooked.push_back(rng(a.p, frames, a.nstride, (int64_t)a.C * a.H * a.W));
-        hooked.push_back(rng(g.p, frames, g.nstride, (int64_t)g.C * g.H * g.W));
+        hooked.push_back(extent(a.p, frames, 4 * a.nstride, 4ll * a.C * a.H * a.W));
+        hooked.push_back(extent(g.p, frames, 4 * g.nstride, 4ll * g.C * g.H * g.W));
     }
-    auto dst_of = [&](const Launch& l) {
-        return rng(l.conv.dst, clips * std::max(1, l.conv.To), l.conv.dst_nstride, (int64_t)l.conv.Cd * l.conv.Ho * l.conv.Wo);
+    auto hook_on = [&](const Range& w) { for (const Range& hk : hooked) if (meets(hk, w)) return true; return false; };
+    // does a launch of either list, other than launches first .. last of list k, read or write `w`?
+    auto others_touch = [&](int k, size_t first, size_t last, const Range& w) {
+        for (int m = 0; m < 2; ++m)
+            for (size_t j = 0; j < acc[m].size(); ++j)
+                if (!(m == k && j >= first && j <= last) && (reads(acc[m][j], w) || writes(acc[m][j], w))) return true;
+        return false;
     };
+    auto swap_launches = [&](int k, size_t i, size_t j) { std::swap((*lists[k])[i], (*lists[k])[j]); std::swap(acc[k][i], acc[k][j]); };
     // A first bottleneck runs its shortcut convolution between conv2 and conv3 (conv3 adds it): where that launch and the 3x3 are
     // independent of each other, they swap places so that the pair becomes adjacent.
-    for (std::vector<Launch>* L : {&n.fwd, &n.bwd})
-        for (size_t i = 0; i + 2 < L->size(); ++i) {
-            Launch& a = (*L)[i]; Launch& c = (*L)[i + 1]; Launch& b = (*L)[i + 2];
+    for (int k = 0; k < 2; ++k)
+        for (size_t i = 0; i + 2 < lists[k]->size(); ++i) {
+            const Launch& a = (*lists[k])[i]; const Launch& c = (*lists[k])[i + 1]; const Launch& b = (*lists[k])[i + 2];
             if (a.kind != L_CONV || c.kind != L_CONV || b.kind != L_CONV || a.src_is_input || c.src_is_input || !k_conv_fusable(a.conv, b.conv)) continue;
             if (k_conv_fusable(a.conv, c.conv)) continue;
-            const I2VConvParams& pa = a.conv; const I2VConvParams& pc = c.conv;
-            const bool dep = touches(c, dst_of(a), false, false) || touches(a, dst_of(c), false, false) ||
-                             (pa.gate_out && (pa.gate_out == pc.gate || pa.gate_out == pc.gate_out)) || (pc.gate_out && pc.gate_out == pa.gate);
-            if (!dep) std::swap(a, c);
+            if (!conflict(acc[k][i], acc[k][i + 1])) swap_launches(k, i, i + 1);
         }
-    for (std::vector<Launch>* L : {&n.fwd, &n.bwd})
-        for (size_t i = 0; i + 1 < L->size(); ++i) {
-            Launch& a = (*L)[i]; Launch& b = (*L)[i + 1];
+    for (int k = 0; k < 2; ++k)
+        for (size_t i = 0; i + 1 < lists[k]->size(); ++i) {
+            Launch& a = (*lists[k])[i]; const Launch& b = (*lists[k])[i + 1];
             a.fuse_ok = 0;
             if (a.kind != L_CONV || b.kind != L_CONV || a.src_is_input || b.src_is_input || a.T != b.T) continue;
             const int ok = k_conv_fusable(a.conv, b.conv);
             if (!ok) continue;
-            const Range w = dst_of(a);
-            bool other = false;
-            for (auto& hk : hooked) other |= meet(hk, w);
-            for (std::vector<Launch>* M : {&n.fwd, &n.bwd})
-                for (size_t j = 0; j < M->size() && !other; ++j)
-                    other |= touches((*M)[j], w, M == L && j == i + 1, M == L && j == i);
+            // the intermediate: a writes it and b reads it as its source -- and neither may see it through any other operand
+            const Range w = conv_dst(a, clips);
+            const bool other = hook_on(w) || others_touch(k, i, i + 1, w) || reads(acc[k][i], w) || reads(acc[k][i + 1], w) > 1 || writes(acc[k][i + 1], w);
             if (!other) a.fuse_ok = ok;
             if (getenv("I2V_FUSE_DEBUG"))
-                fprintf(stderr, "[i2v fuse] %s pair %zu: 3x3 Cd=%d K=%d %dx%d -> 1x1 Cd=%d K=%d: eligible=%d other_reader=%d\n", L == &n.fwd ? "fwd" : "bwd", i,
+                fprintf(stderr, "[i2v fuse] %s pair %zu: 3x3 Cd=%d K=%d %dx%d -> 1x1 Cd=%d K=%d: eligible=%d other_reader=%d\n", k ? "bwd" : "fwd", i,
                         a.conv.Cd, a.conv.K, a.conv.Hg, a.conv.Wg, b.conv.Cd, b.conv.K, ok, (int)other);
         }
     // ---- fused fast-pathway blocks (k_fastblock): groups of consecutive launches, found from the graph nodes behind them ----
@@ -101,35 +126,26 @@ void mark_fusable(Net& n) {
         auto is_t = [&](const i2v_conv3d_desc& c) { return unit(c) && c.kh == 1 && c.kw == 1 && c.pad == 0 && (c.kt & 1) && 2 * c.pad_t == c.kt - 1; };      // k x 1 x 1, "same"
         auto is_33 = [&](const i2v_conv3d_desc& c) { return unit(c) && c.kt == 1 && c.kh == 3 && c.kw == 3 && c.pad == 1 && c.pad_t == 0; };
         // nothing but the group's own launches may touch an intermediate, and it must not be hooked
-        auto private_to = [&](std::vector<Launch>* L, size_t first, size_t last, const Launch& w) {
-            const Range r = dst_of(w);
-            for (auto& hk : hooked) if (meet(hk, r)) return false;
-            for (std::vector<Launch>* M : {&n.fwd, &n.bwd})
-                for (size_t j = 0; j < M->size(); ++j) {
-                    if (M == L && j >= first && j <= last) continue;
-                    if (touches((*M)[j], r, false, false)) return false;
-                }
-            return true;
+        auto private_to = [&](int k, size_t first, size_t last, const Launch& w) {
+            const Range r = conv_dst(w, clips);
+            return !hook_on(r) && !others_touch(k, first, last, r);
         };
         for (Launch& l : n.fwd) l.fb_ok = 0;
         for (Launch& l : n.bwd) l.fb_ok = 0;
         // backward: [conv3's input gradient, X, conv2's input gradient] with X independent of both (a first block's projection-shortcut
         // gradient sits between them): X moves in front
         for (size_t i = 0; !fb_off && i + 2 < n.bwd.size(); ++i) {
-            Launch& a = n.bwd[i]; Launch& x = n.bwd[i + 1]; Launch& b = n.bwd[i + 2];
+            const Launch& a = n.bwd[i]; const Launch& x = n.bwd[i + 1]; const Launch& b = n.bwd[i + 2];
             const i2v_conv3d_desc* ca = cd_of(a); const i2v_conv3d_desc* cb = cd_of(b);
             if (!ca || !cb || !is_pw(*ca) || !is_33(*cb) || b.conv.src != a.conv.dst || x.kind != L_CONV) continue;
-            const I2VConvParams& px = x.conv;
-            const bool dep = touches(x, dst_of(a), false, false) || touches(a, dst_of(x), false, false) || touches(x, dst_of(b), false, false) || touches(b, dst_of(x), false, false) ||
-                             (px.gate_out && (px.gate_out == a.conv.gate || px.gate_out == b.conv.gate));
-            if (!dep) { Launch t = x; n.bwd[i + 1] = n.bwd[i]; n.bwd[i] = t; }
+            if (!conflict(acc[1][i + 1], acc[1][i]) && !conflict(acc[1][i + 1], acc[1][i + 2])) swap_launches(1, i, i + 1);
         }
         for (size_t i = 0; !fb_off && i + 1 < n.bwd.size(); ++i) {
             Launch& a = n.bwd[i]; Launch& b = n.bwd[i + 1];
             const i2v_conv3d_desc* ca = cd_of(a); const i2v_conv3d_desc* cb = cd_of(b);
             if (!ca || !cb || !is_pw(*ca) || !is_33(*cb) || a.T != b.T || b.conv.src != a.conv.dst) continue;
             if (i2v_fastblock_rows(a.conv, b.conv, nullptr, nullptr) <= 0) continue;
-            if (!private_to(&n.bwd, i, i + 1, a)) continue;
+            if (!private_to(1, i, i + 1, a)) continue;
             a.fb_ok = 2;
         }
         for (size_t i = 0; !fb_off && i + 2 < n.fwd.size(); ++i) {
@@ -141,24 +157,24 @@ void mark_fusable(Net& n) {
             if (!cc || !is_pw(*cc)) continue;
             if (cc->src == cb->dst && cc->residual >= 0 && cc->relu && a.T == b.T && a.T == c3.T) {               // identity shortcut
                 if (i2v_fastblock_rows(a.conv, b.conv, &c3.conv, nullptr) <= 0) continue;
-                if (!private_to(&n.fwd, i, i + 2, a) || !private_to(&n.fwd, i, i + 2, b)) continue;
+                if (!private_to(0, i, i + 2, a) || !private_to(0, i, i + 2, b)) continue;
                 a.fb_ok = 3;
             } else if (i + 3 < n.fwd.size() && cc->src == ca->src && !cc->relu && cc->residual < 0) {             // projection shortcut, then conv3
                 Launch& c4 = n.fwd[i + 3];
                 const i2v_conv3d_desc* c4d = cd_of(c4);
                 if (!c4d || !is_pw(*c4d) || c4d->src != cb->dst || c4d->residual != cc->dst || !c4d->relu || a.T != b.T || a.T != c3.T || a.T != c4.T) continue;
                 if (i2v_fastblock_rows(a.conv, b.conv, &c4.conv, &c3.conv) <= 0) continue;
-                if (!private_to(&n.fwd, i, i + 3, a) || !private_to(&n.fwd, i, i + 3, b) || !private_to(&n.fwd, i, i + 3, c3)) continue;
+                if (!private_to(0, i, i + 3, a) || !private_to(0, i, i + 3, b) || !private_to(0, i, i + 3, c3)) continue;
                 a.fb_ok = 4;
             }
         }
         // without the autotuner (I2V_AUTOTUNE=0: tests, tools, the host simulation) a group is fused only on request
         const bool fb_force = [] { const char* e = getenv("I2V_FORCE_FASTBLOCK"); return e && e[0] == '1'; }();      // (read per plan: tests compare both)
-        for (std::vector<Launch>* L : {&n.fwd, &n.bwd})
+        for (std::vector<Launch>* L : lists)
             for (Launch& a : *L)
                 for (int bk = 0; bk < 4; ++bk) a.fb_b[bk] = (a.fb_ok && fb_force) ? 1 : 0;
         if (getenv("I2V_FUSE_DEBUG"))
-            for (std::vector<Launch>* L : {&n.fwd, &n.bwd})
+            for (std::vector<Launch>* L : lists)
                 for (size_t i = 0; i < L->size(); ++i)
                     if ((*L)[i].fb_ok) fprintf(stderr, "[i2v fastblock] %s launch %zu: group of %d (Cs %d -> %d mid channels, %dx%d)\n", L == &n.fwd ? "fwd" : "bwd", i, (*L)[i].fb_ok,
                                                (*L)[i].conv.Cs, (*L)[i].conv.Cd, (*L)[i].conv.Hg, (*L)[i].conv.Wg);
@@ -168,48 +184,48 @@ void mark_fusable(Net& n) {
     // next one's addend on the same grid (the stride-1 first bottleneck: the shortcut's input gradient under conv1's).  The pair never
     // stores the intermediate, so nothing -- launch of either list, hook, in-place gain -- may look at that memory while the two launches
     // would have kept a's output in it (spelled out below).  The shortcut need not be adjacent to its consumer: the executor runs it in the consumer's place, which is the same
-    // schedule with the shortcut moved down -- admitted only if it is independent of every launch it passes (the test of the swap above).
+    // schedule with the shortcut moved down -- admitted only if it does not conflict with any launch it passes (the test of the swaps above).
     {
         const bool sc_off = [] { const char* e = getenv("I2V_SCPAIR"); return e && e[0] == '0'; }();      // (read per plan: tests and A/B runs compare both)
-        for (std::vector<Launch>* L : {&n.fwd, &n.bwd}) {
-            for (Launch& l : *L) { l.sc_ok = 0; l.sc_private = false; for (int bk = 0; bk < 4; ++bk) l.sc_b[bk] = 0; }
-            for (size_t i = 0; !sc_off && i + 1 < L->size(); ++i) {
-                Launch& a = (*L)[i];
+        for (int k = 0; k < 2; ++k) {
+            std::vector<Launch>& L = *lists[k];
+            const std::vector<Access>& A = acc[k];
+            for (Launch& l : L) { l.sc_ok = 0; l.sc_private = false; for (int bk = 0; bk < 4; ++bk) l.sc_b[bk] = 0; }
+            for (size_t i = 0; !sc_off && i + 1 < L.size(); ++i) {
+                Launch& a = L[i];
                 if (a.kind != L_CONV || a.src_is_input || a.conv.add0 || a.conv.relu) continue;
-                for (size_t j = i + 1; j < L->size() && j <= i + 3; ++j) {
-                    const Launch& b = (*L)[j];
+                for (size_t j = i + 1; j < L.size() && j <= i + 3; ++j) {
+                    const Launch& b = L[j];
                     if (b.kind != L_CONV || b.conv.add0 != a.conv.dst) continue;
                     if (!sc_pair_ok(a, b)) break;
-                    const Range w = dst_of(a);
+                    const Range w = conv_dst(a, clips);
                     // The pair differs from the two launches in what `w` holds from a's place in the list on, until something overwrites
-                    // it: nothing may look at it there.  Not the launches passed; not b through another operand; after b, in list order,
+                    // it: nothing may look at it there.  Not the launches passed; not b through a second operand; after b, in list order,
                     // no launch may read it before one has overwritten all of it (b itself, where an input gradient adds IN PLACE; the
                     // next user of a scratch view) -- and while it is live no hook and no launch of the other list may touch it at all.
-                    auto conv_kind = [](const Launch& c) { return c.kind == L_CONV || c.kind == L_IMGGRAD || c.kind == L_GCONV || c.kind == L_DWCONV; };
-                    auto reads = [&](const Launch& c) { return touches(c, w, false, conv_kind(c)); };
-                    auto covers = [&](const Launch& c) { return conv_kind(c) && c.conv.dst && dst_of(c).first <= w.first && dst_of(c).second >= w.second; };
-                    Launch b_rest = b; b_rest.conv.add0 = nullptr;          // b without the operand that legitimately is the intermediate
-                    bool other = reads(b_rest), dead = covers(b);
-                    for (size_t k = i + 1; k < j && !other; ++k) other |= touches((*L)[k], w, false, false);
-                    for (size_t k = j + 1; k < L->size() && !other && !dead; ++k) {
-                        if (reads((*L)[k])) other = true;
-                        else if (covers((*L)[k])) dead = true;
-                        else other = touches((*L)[k], w, false, false);
+                    bool other = reads(A[j], w) > 1, dead = covers(A[j], w);
+                    for (size_t m = i + 1; m < j && !other; ++m) other = reads(A[m], w) || writes(A[m], w);
+                    for (size_t m = j + 1; m < L.size() && !other && !dead; ++m) {
+                        if (reads(A[m], w)) other = true;
+                        else if (covers(A[m], w)) dead = true;
+                        else other = writes(A[m], w);
                     }
                     if (!dead) {
-                        for (auto& hk : hooked) other |= meet(hk, w);
-                        for (const Launch& c : (L == &n.fwd ? n.bwd : n.fwd)) other = other || touches(c, w, false, false);
+                        other = other || hook_on(w);
+                        for (const Access& c : acc[1 - k]) other = other || reads(c, w) || writes(c, w);
                     }
-                    bool dep = false;                                       // ... and of the launches it passes: they write nothing it reads
-                    for (size_t k = i + 1; k < j && !dep; ++k) {
-                        const Launch& m = (*L)[k];
-                        const I2VConvParams& pa = a.conv; const I2VConvParams& pm = m.conv;
-                        dep = (m.kind != L_CONV && m.kind != L_GCONV && m.kind != L_DWCONV) || m.src_is_input || touches(a, dst_of(m), false, false) ||
-                              (pm.gate_out && (pm.gate_out == pa.gate || pm.gate_out == pa.gate_out)) || (pa.gate_out && (pa.gate_out == pm.gate || pa.gate_out == pm.gate_out));
+                    // ... and the launches it passes are convolutions on planned views that it does not conflict with.  This is conflict()
+                    // less ONE term: a passed launch that reads `w` is an other_reader (above) and not a dependent, the split that the
+                    // recorded decisions (tests/golden/plan_trace.txt) have always reported; the pair is refused either way.
+                    bool dep = false;
+                    for (size_t m = i + 1; m < j && !dep; ++m) {
+                        dep = (L[m].kind != L_CONV && L[m].kind != L_GCONV && L[m].kind != L_DWCONV) || L[m].src_is_input;
+                        for (const Range& x : A[m].w) dep = dep || reads(A[i], x) || writes(A[i], x);
+                        for (const Range& x : A[i].w) dep = dep || (x != w && reads(A[m], x));
                     }
                     if (!other && !dep) { a.sc_ok = (int)(j - i); a.sc_private = !dead; for (int bk = 0; bk < 4; ++bk) a.sc_b[bk] = 1; }
                     if (getenv("I2V_FUSE_DEBUG"))
-                        fprintf(stderr, "[i2v scpair] %s launches %zu + %zu (K %d + %d -> Cd %d, %dx%d): other_reader=%d dependent=%d\n", L == &n.fwd ? "fwd" : "bwd", i, j,
+                        fprintf(stderr, "[i2v scpair] %s launches %zu + %zu (K %d + %d -> Cd %d, %dx%d): other_reader=%d dependent=%d\n", k ? "bwd" : "fwd", i, j,
                                 a.conv.K, b.conv.K, b.conv.Cd, b.conv.Hg, b.conv.Wg, (int)other, (int)dep);
                     break;
                 }
@@ -219,9 +235,30 @@ void mark_fusable(Net& n) {
     // without the autotuner (I2V_AUTOTUNE=0: tests, tools) a pair is fused only on request: I2V_FORCE_FUSE = 1 (plain) / 2 (halo where it applies)
     const char* force = getenv("I2V_FORCE_FUSE");
     const int f = force ? atoi(force) : 0;
-    for (std::vector<Launch>* L : {&n.fwd, &n.bwd})
+    for (std::vector<Launch>* L : lists)
         for (Launch& a : *L)
             for (int b = 0; b < 4; ++b) a.fuse_b[b] = (a.fuse_ok && f) ? ((f == 2 && (a.fuse_ok & 2)) ? 2 : 1) : 0;
+}
+
+// What the plan leaves UNSTORED, once, for i2v_net_read_tensor: the intermediate of a pair that runs fused in any batch bucket, every
+// member's output but the last of a fast-pathway block that does, and the output of a shortcut that runs inside a pair unless its
+// consumer adds in place (then the view holds the consumer's result).  In this order: a read-back names the first grouping that applies.
+void record_unstored(Net& n) {
+    n.unstored.clear();
+    const int64_t clips = n.maxN / n.Tin();
+    auto any = [](const int b[4]) { return (b[0] | b[1] | b[2] | b[3]) != 0; };
+    for (int group = 0; group < 3; ++group)
+        for (const std::vector<Launch>* L : {&n.fwd, &n.bwd})
+            for (size_t i = 0; i < L->size(); ++i) {
+                const Launch& l = (*L)[i];
+                if (l.kind != L_CONV) continue;
+                if (group == 0 && l.fuse_ok && any(l.fuse_b)) n.unstored.push_back({conv_dst(l, clips), 0, -1});
+                if (group == 1 && l.fb_ok && any(l.fb_b))
+                    for (int j = 0; j + 1 < l.fb_ok && i + j < L->size(); ++j) n.unstored.push_back({conv_dst((*L)[i + j], clips), 1, -1});
+                // a forward shortcut whose view nothing else ever touches can be produced on demand: the launch itself, from its source
+                if (group == 2 && l.sc_ok && any(l.sc_b) && (*L)[i + l.sc_ok].conv.dst != l.conv.dst)
+                    n.unstored.push_back({conv_dst(l, clips), 2, (L == &n.fwd && l.sc_private) ? (int)i : -1});
+            }
 }
 
 // Launch overlap (round 6): a single 32-frame clip leaves the 14 x 14 layers with 1.5 tiles per CU, and a launch
@@ -229,9 +266,8 @@ void mark_fusable(Net& n) {
 // only (conv3 adds its result); backward, its input gradient depends on the gradient of the block's output only (conv1's input
 // gradient adds it).  Such a launch is HOISTED: issued on the net's side stream as soon as the launch it depends on has been issued
 // on the main stream, joined (event wait on the main stream) in front of the first launch that touches its operands.  Which launches
-// qualify is decided from the address ranges every launch of a list reads and writes -- data operands, 1-bit gate rows, arg-max
-// bytes, the caller's gradient tensor as one opaque range; attention launches are barriers -- conservatively (ranges at the planned
-// frame count; any overlap counts).  No launch changes, so every result stays bit-identical; the host simulation, which executes
+// qualify is decided by conflict() on the access sets of a list (access_of above: ranges at the planned frame count, any overlap
+// counts, the caller's gradient tensor one opaque range, attention launches barriers).  No launch changes, so every result stays bit-identical; the host simulation, which executes
 // launches synchronously in ISSUE order, really runs a hoisted launch early and so tests the analysis (tests/test_planner_hostsim.py).
 // MEASURED AND NOT TAKEN (tools/overlap_probe.py, profiles/r6_overlap_probe.txt): one 32-frame clip 610 -> 589 frames/s (-3.4 %), four
 // clips 761 -> 755 -- every hoisted launch costs two event records and two cross-queue waits, and a queue that waits on another
@@ -243,67 +279,10 @@ void mark_overlap(Net& n) {
     const char* e = getenv("I2V_OVERLAP_MAX_FRAMES");
     n.ov_max_frames = e ? atoi(e) : 0;
     if (n.ov_max_frames <= 0) return;
-    const int64_t clips = n.maxN / n.Tin();
-    typedef std::pair<const char*, const char*> Range;
-    struct RW { std::vector<Range> r, w; bool barrier = false; };
-    static const char gx_tag[16] = {0};          // stands for the caller's gradient tensor (every launch that touches it conflicts with every other)
-    const Range GX(gx_tag, gx_tag + 16);
-    auto rng = [](const void* q, int64_t fr, int64_t stride_bytes, int64_t plane_bytes) {
-        const char* f = (const char*)q;
-        return f ? Range(f, f + (fr > 0 ? (fr - 1) * stride_bytes : 0) + std::max<int64_t>(plane_bytes, 1)) : Range(nullptr, nullptr);
-    };
-    auto rw_of = [&](const Launch& c) {
-        RW o;
-        auto rd = [&](const Range& x) { if (x.first) o.r.push_back(x); };
-        auto wr = [&](const Range& x) { if (x.first) o.w.push_back(x); };
-        if (c.kind == L_CONV || c.kind == L_IMGGRAD || c.kind == L_GCONV || c.kind == L_DWCONV) {
-            const I2VConvParams& q = c.conv;
-            const int64_t fs = clips * std::max(1, q.Ts), fo = clips * std::max(1, q.To);
-            const int64_t dplane = 4ll * (q.blk > 1 ? q.Cd / (q.blk * q.blk) : q.Cd) * q.Ho * q.Wo;
-            if (!c.src_is_input) rd(rng(q.src, fs, 4 * q.src_nstride, 4ll * q.Cs * q.Hs * q.Ws));
-            rd(rng(q.add0, fo, 4 * q.add0_nstride, dplane)); rd(rng(q.add1, fo, 4 * q.add1_nstride, dplane)); rd(rng(q.mask, fo, 4 * q.mask_nstride, dplane));
-            rd(rng(q.gate, 1, 0, 4ll * q.Cd * q.gate_stride)); wr(rng(q.gate_out, 1, 0, 4ll * q.Cd * q.gate_out_stride));
-            if (c.kind == L_IMGGRAD) { wr(GX); rd(GX); } else wr(rng(q.dst, fo, 4 * q.dst_nstride, dplane));
-        } else if (c.kind == L_ADDMASK) {
-            const int64_t fr = clips * std::max(1, c.T), pl = 4ll * c.am.C * c.am.HW;
-            wr(rng(c.am.out, fr, 4 * c.am.out_nstride, pl));
-            for (int i = 0; i < 3; ++i) rd(rng(c.am.a[i], fr, 4 * c.am.a_nstride[i], pl));
-            rd(rng(c.am.mask, fr, 4 * c.am.mask_nstride, pl)); rd(rng(c.am.gate, 1, 0, 4ll * c.am.C * c.am.gate_stride));
-        } else if (c.kind == L_MEMSET) {
-            if (c.ms_gx) wr(GX); else wr(rng(c.ms_ptr, 1, 0, 4ll * (int64_t)c.ms_floats_per_frame * clips * std::max(1, c.T)));
-        } else if (c.kind == L_AGEMM || c.kind == L_SOFTMAX) {
-            o.barrier = true;
-        } else if (c.kind == L_SE_SQUEEZE || c.kind == L_SE_EXCITE || c.kind == L_SE_SCALE) {
-            const I2VSeParams& q = c.se;
-            const int64_t fr = clips * std::max(1, c.T), pl = 4ll * q.C * q.HW;
-            const Range vec = rng(c.se_vec, 1, 0, 4ll * (int64_t)c.se_vec_floats);     // (the node's vectors: read and written by its launches only)
-            rd(vec); wr(vec);
-            if (c.kind != L_SE_EXCITE) { rd(rng(q.x, fr, 4 * q.x_nstride, pl)); rd(rng(q.g, fr, 4 * q.g_nstride, pl)); }
-            if (c.kind == L_SE_SCALE) {
-                rd(rng(q.r, fr, 4 * q.r_nstride, pl)); wr(rng(q.dst, fr, 4 * q.dst_nstride, pl));
-                wr(rng(q.gate_out, 1, 0, 4ll * q.C * q.gate_out_stride));
-            }
-        } else {
-            const I2VPoolParams& q = c.pool;
-            const int64_t fr = clips * std::max(std::max(1, c.T), std::max(q.Ts, q.To)), pin = 4ll * q.C * q.Hs * q.Ws, pout = 4ll * q.C * q.Ho * q.Wo;
-            const Range idx = rng(q.idx, 1, 0, fr * (int64_t)q.C * q.Ho * q.Wo);
-            const bool fwd = c.kind == L_POOLF || c.kind == L_POOL3F || c.kind == L_AVGF;
-            if (fwd) { rd(rng(q.x, fr, 4 * q.x_nstride, pin)); wr(rng(q.y, fr, 4 * q.y_nstride, pout)); wr(idx); }
-            else { rd(rng(q.x, fr, 4 * q.x_nstride, pin)); rd(rng(q.y, fr, 4 * q.y_nstride, pout)); rd(rng(q.yact, fr, 4 * q.yact_nstride, pout)); rd(idx);
-                   wr(rng(q.gx, fr * std::max(1, q.stride_t), 4 * q.gx_nstride, pin)); }
-        }
-        return o;
-    };
-    auto meet = [](const std::vector<Range>& A, const std::vector<Range>& B) {
-        for (const Range& a : A) for (const Range& b : B) if (a.first < b.second && b.first < a.second) return true;
-        return false;
-    };
-    auto conflict = [&](const RW& a, const RW& b) { return a.barrier || b.barrier || meet(a.r, b.w) || meet(a.w, b.w) || meet(a.w, b.r); };
     int k = 0;
     for (std::vector<Launch>* L : {&n.fwd, &n.bwd}) {
         const int M = (int)L->size();
-        std::vector<RW> rw; rw.reserve(M);
-        for (const Launch& l : *L) rw.push_back(rw_of(l));
+        const std::vector<Access> rw = access_of(*L, n.maxN / n.Tin());
         std::vector<char> member(M, 0);          // part of a group that may run as ONE kernel (fused pair, fused fast-pathway block): stays in place
         for (int i = 0; i < M; ++i) {
             const Launch& l = (*L)[i];
