@@ -228,8 +228,8 @@ int k_conv(const I2VConvParams& p_in, i2v_stream_t s) {
 // Both pooling kernels: one block per (frame, channel) plane and band of output rows; the band's input
 // rows (fwd) / arg-max bytes and upstream gradients (bwd) are staged in LDS with coalesced loads, so the
 // kernels stream at HBM rate instead of issuing k*k strided global loads per element.  32-bit index math.
-#define POOL_LDS_FLOATS 8192
-#define POOL_FWD_LDS_FLOATS 4096    // forward band: 16 KB -> 10 blocks per CU in flight (8192: 2.7 TB/s, 4096: 4.0, 2048: 3.6)
+#define POOL_LDS_FLOATS 8192            // (tests/pool_cases.py derives its banded cases from these two sizes: re-derive them with a change here)
+#define POOL_FWD_LDS_FLOATS 4096    // forward band: 16 KB -> 10 blocks per CU in flight (8192: 2.7 TB/s, 4096: 4.0, 2048: 3.6); see tests/pool_cases.py
 __global__ void __launch_bounds__(256) pool_fwd_kernel(const I2VPoolParams p, const int band_rows) {
     __shared__ float xs[POOL_FWD_LDS_FLOATS];
     const int plane = blockIdx.x, n = plane / p.C, c = plane - n * p.C;
@@ -404,6 +404,10 @@ __global__ void avgpool_fwd_kernel(const I2VPoolParams p) {
     }
 }
 
+// gather form, as pool3d_bwd_kernel: an input element collects from every window that covers it (k > stride: several; k < stride: the
+// gaps between windows get zero), in (output row, output column) order, then one multiplication by 1 / k^2.  mask_relu: the ReLU
+// gate of the averaged tensor, which this launch finalises.  (The first addend is assigned, not added to 0: behind a single window a
+// -0 stays -0, the bits of the one-window form this kernel had.)
 __global__ void avgpool_bwd_kernel(const I2VPoolParams p) {
     const int64_t total = (int64_t)p.N * p.C * p.Hs * p.Ws;
     const float inv = 1.f / (float)(p.k * p.k);
@@ -411,10 +415,21 @@ __global__ void avgpool_bwd_kernel(const I2VPoolParams p) {
         const int w = idx % p.Ws; int64_t r = idx / p.Ws;
         const int h = r % p.Hs; r /= p.Hs;
         const int c = r % p.C; const int64_t n = r / p.C;
-        const int ho = h / p.stride, wo = w / p.stride;
-        const bool in = (h - ho * p.stride) < p.k && (w - wo * p.stride) < p.k && ho < p.Ho && wo < p.Wo;
-        p.gx[n * p.gx_nstride + ((int64_t)c * p.Hs + h) * p.Ws + w] =
-            in ? p.y[n * p.y_nstride + ((int64_t)c * p.Ho + ho) * p.Wo + wo] * inv : 0.f;
+        float g = 0.f;
+        if (!p.mask_relu || p.x[n * p.x_nstride + ((int64_t)c * p.Hs + h) * p.Ws + w] > 0.f) {
+            int a_lo = h - p.k + 1; a_lo = a_lo <= 0 ? 0 : (a_lo + p.stride - 1) / p.stride;
+            const int a_hi = min(h / p.stride, p.Ho - 1);
+            int b_lo = w - p.k + 1; b_lo = b_lo <= 0 ? 0 : (b_lo + p.stride - 1) / p.stride;
+            const int b_hi = min(w / p.stride, p.Wo - 1);
+            bool first = true;
+            for (int ho = a_lo; ho <= a_hi; ++ho)
+                for (int wo = b_lo; wo <= b_hi; ++wo) {
+                    const float v = p.y[n * p.y_nstride + ((int64_t)c * p.Ho + ho) * p.Wo + wo];
+                    g = first ? v : g + v; first = false;
+                }
+            if (!first) g *= inv;
+        }
+        p.gx[n * p.gx_nstride + ((int64_t)c * p.Hs + h) * p.Ws + w] = g;
     }
 }
 

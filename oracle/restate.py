@@ -136,10 +136,10 @@ class OracleNet:
                     gx = gx * (pre > 0).to(self.dtype) * inv.view(1, -1, 1, 1)
                 self._view(gb, nd.src, N).add_(gx)
             elif nd.op == "avgpool":
-                gx = gd.repeat_interleave(nd.k, 2).repeat_interleave(nd.k, 3) / (nd.k * nd.k)
-                full = torch.zeros_like(src)
-                full[:, :, :gx.shape[2], :gx.shape[3]] = gx
-                self._view(gb, nd.src, N).add_(full)
+                # ATen's own adjoint: right for overlapping windows (k > stride) and for gaps between them (k < stride) as well
+                gx = torch.ops.aten.avg_pool2d_backward(gd.contiguous(), src.contiguous(), [nd.k, nd.k], [nd.stride, nd.stride], [0, 0],
+                                                        False, True, None)
+                self._view(gb, nd.src, N).add_(gx)
             else:
                 idx = self.pool_idx[i]
                 C = src.shape[1]

@@ -243,21 +243,30 @@ int k_pool3d_bwd(const I2VPoolParams& p, i2v_stream_t) {
 }
 
 int k_avgpool_fwd(const I2VPoolParams& p, i2v_stream_t) {
+    const float inv = 1.f / (float)(p.k * p.k);
     for (int n = 0; n < p.N; ++n) for (int c = 0; c < p.C; ++c) for (int ho = 0; ho < p.Ho; ++ho) for (int wo = 0; wo < p.Wo; ++wo) {
         float s = 0.f;
         for (int r = 0; r < p.k; ++r) for (int q = 0; q < p.k; ++q)
             s += p.x[(size_t)n * p.x_nstride + ((size_t)c * p.Hs + ho * p.stride + r) * p.Ws + wo * p.stride + q];
-        p.y[(size_t)n * p.y_nstride + ((size_t)c * p.Ho + ho) * p.Wo + wo] = s / (p.k * p.k);
+        p.y[(size_t)n * p.y_nstride + ((size_t)c * p.Ho + ho) * p.Wo + wo] = s * inv;
     }
     return 0;
 }
 
+// every window covering the element, in (output row, output column) order, then one multiplication by 1 / k^2; the ReLU gate of the
+// averaged tensor where this launch finalises its gradient (mask_relu)
 int k_avgpool_bwd(const I2VPoolParams& p, i2v_stream_t) {
+    const float inv = 1.f / (float)(p.k * p.k);
     for (int n = 0; n < p.N; ++n) for (int c = 0; c < p.C; ++c) for (int h = 0; h < p.Hs; ++h) for (int w = 0; w < p.Ws; ++w) {
-        int ho = h / p.stride, wo = w / p.stride;
-        bool in = (h - ho * p.stride) < p.k && (w - wo * p.stride) < p.k && ho < p.Ho && wo < p.Wo;
-        p.gx[(size_t)n * p.gx_nstride + ((size_t)c * p.Hs + h) * p.Ws + w] =
-            in ? p.y[(size_t)n * p.y_nstride + ((size_t)c * p.Ho + ho) * p.Wo + wo] / (p.k * p.k) : 0.f;
+        float g = 0.f; bool first = true;
+        if (!p.mask_relu || p.x[(size_t)n * p.x_nstride + ((size_t)c * p.Hs + h) * p.Ws + w] > 0.f)
+            for (int ho = std::max(0, (h - p.k) / p.stride); ho <= std::min(h / p.stride, p.Ho - 1); ++ho)       // (a loose range: the test below decides)
+            for (int wo = std::max(0, (w - p.k) / p.stride); wo <= std::min(w / p.stride, p.Wo - 1); ++wo) {
+                if (h < ho * p.stride || h >= ho * p.stride + p.k || w < wo * p.stride || w >= wo * p.stride + p.k) continue;
+                const float v = p.y[(size_t)n * p.y_nstride + ((size_t)c * p.Ho + ho) * p.Wo + wo];
+                g = first ? v : g + v; first = false;
+            }
+        p.gx[(size_t)n * p.gx_nstride + ((size_t)c * p.Hs + h) * p.Ws + w] = first ? 0.f : g * inv;
     }
     return 0;
 }
