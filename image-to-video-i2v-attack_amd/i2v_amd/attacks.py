@@ -121,6 +121,8 @@ class _ImageGuided(Attack):
                 nets.append(self.engine.build_convnext_net(g, sd, hooks, frames))
             elif isinstance(g, _graphs.MixerSpec):      # MLP-Mixer / ResMLP on the transformer stack: blocks, hooked as ViT's
                 nets.append(self.engine.build_mixer_net(g, sd, hooks, frames))
+            elif isinstance(g, _graphs.CaitSpec):       # CaiT on the transformer stack: self-attention blocks, hooked as ViT's
+                nets.append(self.engine.build_cait_net(g, sd, hooks, frames))
             else:
                 nets.append(self.engine.build_net(g, sd, hooks, frames))
         self._nets, self._net_key, self._max_frames = nets, key, frames

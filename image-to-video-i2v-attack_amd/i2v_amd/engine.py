@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
+from .graphs import CaitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -143,6 +143,35 @@ class Engine:
                                                                  o(w1 if Sh else None), o(b1 if Sh else None), _ptr(w2t, self), o(w1t),
                                                                  o(in_scale), o(in_shift), o(out_scale), channel_tile, self.stream()))
         return dz
+
+    def build_cait_net(self, spec: CaitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "CaitNet":
+        """A CaiT surrogate (`include/i2v_cait.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
+        return self._build(CaitNet, spec, state_dict, list(hook_blocks), max_frames)
+
+    def cait_attention(self, qkv: torch.Tensor, heads: int, scale: float, wl, bl, ww, bw):
+        """Talking-heads attention on its own (`i2v_cait_attention_f32`): qkv (frames, T, 3 heads dh) as the ViT entry takes it, wl / ww
+        (heads, heads), bl / bw (heads) -> (out (frames, T, heads dh), probs (frames, heads, T, ld): post-softmax, pre-mix)."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        assert 3 * heads * dh == C3 and tuple(wl.shape) == tuple(ww.shape) == (heads, heads)
+        ld = (T + 3) // 4 * 4
+        probs = torch.zeros(n, heads, T, ld, dtype=torch.float32, device=qkv.device)
+        out = torch.empty(n, T, heads * dh, dtype=torch.float32, device=qkv.device)
+        _lib.check(self.capi, self.capi.i2v_cait_attention_f32(_ptr(qkv, self), n, T, heads, dh, scale, _ptr(wl, self), _ptr(bl, self),
+                                                               _ptr(ww, self), _ptr(bw, self), _ptr(probs, self), _ptr(out, self), self.stream()))
+        return out, probs
+
+    def cait_attention_bwd(self, qkv: torch.Tensor, probs: torch.Tensor, dout: torch.Tensor, heads: int, scale: float, wl, ww, bw) -> torch.Tensor:
+        """The input gradient of that launch (`i2v_cait_attention_bwd_f32`) from dout = d(out): dqkv (frames, T, 3 heads dh).  The two
+        scratch arrays of the probabilities' size are made here."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        ds, pm = torch.empty_like(probs), torch.empty_like(probs)
+        dqkv = torch.empty_like(qkv)
+        _lib.check(self.capi, self.capi.i2v_cait_attention_bwd_f32(_ptr(qkv, self), _ptr(probs, self), _ptr(dout, self), n, T, heads, dh, scale,
+                                                                   _ptr(wl, self), _ptr(ww, self), _ptr(bw, self), _ptr(ds, self), _ptr(pm, self),
+                                                                   _ptr(dqkv, self), self.stream()))
+        return dqkv
 
     # ---- measurement ----
     KINDS = ("conv_igemm_fwd", "conv_igemm_imggrad", "pool_fwd", "pool_bwd", "addmask", "conv_igemm_dgrad")
@@ -784,6 +813,27 @@ class MixerNet(TokenNet):
         h = C.c_void_p()
         _lib.check(capi, capi.i2v_mixer_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames,
                                                C.byref(h)))
+        return h
+
+    def hook_shape(self, i):
+        return (self.graph.tokens, self.graph.dim, 1)
+
+
+class CaitNet(TokenNet):
+    """A CaiT surrogate: a hook is the residual stream after one self-attention block, (tokens * dim) floats per frame."""
+    _api = "cait"
+
+    def _create(self, spec: CaitSpec, sd, hook_blocks, max_frames):
+        eng, capi = self.eng, self.eng.capi
+        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
+        # native order (include/i2v_cait.h): the stem, pos_embed, then the blocks with gamma_1 / gamma_2 folded; kept alive until the upload
+        w = spec.native_arrays(sd, nb)
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
+        cfg = _lib.CaitConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.ln_eps)
+        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
+        h = C.c_void_p()
+        _lib.check(capi, capi.i2v_cait_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames,
+                                              C.byref(h)))
         return h
 
     def hook_shape(self, i):

@@ -1594,6 +1594,158 @@ def mixer_tiny_twin(kind: str = "mixer", patch: int = 16, in_hw=(64, 64)) -> Mix
 
 
 # ---------------------------------------------------------------------------
+# the CaiT surrogates: self-attention blocks with talking-heads attention and LayerScale, planned on the transformer stack
+# (include/i2v_cait.h)
+# ---------------------------------------------------------------------------
+#: timm 0.5.0's `Cait` models at 224 x 224 (patch 16, MLP ratio 4, head width 48): name -> (dim, self-attention blocks, heads).
+CAIT_MODELS: Dict[str, Tuple[int, int, int]] = {
+    "cait_xxs24_224": (192, 24, 4),
+    "cait_xxs36_224": (192, 36, 4),
+    "cait_s24_224": (384, 24, 8),
+}
+
+
+@dataclass
+class CaitSpec:
+    """timm 0.5.0 `Cait` up to its last self-attention block: patch embedding (patch x patch convolution, stride
+    patch, bias), pos_embed (tokens, dim) added, NO prefix token -- `cls_token` joins only in the two class-attention blocks, which lie
+    behind the last hookable block and never run --, then `blocks` pre-norm blocks
+      x += gamma_1 * proj(THA(LN1 x));  x += gamma_2 * fc2(GELU(fc1(LN2 x)))
+    LayerNorm eps `ln_eps`, exact GELU, THA talking-heads attention: S_h = (scale q_h) k_h^T, S'_g = sum_h proj_l[g][h] S_h + bias,
+    P = softmax over keys, P'_g = sum_h proj_w[g][h] P_h + bias, out_g = P'_g v_g, scale (dim / heads) ** -0.5.
+    `hooks`: depth d (1..4) -> zero-based block d * blocks / 4 - 1 (5, 11, 17, 23 of 24; 8, 17, 26, 35 of 36), whose OUTPUT (the residual
+    stream after it, all tokens) is the hooked feature: tokens * dim floats per frame, token-major."""
+    arch: str
+    img: int
+    patch: int = 16
+    in_chans: int = 3
+    dim: int = 384
+    heads: int = 8
+    blocks: int = 24
+    ln_eps: float = 1e-6
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        if self.img % self.patch or self.patch % 4 or self.dim % self.heads or (self.dim // self.heads) % 4:
+            raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame, patch {self.patch}, width {self.dim}, {self.heads} heads: the "
+                             "patch must divide the frame, and patch and head width must be multiples of 4")
+        if self.blocks % 4:
+            raise ValueError(f"{self.arch}: {self.blocks} blocks: depths 1..4 hook blocks d * blocks / 4 - 1")
+        if not self.hooks:
+            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def tokens(self) -> int:
+        return (self.img // self.patch) ** 2
+
+    @property
+    def mlp(self) -> int:
+        return 4 * self.dim
+
+    def hook_dim(self, i: int = 0) -> int:
+        """Floats per frame of the feature hooked at block i (the same for every block)."""
+        return self.tokens * self.dim
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def block_keys(self, i: int) -> List[str]:
+        """timm's order: the block's own parameters (the LayerScale vectors) ahead of its children's."""
+        p = f"blocks.{i}."
+        return [p + k for k in ("gamma_1", "gamma_2", "norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight",
+                                "attn.proj.bias", "attn.proj_l.weight", "attn.proj_l.bias", "attn.proj_w.weight", "attn.proj_w.bias",
+                                "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last self-attention block, in timm's order (`cls_token`,
+        `blocks_token_only.*`, `norm.*` and `head.*` lie behind every hook and are not used)."""
+        D, H, M = self.dim, self.heads, self.mlp
+        out = {"pos_embed": (1, self.tokens, D), "patch_embed.proj.weight": (D, self.in_chans, self.patch, self.patch),
+               "patch_embed.proj.bias": (D,)}
+        shapes = [(D,), (D,), (D,), (D,), (3 * D, D), (3 * D,), (D, D), (D,), (H, H), (H,), (H, H), (H,), (D,), (D,), (M, D), (M,), (D, M), (D,)]
+        for i in range(self.blocks):
+            out.update(zip(self.block_keys(i), shapes))
+        return out
+
+    def native_arrays(self, sd, n_blocks: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_cait_create` takes for the first `n_blocks` blocks, from a timm-layout state dict, as float32 host tensors: the
+        patch weight and bias, pos_embed as (tokens, dim), then 16 per block -- norm1, qkv, proj_l, proj_w as they lie, `attn.proj` with
+        `gamma_1` folded in (row o of the weight and element o of the bias times gamma_1[o]), norm2, fc1, and `mlp.fc2` with `gamma_2`
+        folded in the same way: LayerScale costs nothing at run time.  The folds are made in float64."""
+        f = lambda k: sd[k].detach().float().cpu()      # noqa: E731
+        out = [f("patch_embed.proj.weight").contiguous(), f("patch_embed.proj.bias").contiguous(),
+               f("pos_embed").reshape(self.tokens, self.dim).contiguous()]
+        for i in range(n_blocks):
+            p = f"blocks.{i}."
+            g1, g2 = f(p + "gamma_1").double(), f(p + "gamma_2").double()
+            out += [f(p + k).contiguous() for k in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj_l.weight",
+                                                    "attn.proj_l.bias", "attn.proj_w.weight", "attn.proj_w.bias")]
+            out += [(f(p + "attn.proj.weight").double() * g1[:, None]).float().contiguous(), (f(p + "attn.proj.bias").double() * g1).float().contiguous()]
+            out += [f(p + k).contiguous() for k in ("norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias")]
+            out += [(f(p + "mlp.fc2.weight").double() * g2[:, None]).float().contiguous(), (f(p + "mlp.fc2.bias").double() * g2).float().contiguous()]
+        return out
+
+    def macs_per_frame(self) -> int:
+        T, D, M, H = self.tokens, self.dim, self.mlp, self.heads
+        per_block = T * D * (3 * D + D + 2 * M) + 2 * T * T * D + 2 * T * T * H * H
+        return T * D * self.in_chans * self.patch ** 2 + self.blocks * per_block
+
+    def workspace_bytes(self, hook_blocks: Sequence[int], frames: int) -> int:
+        """Device bytes `i2v_cait_create` plans for these hooks and `frames` frames (the formula of csrc/i2v_cait.cpp: the weights of the
+        blocks run; per block its input, qkv, the probabilities, the mid stream, the fc1 pre-activation and four statistics per token;
+        the shared scratch -- the last stream, two streams, one MLP-wide, TWO arrays of the probabilities' size, the qkv gradient, the
+        patch rows; one gradient view per hook)."""
+        D, M, T, H, nb = self.dim, self.mlp, self.tokens, self.heads, max(hook_blocks) + 1
+        KP, FT = self.in_chans * self.patch ** 2, frames * T
+        probs = frames * H * T * ((T + 3) // 4 * 4)
+        weights = D * KP + D + T * D + nb * (4 * D * D + 2 * D * M + 9 * D + M + 2 * H * H + 2 * H)
+        per_block = 5 * FT * D + probs + FT * M + 4 * FT
+        shared = 6 * FT * D + FT * M + 2 * probs + FT * KP
+        return 4 * (weights + nb * per_block + shared + len(hook_blocks) * FT * D)
+
+
+def is_cait_name(model_name: str) -> bool:
+    """A name of timm's CaiT vocabulary (`cait.py`), served (`CAIT_MODELS`) or not: `graphs.build` routes these to `cait_named`, which
+    refuses the ones that are not offered with a message that lists the served names."""
+    return model_name in CAIT_MODELS or model_name.startswith("cait")
+
+
+def cait_named(model_name: str, in_hw=(224, 224)) -> CaitSpec:
+    """Any row of `CAIT_MODELS`, at 224 x 224 only.  Refused, each with the reason: the 384 x 384 and 448 x 448 checkpoints
+    (`cait_xxs24_384` ... `cait_m48_448`), and names outside the table."""
+    served = "served: " + ", ".join(CAIT_MODELS)
+    if model_name not in CAIT_MODELS:
+        if model_name.endswith(("_384", "_448")):
+            why = ("the 384 x 384 and 448 x 448 checkpoints are not offered (224 x 224 only: pos_embed is not interpolated, and 576 or "
+                   "784 keys do not fit the attention tile)")
+        else:
+            why = "not a model of this table"
+        raise ValueError(f"CaiT surrogate {model_name!r}: {why}; {served}")
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}); "
+                         "interpolating its pos_embed to another size is not supported")
+    dim, blocks, heads = CAIT_MODELS[model_name]
+    return CaitSpec(model_name, 224, 16, 3, dim, heads, blocks)
+
+
+def cait_tiny_twin(in_hw=(64, 64)) -> CaitSpec:
+    """The same topology at test size ("cait_test"): dim 32, 4 heads of width 8, 8 blocks, so depths 1..4 hook blocks 1, 3, 5, 7; square
+    frames of a multiple of 16 pixels -- 16 tokens at 64 x 64, exactly one attention tile; 80 x 80 gives 25, a tile and a tail.  Not a
+    row of `CAIT_MODELS`."""
+    if in_hw[0] != in_hw[1] or in_hw[0] % 16:
+        raise ValueError(f"the test-size CaiT takes square frames of a multiple of 16 pixels (got {tuple(in_hw)})")
+    return CaitSpec("cait_test", int(in_hw[0]), 16, 3, 32, 4, 8)
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -1632,6 +1784,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return convnext_named(model_name, in_hw)
     if is_mixer_name(model_name):       # extension: timm's all-MLP models, MLP-Mixer and ResMLP (token mixing down the token axis)
         return mixer_named(model_name, in_hw)
+    if is_cait_name(model_name):        # extension: timm's CaiT family (talking-heads attention, LayerScale, no prefix token)
+        return cait_named(model_name, in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -1675,4 +1829,6 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
     if model_name in MIXER_MODELS:      # one twin per kind: the Mixer one follows the name's patch, the ResMLP one has 4 tokens
         kind, patch, _, _ = MIXER_MODELS[model_name]
         return mixer_tiny_twin(kind, patch if kind == "mixer" else 32, in_hw)
+    if model_name in CAIT_MODELS:
+        return cait_tiny_twin(in_hw)
     return build(model_name, in_hw)

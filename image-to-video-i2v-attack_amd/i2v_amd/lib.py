@@ -223,6 +223,26 @@ MIXER_EXPORTS = tuple(_MIXER_PROTOS)
 MIXER_NODE_PROTOS = {k: _MIXER_PROTOS[k] for k in ("i2v_mixer_tokens_f32", "i2v_mixer_tokens_bwd_f32")}
 
 
+class CaitConfig(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("img", "patch", "in_chans", "dim", "heads", "mlp", "blocks")] + [("ln_eps", C.c_float)])
+
+
+# The CaiT surrogates (`include/i2v_cait.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it: the
+# planner runs there on scalar restatements, and so do the two talking-heads attention entries on their own.
+_CAIT_PROTOS = {
+    "i2v_cait_create": ([_I, C.POINTER(CaitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    "i2v_cait_destroy": ([_P], _I),
+    "i2v_cait_workspace_bytes": ([_P], _L),
+    "i2v_cait_forward": ([_P, _P, _I, _P], _I),
+    "i2v_cait_backward": ([_P, _P, _I, _P], _I),
+    "i2v_cait_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+    "i2v_cait_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    "i2v_cait_attention_f32": ([_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P], _I),
+    "i2v_cait_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P], _I),
+}
+CAIT_EXPORTS = tuple(_CAIT_PROTOS)
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
@@ -250,6 +270,7 @@ def load():
         bind(lib, _SWIN_PROTOS)
         bind(lib, _CONVNEXT_PROTOS)
         bind(lib, _MIXER_PROTOS)
+        bind(lib, _CAIT_PROTOS)
         _lib = lib
     return _lib
 

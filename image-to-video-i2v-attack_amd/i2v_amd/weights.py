@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
+from .graphs import CaitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -114,6 +114,37 @@ def _mixer_synthetic(spec: MixerSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _cait_synthetic(spec: CaitSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained CaiT, drawn per key so that every piece of the block's arithmetic shows in the hooks: Linears (the
+    patch embedding as one) ~ fan_in^-0.5 N(0, 1), which keeps a unit-variance stream and puts the attention logits at O(1); `attn.proj`
+    and `mlp.fc2` at half that; LayerNorm gains 1 + 0.1 N(0, 1); biases 0.02 N(0, 1); pos_embed 0.5 N(0, 1).  The LayerScale vectors
+    `gamma_1` / `gamma_2` are uniform on [0.5, 1] with random signs -- timm initialises them at 1e-5 or 1e-6, which would make every
+    block an identity and the tests blind to the kernel.  The talking-heads mixes `attn.proj_l.weight` / `attn.proj_w.weight` are the
+    identity plus 0.25 N(0, 1) per entry, with `proj_l.bias` ~ 0.5 N(0, 1) and `proj_w.bias` ~ 0.02 N(0, 1): far from the identity and
+    the zeros a skipped mix would compute."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.endswith((".gamma_1", ".gamma_2")):
+            sd[k] = (0.5 + 0.5 * torch.rand(*shp, generator=g)) * (torch.randint(0, 2, shp, generator=g).float() * 2 - 1)
+        elif k.endswith(("proj_l.weight", "proj_w.weight")):
+            sd[k] = torch.eye(shp[0]) + 0.25 * torch.randn(*shp, generator=g)
+        elif k.endswith("proj_l.bias"):
+            sd[k] = 0.5 * torch.randn(*shp, generator=g)
+        elif k == "pos_embed":
+            sd[k] = 0.5 * torch.randn(*shp, generator=g)
+        elif k.endswith(("norm1.weight", "norm2.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if k.endswith(("fc2.weight", "attn.proj.weight")) else 1.0) * fan_in ** -0.5)
+    return sd
+
+
 def check_swin_buffers(spec: SwinSpec, sd, where: str) -> None:
     """timm's Swin checkpoints carry the buffers `relative_position_index` and `attn_mask`; they are computed from the geometry here
     and never loaded, so one that differs describes another model: refused by key name."""
@@ -148,6 +179,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _convnext_synthetic(graph, seed)
     if isinstance(graph, MixerSpec):
         return _mixer_synthetic(graph, seed)
+    if isinstance(graph, CaitSpec):
+        return _cait_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":
