@@ -1524,7 +1524,7 @@ __global__ void __launch_bounds__(256) tap_sign_abs_kernel(const float* __restri
     double acc = 0.0;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float v = sm[i];
-        sg[i] = v > 0.f ? 1.f : (v < 0.f ? -1.f : v);                   // torch.sign: +-0 and NaN pass through
+        sg[i] = v > 0.f ? 1.f : (v < 0.f ? -1.f : (v == 0.f ? 0.f : v));  // torch.sign: +0 for either zero, NaN passes through
         acc += (double)fabsf(v);
     }
     red[threadIdx.x] = acc; __syncthreads();

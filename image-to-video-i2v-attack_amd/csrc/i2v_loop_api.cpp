@@ -94,6 +94,7 @@ extern "C" int i2v_std_grad_f32(const float* a, int64_t a_stride, int64_t D, int
 extern "C" int i2v_std_fwd_bwd_f32(const float* a, int64_t a_stride, int64_t D, int frames, int mask_relu,
                                    int accumulate, float* std_out, float* grad, int64_t grad_stride,
                                    void* scratch, void* stream) {
+    BAD_ARG_IF(!a || !std_out || !grad || !scratch || D <= 0 || frames <= 0 || (int64_t)frames * D < 2, " (at least two elements)");
     if (i2v_std_reduce_f32(a, a_stride, D, frames, scratch, stream)) return 1;
     return i2v_std_grad_f32(a, a_stride, D, frames, (int64_t)frames * D, mask_relu, accumulate, std_out, grad,
                             grad_stride, scratch, stream);

@@ -306,7 +306,7 @@ static double tree64d(const double* v) {
 }
 
 int k_cos(const I2VCosParams& p, i2v_stream_t) {
-    const bool vec = ((p.a_nstride | p.b_nstride) & 3) == 0;      // device also requires 16-byte aligned bases (always true there)
+    const bool vec = ((p.a_nstride | p.b_nstride) & 3) == 0 && (((uintptr_t)p.a | (uintptr_t)p.b) & 15) == 0;      // as the device: strides AND bases
     std::vector<float> part((size_t)p.N * p.nblk * 4, 0.f);
     for (int n = 0; n < p.N; ++n) {
         const float* a = p.a + (size_t)n * p.a_nstride; const float* b = p.b + (size_t)n * p.b_nstride;
@@ -853,7 +853,7 @@ int k_tap_perts(const float* adv, const float* videos, float* out, int b, int c,
 }
 int k_tap_sign_abs(const float* smooth, float* sign_out, float* reg, int64_t n, double*, i2v_stream_t) {
     double s = 0.0;
-    for (int64_t i = 0; i < n; ++i) { const float v = smooth[i]; sign_out[i] = v > 0.f ? 1.f : (v < 0.f ? -1.f : v); s += (double)fabsf(v); }
+    for (int64_t i = 0; i < n; ++i) { const float v = smooth[i]; sign_out[i] = v > 0.f ? 1.f : (v < 0.f ? -1.f : (v == 0.f ? 0.f : v)); s += (double)fabsf(v); }
     *reg = (float)s;
     return 0;
 }
