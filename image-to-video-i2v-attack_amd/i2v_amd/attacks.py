@@ -123,6 +123,8 @@ class _ImageGuided(Attack):
                 nets.append(self.engine.build_mixer_net(g, sd, hooks, frames))
             elif isinstance(g, _graphs.CaitSpec):       # CaiT on the transformer stack: self-attention blocks, hooked as ViT's
                 nets.append(self.engine.build_cait_net(g, sd, hooks, frames))
+            elif isinstance(g, _graphs.ConvitSpec):     # ConViT on the transformer stack: blocks, hooked as ViT's; 197 tokens behind the join
+                nets.append(self.engine.build_convit_net(g, sd, hooks, frames))
             else:
                 nets.append(self.engine.build_net(g, sd, hooks, frames))
         self._nets, self._net_key, self._max_frames = nets, key, frames

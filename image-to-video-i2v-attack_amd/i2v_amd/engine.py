@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import CaitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
+from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -171,6 +171,38 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_cait_attention_bwd_f32(_ptr(qkv, self), _ptr(probs, self), _ptr(dout, self), n, T, heads, dh, scale,
                                                                    _ptr(wl, self), _ptr(ww, self), _ptr(bw, self), _ptr(ds, self), _ptr(pm, self),
                                                                    _ptr(dqkv, self), self.stream()))
+        return dqkv
+
+    def build_convit_net(self, spec: ConvitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "ConvitNet":
+        """A ConViT surrogate (`include/i2v_convit.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
+        return self._build(ConvitNet, spec, state_dict, list(hook_blocks), max_frames)
+
+    def convit_attention(self, qkv: torch.Tensor, heads: int, scale: float, c=None, table=None):
+        """Gated positional attention on its own (`i2v_convit_attention_f32`): qkv (frames, T, 3 heads dh) as the ViT entry takes it, c
+        (heads), table (heads, T, ld) non-negative with ld = T rounded up to 4; both None: plain attention -> (out (frames, T, heads dh)
+        = fma(c, Ppatch, table) v, probs (frames, heads, T, ld): Ppatch, the softmax before the blend)."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        ld = (T + 3) // 4 * 4
+        assert 3 * heads * dh == C3 and (table is None or tuple(table.shape) == (heads, T, ld))
+        probs = torch.zeros(n, heads, T, ld, dtype=torch.float32, device=qkv.device)
+        out = torch.empty(n, T, heads * dh, dtype=torch.float32, device=qkv.device)
+        o = lambda t: None if t is None else _ptr(t, self)      # noqa: E731
+        _lib.check(self.capi, self.capi.i2v_convit_attention_f32(_ptr(qkv, self), n, T, heads, dh, scale, o(c), o(table), _ptr(probs, self),
+                                                                 _ptr(out, self), self.stream()))
+        return out, probs
+
+    def convit_attention_bwd(self, qkv: torch.Tensor, probs: torch.Tensor, dout: torch.Tensor, heads: int, scale: float, c=None,
+                             table=None) -> torch.Tensor:
+        """The input gradient of that launch (`i2v_convit_attention_bwd_f32`) from dout = d(out): dqkv (frames, T, 3 heads dh).  The
+        scratch array of the probabilities' size is made here."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        ds = torch.empty_like(probs)
+        dqkv = torch.empty_like(qkv)
+        o = lambda t: None if t is None else _ptr(t, self)      # noqa: E731
+        _lib.check(self.capi, self.capi.i2v_convit_attention_bwd_f32(_ptr(qkv, self), _ptr(probs, self), _ptr(dout, self), n, T, heads, dh, scale,
+                                                                     o(c), o(table), _ptr(ds, self), _ptr(dqkv, self), self.stream()))
         return dqkv
 
     # ---- measurement ----
@@ -838,3 +870,26 @@ class CaitNet(TokenNet):
 
     def hook_shape(self, i):
         return (self.graph.tokens, self.graph.dim, 1)
+
+
+class ConvitNet(TokenNet):
+    """A ConViT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame before the class token joins
+    and ((tokens + 1) * dim) behind it."""
+    _api = "convit"
+
+    def _create(self, spec: ConvitSpec, sd, hook_blocks, max_frames):
+        eng, capi = self.eng, self.eng.capi
+        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
+        # native order (include/i2v_convit.h): the stem, pos_embed, cls_token, then the blocks -- qk and v stacked, the gate folded into
+        # one table and one vector per GPSA block; kept alive until the upload
+        w = spec.native_arrays(sd, nb)
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
+        cfg = _lib.ConvitConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.local_blocks, spec.ln_eps)
+        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
+        h = C.c_void_p()
+        _lib.check(capi, capi.i2v_convit_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames,
+                                                C.byref(h)))
+        return h
+
+    def hook_shape(self, i):
+        return (self.graph.tokens_at(self.hook_tensors[i]), self.graph.dim, 1)

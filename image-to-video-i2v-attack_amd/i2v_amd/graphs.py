@@ -1746,6 +1746,202 @@ def cait_tiny_twin(in_hw=(64, 64)) -> CaitSpec:
 
 
 # ---------------------------------------------------------------------------
+# the ConViT surrogates: gated positional self-attention blocks, then plain blocks behind a class token that joins in mid-stream,
+# planned on the transformer stack (include/i2v_convit.h)
+# ---------------------------------------------------------------------------
+#: timm 0.5.0's `ConViT` models at 224 x 224 (patch 16, 12 blocks of which the first 10 are GPSA, MLP ratio 4, head width 48, no qkv
+#: bias): name -> (dim, heads).
+CONVIT_MODELS: Dict[str, Tuple[int, int]] = {
+    "convit_tiny": (192, 4),
+    "convit_small": (432, 9),
+    "convit_base": (768, 16),
+}
+
+
+@dataclass
+class ConvitSpec:
+    """timm 0.5.0 `ConViT` up to its last block: patch embedding (patch x patch convolution, stride patch, bias),
+    pos_embed (tokens, dim) added, then `blocks` pre-norm blocks  x += proj(attn(LN1 x));  x += fc2(GELU(fc1(LN2 x))),  LayerNorm eps
+    `ln_eps`, exact GELU, no qkv bias.  Blocks 0 .. local_blocks - 1 run on the patch tokens with gated positional self-attention:
+      P_h = (1 - sigma(g_h)) softmax(scale q_h k_h^T) + sigma(g_h) softmax_j(pos_proj_h . r_ij);  P_h /= sum_j P_h;  out_h = P_h v_h
+    with r_ij = (jx - ix, jy - iy, squared distance) on the token grid.  Before block `local_blocks` the stream becomes [cls_token; x]
+    (tokens + 1), and the remaining blocks use plain attention.
+    `hooks`: depth d (1..4) -> zero-based block d * blocks / 4 - 1 (2, 5, 8, 11 of 12), whose OUTPUT (the residual stream after it, all
+    tokens) is the hooked feature: tokens * dim floats per frame before the join, (tokens + 1) * dim behind it, token-major."""
+    arch: str
+    img: int
+    patch: int = 16
+    in_chans: int = 3
+    dim: int = 192
+    heads: int = 4
+    blocks: int = 12
+    local_blocks: int = 10
+    ln_eps: float = 1e-6
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        if self.img % self.patch or self.patch % 4 or self.dim % self.heads or (self.dim // self.heads) % 4:
+            raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame, patch {self.patch}, width {self.dim}, {self.heads} heads: the "
+                             "patch must divide the frame, and patch and head width must be multiples of 4")
+        if self.blocks % 4 or not 1 <= self.local_blocks <= self.blocks:
+            raise ValueError(f"{self.arch}: {self.blocks} blocks, {self.local_blocks} of them local: depths 1..4 hook blocks d * blocks / 4 "
+                             "- 1, and the class token joins before a block 1 .. blocks")
+        if not self.hooks:
+            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def grid(self) -> int:
+        return self.img // self.patch
+
+    @property
+    def tokens(self) -> int:
+        """Patch tokens: what the stream holds before the class token joins."""
+        return self.grid ** 2
+
+    @property
+    def mlp(self) -> int:
+        return 4 * self.dim
+
+    def tokens_at(self, i: int) -> int:
+        """Tokens block i runs on, and the stream after it holds."""
+        return self.tokens + (1 if i >= self.local_blocks else 0)
+
+    def hook_dim(self, i: int = 0) -> int:
+        """Floats per frame of the feature hooked at block i."""
+        return self.tokens_at(i) * self.dim
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def block_keys(self, i: int) -> List[str]:
+        """timm's order: norm1, the attention (`GPSA`: its own parameter gating_param first, as a state dict lists a module's own
+        parameters ahead of its children's, then qk, v, proj, pos_proj as the constructor makes them; `MHSA`: qkv, proj), norm2, mlp."""
+        p = f"blocks.{i}."
+        attn = (("attn.gating_param", "attn.qk.weight", "attn.v.weight", "attn.proj.weight", "attn.proj.bias", "attn.pos_proj.weight",
+                 "attn.pos_proj.bias") if i < self.local_blocks else ("attn.qkv.weight", "attn.proj.weight", "attn.proj.bias"))
+        return [p + k for k in ("norm1.weight", "norm1.bias") + attn + ("norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias",
+                                                                       "mlp.fc2.weight", "mlp.fc2.bias")]
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block, in timm's order (`norm.*` and `head.*` lie behind
+        every hook and are not used)."""
+        D, H, M = self.dim, self.heads, self.mlp
+        out = {"cls_token": (1, 1, D), "pos_embed": (1, self.tokens, D), "patch_embed.proj.weight": (D, self.in_chans, self.patch, self.patch),
+               "patch_embed.proj.bias": (D,)}
+        tail = [(D,), (D,), (M, D), (M,), (D, M), (D,)]
+        for i in range(self.blocks):
+            attn = [(H,), (2 * D, D), (D, D), (D, D), (D,), (H, 3), (H,)] if i < self.local_blocks else [(3 * D, D), (D, D), (D,)]
+            out.update(zip(self.block_keys(i), [(D,), (D,)] + attn + tail))
+        return out
+
+    def rel_indices(self) -> "torch.Tensor":
+        """r_ij (tokens, tokens, 3) in float64: (jx - ix, jy - iy, (jx - ix)^2 + (jy - iy)^2) for token = y * grid + x."""
+        import torch
+        t = torch.arange(self.tokens)
+        x, y = (t % self.grid).double(), (t // self.grid).double()
+        dx, dy = x[None, :] - x[:, None], y[None, :] - y[:, None]
+        return torch.stack([dx, dy, dx * dx + dy * dy], -1)
+
+    def gate_table(self, sd, i: int):
+        """(c (heads), A (heads, tokens, ld)) of GPSA block i in float32, computed in float64: A_h = sigma(g_h) softmax_j(w_h . r_ij) with
+        rows zero-padded to ld = tokens rounded up to 4, c_h = 1 - sigma(g_h).  `pos_proj.bias` is constant along j and cancels inside
+        the softmax, so it is not read."""
+        import torch
+        p = f"blocks.{i}.attn."
+        sig = torch.sigmoid(sd[p + "gating_param"].detach().double().cpu())
+        pos = torch.einsum("ijk,hk->hij", self.rel_indices(), sd[p + "pos_proj.weight"].detach().double().cpu()).softmax(-1)
+        T, ld = self.tokens, (self.tokens + 3) // 4 * 4
+        A = torch.zeros(self.heads, T, ld, dtype=torch.float64)
+        A[:, :, :T] = sig[:, None, None] * pos
+        return (1.0 - sig).float().contiguous(), A.float().contiguous()
+
+    def native_arrays(self, sd, n_blocks: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_convit_create` takes for the first `n_blocks` blocks, from a timm-layout state dict, as float32 host tensors:
+        the patch weight and bias, pos_embed as (tokens, dim), cls_token as (dim); per GPSA block 14 -- norm1, `attn.qk.weight` and
+        `attn.v.weight` stacked into one (3 dim, dim) array (q of head h at row h dh, k at dim + h dh, v at 2 dim + h dh: the layout of
+        a plain qkv), a zero (3 dim) bias, `gate_table`'s c and A, proj, norm2, fc1, fc2 --; per plain block 12 -- the same with
+        `attn.qkv.weight` as it lies and without c and A."""
+        import torch
+        f = lambda k: sd[k].detach().float().cpu()      # noqa: E731
+        out = [f("patch_embed.proj.weight").contiguous(), f("patch_embed.proj.bias").contiguous(),
+               f("pos_embed").reshape(self.tokens, self.dim).contiguous(), f("cls_token").reshape(self.dim).contiguous()]
+        tail = ("attn.proj.weight", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight",
+                "mlp.fc2.bias")
+        for i in range(n_blocks):
+            p = f"blocks.{i}."
+            out += [f(p + "norm1.weight").contiguous(), f(p + "norm1.bias").contiguous()]
+            if i < self.local_blocks:
+                out += [torch.cat([f(p + "attn.qk.weight"), f(p + "attn.v.weight")], 0).contiguous(), torch.zeros(3 * self.dim)]
+                out += list(self.gate_table(sd, i))
+            else:
+                out += [f(p + "attn.qkv.weight").contiguous(), torch.zeros(3 * self.dim)]
+            out += [f(p + k).contiguous() for k in tail]
+        return out
+
+    def macs_per_frame(self) -> int:
+        D, M = self.dim, self.mlp
+        total = self.tokens * D * self.in_chans * self.patch ** 2
+        for i in range(self.blocks):
+            T = self.tokens_at(i)
+            total += T * D * (3 * D + D + 2 * M) + 2 * T * T * D
+        return total
+
+    def workspace_bytes(self, hook_blocks: Sequence[int], frames: int) -> int:
+        """Device bytes `i2v_convit_create` plans for these hooks and `frames` frames (the formula of csrc/i2v_convit.cpp).  With T_b
+        the tokens of block b, ld_b = T_b rounded up to 4 and T_m those of the deepest block run: the weights of the blocks run (a GPSA
+        block adds heads + heads * tokens * ld floats); per block its input, qkv, the probabilities, the mid stream, the fc1
+        pre-activation and four statistics per token, at T_b; the shared scratch at T_m -- the last stream, two streams, one MLP-wide,
+        ONE array of the probabilities' size, the qkv gradient --, the patch rows, and two streams of patch tokens where blocks follow
+        the join; one gradient view per hook at its own token count."""
+        D, M, T, H, nb = self.dim, self.mlp, self.tokens, self.heads, max(hook_blocks) + 1
+        KP, ld = self.in_chans * self.patch ** 2, (T + 3) // 4 * 4
+        nl = min(nb, self.local_blocks)
+        weights = D * KP + D + T * D + D + nb * (4 * D * D + 2 * D * M + 9 * D + M) + nl * (H + H * T * ld)
+        saves = 0
+        for b in range(nb):
+            Tb = self.tokens_at(b)
+            saves += frames * (Tb * (5 * D + M + 4) + H * Tb * ((Tb + 3) // 4 * 4))
+        Tm = self.tokens_at(nb - 1)
+        shared = frames * (Tm * (6 * D + M) + H * Tm * ((Tm + 3) // 4 * 4) + T * KP + (2 * T * D if nb > nl else 0))
+        hooks = sum(frames * self.tokens_at(b) * D for b in hook_blocks)
+        return 4 * (weights + saves + shared + hooks)
+
+
+def is_convit_name(model_name: str) -> bool:
+    """A name of timm's ConViT vocabulary (`convit.py`), served (`CONVIT_MODELS`) or not: `graphs.build` routes these to `convit_named`,
+    which refuses the ones that are not offered with a message that lists the served names."""
+    return model_name in CONVIT_MODELS or model_name.startswith("convit")
+
+
+def convit_named(model_name: str, in_hw=(224, 224)) -> ConvitSpec:
+    """Any row of `CONVIT_MODELS`, at 224 x 224 only; names outside the table are refused with the reason."""
+    if model_name not in CONVIT_MODELS:
+        raise ValueError(f"ConViT surrogate {model_name!r}: not a model of this table; served: " + ", ".join(CONVIT_MODELS))
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}); its positional "
+                         "attention and pos_embed are tied to the 14 x 14 token grid; served: " + ", ".join(CONVIT_MODELS))
+    dim, heads = CONVIT_MODELS[model_name]
+    return ConvitSpec(model_name, 224, 16, 3, dim, heads, 12, 10)
+
+
+def convit_tiny_twin(in_hw=(64, 64)) -> ConvitSpec:
+    """The same topology at test size ("convit_test"): dim 32, 4 heads of width 8, 8 blocks of which the first 6 are GPSA, so depths
+    1..4 hook blocks 1, 3, 5, 7 and depth 4 crosses the join; square frames of a multiple of 16 pixels -- 16 tokens at 64 x 64, exactly
+    one attention tile, and 25 at 80 x 80, a tile and a tail; 17 / 26 behind the join.  Not a row of `CONVIT_MODELS`."""
+    if in_hw[0] != in_hw[1] or in_hw[0] % 16:
+        raise ValueError(f"the test-size ConViT takes square frames of a multiple of 16 pixels (got {tuple(in_hw)})")
+    return ConvitSpec("convit_test", int(in_hw[0]), 16, 3, 32, 4, 8, 6)
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -1786,6 +1982,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return mixer_named(model_name, in_hw)
     if is_cait_name(model_name):        # extension: timm's CaiT family (talking-heads attention, LayerScale, no prefix token)
         return cait_named(model_name, in_hw)
+    if is_convit_name(model_name):      # extension: timm's ConViT family (gated positional attention, a class token that joins at block 10)
+        return convit_named(model_name, in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -1831,4 +2029,6 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return mixer_tiny_twin(kind, patch if kind == "mixer" else 32, in_hw)
     if model_name in CAIT_MODELS:
         return cait_tiny_twin(in_hw)
+    if model_name in CONVIT_MODELS:
+        return convit_tiny_twin(in_hw)
     return build(model_name, in_hw)

@@ -243,6 +243,26 @@ _CAIT_PROTOS = {
 CAIT_EXPORTS = tuple(_CAIT_PROTOS)
 
 
+class ConvitConfig(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("img", "patch", "in_chans", "dim", "heads", "mlp", "blocks", "local_blocks")] + [("ln_eps", C.c_float)])
+
+
+# The ConViT surrogates (`include/i2v_convit.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it:
+# the planner runs there on scalar restatements, and so do the two gated positional attention entries on their own.
+_CONVIT_PROTOS = {
+    "i2v_convit_create": ([_I, C.POINTER(ConvitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    "i2v_convit_destroy": ([_P], _I),
+    "i2v_convit_workspace_bytes": ([_P], _L),
+    "i2v_convit_forward": ([_P, _P, _I, _P], _I),
+    "i2v_convit_backward": ([_P, _P, _I, _P], _I),
+    "i2v_convit_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+    "i2v_convit_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    "i2v_convit_attention_f32": ([_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P], _I),
+    "i2v_convit_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P], _I),
+}
+CONVIT_EXPORTS = tuple(_CONVIT_PROTOS)
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
@@ -271,6 +291,7 @@ def load():
         bind(lib, _CONVNEXT_PROTOS)
         bind(lib, _MIXER_PROTOS)
         bind(lib, _CAIT_PROTOS)
+        bind(lib, _CONVIT_PROTOS)
         _lib = lib
     return _lib
 

@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import CaitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
+from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -145,6 +145,44 @@ def _cait_synthetic(spec: CaitSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _convit_synthetic(spec: ConvitSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained ConViT, drawn per key as `_cait_synthetic` draws: Linears ~ fan_in^-0.5 N(0, 1) (`attn.proj` and
+    `mlp.fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1), pos_embed and cls_token 0.5 N(0, 1).  `attn.v` is an
+    ordinary Linear draw, not timm's identity.  `attn.pos_proj.weight` is timm's local initialisation -- column 2 = -1, and columns 0 /
+    1 on the head's offset in a floor(sqrt(heads)) grid: head p = h1 + k h2 gets column 1 = 2 (h1 - centre) and column 0 = 2 (h2 -
+    centre) -- plus seeded noise, 0.3 N(0, 1) on the two offset columns and 0.1 N(0, 1) on the distance column, so that the x and y
+    columns of every head differ and a transposed grid convention shows.  `attn.gating_param` ~ N(0, 1), so sigma(g) spans the range
+    (timm starts it at 1); `attn.pos_proj.bias` ~ 0.5 N(0, 1), far from the zero a dropped bias would equal."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.endswith("pos_proj.weight"):
+            H = shp[0]
+            ks = int(H ** 0.5)
+            centre = (ks - 1) / 2 if ks % 2 == 0 else ks // 2
+            w = torch.zeros(H, 3)
+            for h1 in range(ks):
+                for h2 in range(ks):
+                    w[h1 + ks * h2] = torch.tensor([2.0 * (h2 - centre), 2.0 * (h1 - centre), -1.0])
+            sd[k] = w + torch.randn(H, 3, generator=g) * torch.tensor([0.3, 0.3, 0.1])
+        elif k.endswith("gating_param"):
+            sd[k] = torch.randn(*shp, generator=g)
+        elif k.endswith("pos_proj.bias"):
+            sd[k] = 0.5 * torch.randn(*shp, generator=g)
+        elif k in ("pos_embed", "cls_token"):
+            sd[k] = 0.5 * torch.randn(*shp, generator=g)
+        elif k.endswith(("norm1.weight", "norm2.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if k.endswith(("fc2.weight", "attn.proj.weight")) else 1.0) * fan_in ** -0.5)
+    return sd
+
+
 def check_swin_buffers(spec: SwinSpec, sd, where: str) -> None:
     """timm's Swin checkpoints carry the buffers `relative_position_index` and `attn_mask`; they are computed from the geometry here
     and never loaded, so one that differs describes another model: refused by key name."""
@@ -181,6 +219,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _mixer_synthetic(graph, seed)
     if isinstance(graph, CaitSpec):
         return _cait_synthetic(graph, seed)
+    if isinstance(graph, ConvitSpec):
+        return _convit_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":

@@ -47,7 +47,8 @@ def arg_parse(argv=None, ucf101=False):
                              + "; and timm's SE-ResNets / SE-ResNeXts: " + ", ".join(graphs.SERESNET_FAMILY) + "; and timm's ConvNeXts at 224 x 224: "
                              + ", ".join(graphs.CONVNEXT_MODELS) + "; and timm's MLP-Mixers and ResMLPs at 224 x 224: "
                              + ", ".join(graphs.MIXER_MODELS) + "; and timm's CaiTs at 224 x 224: "
-                             + ", ".join(graphs.CAIT_MODELS) + ")")
+                             + ", ".join(graphs.CAIT_MODELS) + "; and timm's ConViTs at 224 x 224: "
+                             + ", ".join(graphs.CONVIT_MODELS) + ")")
     # additions (not in the reference)
     parser.add_argument("--anno", type=str, default=os.environ.get("I2V_ANNO", ""),
                         help="sample list csv `path,gt_label,clip_index` (the reference's kinetics400_attack_samples.csv, utils.py:29); without it 400 synthetic names with labels 0..399 are used")
@@ -84,7 +85,8 @@ def arg_parse(argv=None, ucf101=False):
                                        (graphs.is_swin_name, graphs.swin_named, "the last block of stages {}"),
                                        (graphs.is_convnext_name, graphs.convnext_named, "the last block of stages {}"),
                                        (graphs.is_mixer_name, graphs.mixer_named, "blocks {}"),
-                                       (graphs.is_cait_name, graphs.cait_named, "blocks {}")):
+                                       (graphs.is_cait_name, graphs.cait_named, "blocks {}"),
+                                       (graphs.is_convit_name, graphs.convit_named, "blocks {}")):
             if not is_name(args.direction_image_model):
                 continue
             try:
