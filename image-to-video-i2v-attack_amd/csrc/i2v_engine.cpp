@@ -511,5 +511,6 @@ extern "C" size_t i2v_net_workspace_bytes(i2v_handle h, int net) {
 #include "i2v_mixer.cpp"        // (... and the MLP-Mixer / ResMLP planner, on the same restatements and i2v_mixer_host.h)
 #include "i2v_cait.cpp"         // (... and the CaiT planner, on the same restatements and i2v_cait_host.h)
 #include "i2v_convit.cpp"       // (... and the ConViT planner, on the same restatements and i2v_convit_host.h)
+#include "i2v_xcit.cpp"         // (... and the XCiT planner, on the same restatements and i2v_xcit_host.h)
 #undef fail
 #endif

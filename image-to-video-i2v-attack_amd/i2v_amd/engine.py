@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
+from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec, XcitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -204,6 +204,61 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_convit_attention_bwd_f32(_ptr(qkv, self), _ptr(probs, self), _ptr(dout, self), n, T, heads, dh, scale,
                                                                      o(c), o(table), _ptr(ds, self), _ptr(dqkv, self), self.stream()))
         return dqkv
+
+    def build_xcit_net(self, spec: XcitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "XcitNet":
+        """An XCiT surrogate (`include/i2v_xcit.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
+        return self._build(XcitNet, spec, state_dict, list(hook_blocks), max_frames)
+
+    def xcit_attention(self, qkv: torch.Tensor, heads: int, temperature: torch.Tensor):
+        """Cross-covariance attention on its own (`i2v_xcit_attention_f32`): qkv (frames, T, 3 heads dh) as the ViT entry takes it,
+        temperature (heads) -> (out (frames, T, heads dh), probs (frames, heads, dh, dh), gram (frames, heads, dh + 2, dh): the normalised
+        Gram, then the clamped column norms of q and of k)."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        assert 3 * heads * dh == C3
+        gram = torch.zeros(n, heads, dh + 2, dh, dtype=torch.float32, device=qkv.device)
+        probs = torch.zeros(n, heads, dh, dh, dtype=torch.float32, device=qkv.device)
+        out = torch.empty(n, T, heads * dh, dtype=torch.float32, device=qkv.device)
+        _lib.check(self.capi, self.capi.i2v_xcit_attention_f32(_ptr(qkv, self), n, T, heads, dh, _ptr(temperature, self), _ptr(gram, self),
+                                                               _ptr(probs, self), _ptr(out, self), self.stream()))
+        return out, probs, gram
+
+    def xcit_attention_bwd(self, qkv: torch.Tensor, gram: torch.Tensor, probs: torch.Tensor, dout: torch.Tensor, heads: int,
+                           temperature: torch.Tensor) -> torch.Tensor:
+        """The input gradient of that launch (`i2v_xcit_attention_bwd_f32`) from dout = d(out): dqkv (frames, T, 3 heads dh)."""
+        n, T, C3 = qkv.shape
+        dqkv = torch.empty_like(qkv)
+        _lib.check(self.capi, self.capi.i2v_xcit_attention_bwd_f32(_ptr(qkv, self), _ptr(gram, self), _ptr(probs, self), _ptr(dout, self), n, T,
+                                                                   heads, C3 // (3 * heads), _ptr(temperature, self), _ptr(dqkv, self),
+                                                                   self.stream()))
+        return dqkv
+
+    def xcit_dw3(self, x: torch.Tensor, w: torch.Tensor, bias=None, ta=None, ts=None, add=None, ma=None, mu=None) -> torch.Tensor:
+        """The token-major depthwise 3 x 3 launch on its own (`i2v_xcit_dw3_f32`): x (n, H, W, C), w (9, C); the optional input transform
+        ta * gelu(x) + ts, residual `add` and output multiply ma * gelu'(mu)."""
+        n, H, W, Cn = x.shape
+        y = torch.empty_like(x)
+        o = lambda t: None if t is None else _ptr(t, self)      # noqa: E731
+        _lib.check(self.capi, self.capi.i2v_xcit_dw3_f32(_ptr(x, self), n, H, W, Cn, _ptr(w, self), o(bias), o(ta), o(ts), o(add), o(ma), o(mu),
+                                                         _ptr(y, self), self.stream()))
+        return y
+
+    def xcit_stem_gather(self, src: torch.Tensor, nchw: bool = False) -> torch.Tensor:
+        """The stem's 3 x 3 / 2 / pad 1 gather on its own (`i2v_xcit_stem_gather_f32`): src (n, H, W, C), or (n, C, H, W) with `nchw` ->
+        rows (n Ho Wo, 9 C)."""
+        n, H, W, Cn = (src.shape[0], src.shape[2], src.shape[3], src.shape[1]) if nchw else src.shape
+        rows = torch.empty(n * ((H + 1) // 2) * ((W + 1) // 2), 9 * Cn, dtype=torch.float32, device=src.device)
+        _lib.check(self.capi, self.capi.i2v_xcit_stem_gather_f32(_ptr(src, self), _ptr(rows, self), n, H, W, Cn, int(nchw), self.stream()))
+        return rows
+
+    def xcit_stem_scatter(self, drows: torch.Tensor, shape, pre=None, nchw: bool = False, into=None) -> torch.Tensor:
+        """Its transpose (`i2v_xcit_stem_scatter_f32`): drows (n Ho Wo, 9 C) -> the gradient of a source of `shape`, times gelu'(pre) where
+        pre is given; `into` (image layout only) is added to."""
+        n, H, W, Cn = (shape[0], shape[2], shape[3], shape[1]) if nchw else shape
+        dst = into if into is not None else torch.empty(*shape, dtype=torch.float32, device=drows.device)
+        _lib.check(self.capi, self.capi.i2v_xcit_stem_scatter_f32(_ptr(drows, self), None if pre is None else _ptr(pre, self), _ptr(dst, self),
+                                                                  n, H, W, Cn, int(nchw), int(into is not None), self.stream()))
+        return dst
 
     # ---- measurement ----
     KINDS = ("conv_igemm_fwd", "conv_igemm_imggrad", "pool_fwd", "pool_bwd", "addmask", "conv_igemm_dgrad")
@@ -893,3 +948,24 @@ class ConvitNet(TokenNet):
 
     def hook_shape(self, i):
         return (self.graph.tokens_at(self.hook_tensors[i]), self.graph.dim, 1)
+
+
+class XcitNet(TokenNet):
+    """An XCiT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame."""
+    _api = "xcit"
+
+    def _create(self, spec: XcitSpec, sd, hook_blocks, max_frames):
+        eng, capi = self.eng, self.eng.capi
+        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
+        # native order (include/i2v_xcit.h): the BatchNorm-folded stem, the position table, then 21 arrays per block with the three
+        # LayerScales folded; kept alive until the upload
+        w = spec.native_arrays(sd, nb)
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
+        cfg = _lib.XcitConfig(spec.img, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.ln_eps)
+        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
+        h = C.c_void_p()
+        _lib.check(capi, capi.i2v_xcit_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames, C.byref(h)))
+        return h
+
+    def hook_shape(self, i):
+        return (self.graph.tokens, self.graph.dim, 1)

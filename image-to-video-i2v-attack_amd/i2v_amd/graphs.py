@@ -1942,6 +1942,216 @@ def convit_tiny_twin(in_hw=(64, 64)) -> ConvitSpec:
 
 
 # ---------------------------------------------------------------------------
+# the XCiT surrogates: cross-covariance attention (channels attend to channels), a convolutional stem and a depthwise "local patch
+# interaction" per block, planned on the transformer stack (include/i2v_xcit.h)
+# ---------------------------------------------------------------------------
+_XCIT_BASE: Dict[str, Tuple[int, int, int]] = {
+    "xcit_nano_12_p16_224": (128, 12, 4),
+    "xcit_tiny_12_p16_224": (192, 12, 4),
+    "xcit_tiny_24_p16_224": (192, 24, 4),
+    "xcit_small_12_p16_224": (384, 12, 8),
+    "xcit_small_24_p16_224": (384, 24, 8),
+    "xcit_medium_24_p16_224": (512, 24, 8),
+    "xcit_large_24_p16_224": (768, 24, 16),
+}
+#: timm 0.5.0's `XCiT` models at 224 x 224 with patch 16 (MLP ratio 4, qkv bias, LayerScale): name -> (dim, blocks, heads).  Each name has
+#: a `_dist` twin: the same architecture (no distillation token), its own checkpoint file.
+XCIT_MODELS: Dict[str, Tuple[int, int, int]] = {**_XCIT_BASE, **{k + "_dist": v for k, v in _XCIT_BASE.items()}}
+
+BN2D_EPS = 1e-5      # torch's BatchNorm2d default: the stem's and the local patch interaction's
+
+
+@dataclass
+class XcitSpec:
+    """timm 0.5.0 `XCiT` up to its last cross-covariance block.  Stem: four 3 x 3 / stride 2 / pad 1 convolutions
+    without bias (widths dim / 8, dim / 4, dim / 2, dim), each followed by an eval-mode BatchNorm2d, the first three by the exact GELU;
+    then + the Fourier position features of the token grid through a 1 x 1 convolution.  Then `blocks` blocks, LayerNorm eps `ln_eps`:
+      x += gamma1 proj(XCA(norm1 x));  x += gamma3 LPI(norm3 x);  x += gamma2 fc2(gelu(fc1(norm2 x)))
+    XCA: per head the (dh, dh) softmax of temperature * (q / ||q||)^T (k / ||k||), the norms taken per column over the tokens, applied to
+    v's columns.  LPI on the grid: depthwise 3 x 3 with bias, GELU, eval-mode BatchNorm2d, depthwise 3 x 3 with bias.
+    `hooks`: depth d (1..4) -> zero-based block d * blocks / 4 - 1, whose OUTPUT (the residual stream after it) is the hooked feature:
+    tokens * dim floats per frame, token-major.  The class-attention blocks, `cls_token`, `norm.*` and `head.*` lie behind every hook."""
+    arch: str
+    img: int
+    in_chans: int = 3
+    dim: int = 192
+    heads: int = 4
+    blocks: int = 12
+    ln_eps: float = 1e-6
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        if self.img % 16 or self.dim % 8 or self.dim % self.heads or (self.dim // self.heads) % 4 or self.dim // self.heads > 64:
+            raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame, width {self.dim}, {self.heads} heads: the frame must be a multiple "
+                             "of 16 pixels, the width of 8, and the head width a multiple of 4 up to 64")
+        if self.blocks % 4:
+            raise ValueError(f"{self.arch}: {self.blocks} blocks: depths 1..4 hook blocks d * blocks / 4 - 1")
+        if not self.hooks:
+            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
+
+    patch = 16
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def grid(self) -> int:
+        return self.img // 16
+
+    @property
+    def tokens(self) -> int:
+        return self.grid ** 2
+
+    @property
+    def mlp(self) -> int:
+        return 4 * self.dim
+
+    @property
+    def stem_widths(self) -> List[int]:
+        return [self.in_chans, self.dim // 8, self.dim // 4, self.dim // 2, self.dim]
+
+    def hook_dim(self, i: int = 0) -> int:
+        return self.tokens * self.dim
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def block_keys(self, i: int) -> List[str]:
+        """timm's order: the block's own parameters gamma1, gamma3, gamma2 first, then norm1, attn (its own `temperature` first), norm3,
+        local_mp, norm2, mlp.  `local_mp.bn.num_batches_tracked` is not read."""
+        p = f"blocks.{i}."
+        return [p + k for k in ("gamma1", "gamma3", "gamma2", "norm1.weight", "norm1.bias", "attn.temperature", "attn.qkv.weight",
+                                "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm3.weight", "norm3.bias", "local_mp.conv1.weight",
+                                "local_mp.conv1.bias", "local_mp.bn.weight", "local_mp.bn.bias", "local_mp.bn.running_mean",
+                                "local_mp.bn.running_var", "local_mp.conv2.weight", "local_mp.conv2.bias", "norm2.weight", "norm2.bias",
+                                "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter and BatchNorm statistic up to the last block, in timm's order."""
+        D, H, M, cs = self.dim, self.heads, self.mlp, self.stem_widths
+        out = {}
+        for k in range(4):
+            p = f"patch_embed.proj.{2 * k}."
+            out[p + "0.weight"] = (cs[k + 1], cs[k], 3, 3)
+            out.update({p + "1." + n: (cs[k + 1],) for n in ("weight", "bias", "running_mean", "running_var")})
+        out["pos_embeder.token_projection.weight"] = (D, 64, 1, 1)
+        out["pos_embeder.token_projection.bias"] = (D,)
+        shapes = [(D,), (D,), (D,), (D,), (D,), (H, 1, 1), (3 * D, D), (3 * D,), (D, D), (D,), (D,), (D,), (D, 1, 3, 3), (D,), (D,), (D,), (D,),
+                  (D,), (D, 1, 3, 3), (D,), (D,), (D,), (M, D), (M,), (D, M), (D,)]
+        for i in range(self.blocks):
+            out.update(zip(self.block_keys(i), shapes))
+        return out
+
+    def fourier_features(self) -> "torch.Tensor":
+        """(tokens, 64) in float64: timm's `PositionalEncodingFourier` before its 1 x 1 convolution -- hidden 32 per axis, temperature
+        10000, scale 2 pi, coordinates 1 .. grid divided by (grid + 1e-6); sin on even feature indices and cos on odd; y features first."""
+        import math
+        import torch
+        g = self.grid
+        coord = torch.arange(1, g + 1, dtype=torch.float64) / (g + 1e-6) * (2 * math.pi)
+        i = torch.arange(32, dtype=torch.float64)
+        dim_t = 10000.0 ** (2 * torch.div(i, 2, rounding_mode="floor") / 32)
+        arg = coord[:, None] / dim_t[None, :]                                   # (g, 32)
+        feat = torch.where((torch.arange(32) % 2 == 0)[None, :], arg.sin(), arg.cos())
+        fy = feat[:, None, :].expand(g, g, 32)                                  # token (y, x): y features, then x features
+        fx = feat[None, :, :].expand(g, g, 32)
+        return torch.cat([fy, fx], -1).reshape(g * g, 64)
+
+    def native_arrays(self, sd, n_blocks: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_xcit_create` takes for the first `n_blocks` blocks, from a timm-layout state dict, as float32 host tensors,
+        folded in float64: per stem convolution the BatchNorm-folded weight as (C_out, 9 C_in) with column (3 ky + kx) C_in + c and the
+        bias; the position table (tokens, dim); per block 21 -- norm1, qkv, temperature (heads), gamma1-folded proj, norm2, fc1,
+        gamma2-folded fc2, norm3, conv1 as (9, dim) and its bias, the LPI BatchNorm as (a, s), gamma3-folded conv2 as (9, dim) and bias.
+        The LPI BatchNorm cannot go into conv2: conv2 pads the BatchNorm's OUTPUT with zeros, so a tap outside the plane adds 0, not s."""
+        import torch
+        d = lambda k: sd[k].detach().double().cpu()      # noqa: E731
+        f32 = lambda t: t.float().contiguous()           # noqa: E731
+        out = []
+        for k in range(4):
+            p = f"patch_embed.proj.{2 * k}."
+            s = d(p + "1.weight") / torch.sqrt(d(p + "1.running_var") + BN2D_EPS)
+            w = d(p + "0.weight") * s[:, None, None, None]
+            out += [f32(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)), f32(d(p + "1.bias") - d(p + "1.running_mean") * s)]
+        wp = d("pos_embeder.token_projection.weight").reshape(self.dim, 64)
+        out.append(f32(self.fourier_features() @ wp.t() + d("pos_embeder.token_projection.bias")))
+        D = self.dim
+        for i in range(n_blocks):
+            p = f"blocks.{i}."
+            g1, g2, g3 = d(p + "gamma1"), d(p + "gamma2"), d(p + "gamma3")
+            a = d(p + "local_mp.bn.weight") / torch.sqrt(d(p + "local_mp.bn.running_var") + BN2D_EPS)
+            out += [f32(d(p + "norm1.weight")), f32(d(p + "norm1.bias")), f32(d(p + "attn.qkv.weight")), f32(d(p + "attn.qkv.bias")),
+                    f32(d(p + "attn.temperature").reshape(self.heads)),
+                    f32(d(p + "attn.proj.weight") * g1[:, None]), f32(d(p + "attn.proj.bias") * g1),
+                    f32(d(p + "norm2.weight")), f32(d(p + "norm2.bias")), f32(d(p + "mlp.fc1.weight")), f32(d(p + "mlp.fc1.bias")),
+                    f32(d(p + "mlp.fc2.weight") * g2[:, None]), f32(d(p + "mlp.fc2.bias") * g2),
+                    f32(d(p + "norm3.weight")), f32(d(p + "norm3.bias")),
+                    f32(d(p + "local_mp.conv1.weight").reshape(D, 9).t()), f32(d(p + "local_mp.conv1.bias")),
+                    f32(a), f32(d(p + "local_mp.bn.bias") - d(p + "local_mp.bn.running_mean") * a),
+                    f32((d(p + "local_mp.conv2.weight").reshape(D, 9) * g3[:, None]).t()), f32(d(p + "local_mp.conv2.bias") * g3)]
+        return out
+
+    def macs_per_frame(self) -> int:
+        D, M, T, cs = self.dim, self.mlp, self.tokens, self.stem_widths
+        total = sum((self.img >> (k + 1)) ** 2 * 9 * cs[k] * cs[k + 1] for k in range(4))
+        return total + self.blocks * (T * D * (3 * D + D + 2 * M) + 2 * T * D * (D // self.heads) + 18 * T * D)
+
+    def workspace_bytes(self, hook_blocks: Sequence[int], frames: int) -> int:
+        """Device bytes `i2v_xcit_create` plans for these hooks and `frames` frames (the formula of csrc/i2v_xcit.cpp): the folded stem
+        weights and the position table; per block run its 21 arrays and the two mirrored (9, dim) filters; the stem's gathered rows (the
+        largest of the four stages) and the pre-activation and GELU planes of its first three stages; per block its input, qkv, the
+        normalised Gram with two rows of norms, the probabilities, the two mid streams, the LPI pre-activation, the fc1 pre-activation
+        and six statistics per token; the shared scratch -- the last stream, two streams, one MLP-wide, one qkv-wide --; one gradient
+        view per hook."""
+        D, M, T, H, nb, cs = self.dim, self.mlp, self.tokens, self.heads, max(hook_blocks) + 1, self.stem_widths
+        dh = D // H
+        planes = [(self.img >> (k + 1)) ** 2 for k in range(4)]
+        weights = sum(cs[k + 1] * 9 * cs[k] + cs[k + 1] for k in range(4)) + T * D + nb * (12 * D * D + 37 * D + H + 18 * D)
+        stem = frames * (max(planes[k] * 9 * cs[k] for k in range(4)) + 2 * sum(planes[k] * cs[k + 1] for k in range(3)))
+        saves = nb * frames * (T * (11 * D + 6) + H * dh * (2 * dh + 2))
+        shared = frames * T * (6 * D + M)
+        return 4 * (weights + stem + saves + shared + len(hook_blocks) * frames * T * D)
+
+
+def is_xcit_name(model_name: str) -> bool:
+    """A name of timm's XCiT vocabulary (`xcit.py`), served (`XCIT_MODELS`) or not: `graphs.build` routes these to `xcit_named`, which
+    refuses the ones that are not offered with a message that lists the served names."""
+    return model_name.startswith("xcit")
+
+
+def xcit_named(model_name: str, in_hw=(224, 224)) -> XcitSpec:
+    """Any row of `XCIT_MODELS`, at 224 x 224 only; names outside the table are refused with the reason."""
+    served = "; served: " + ", ".join(XCIT_MODELS)
+    if model_name not in XCIT_MODELS:
+        why = "not a model of this table"
+        if "_p8_" in model_name:
+            why += " (patch 8: a three-convolution stem and 784 tokens, not planned)"
+        elif "_384" in model_name:
+            why += " (384 x 384 frames: only the 224 x 224 models are served)"
+        raise ValueError(f"XCiT surrogate {model_name!r}: {why}" + served)
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}); its checkpoint is the "
+                         "224 x 224 model's" + served)
+    dim, blocks, heads = XCIT_MODELS[model_name]
+    return XcitSpec(model_name, 224, 3, dim, heads, blocks)
+
+
+def xcit_tiny_twin(in_hw=(64, 64)) -> XcitSpec:
+    """The same topology at test size, 8 blocks (depths 1..4 hook blocks 1, 3, 5, 7): "xcit_test" on square frames of a multiple of 16
+    pixels -- at 64 x 64 4 x 4 = 16 tokens, dim 32, 4 heads of 8 -- and "xcit_test_80" at 80 x 80 -- 5 x 5 = 25 tokens (an odd plane, no
+    multiple of 4 or 16), dim 48, 4 heads of 12, stem rows of 27 / 54 / 108 / 216.  Not rows of `XCIT_MODELS`."""
+    if in_hw[0] != in_hw[1] or in_hw[0] % 16:
+        raise ValueError(f"the test-size XCiT takes square frames of a multiple of 16 pixels (got {tuple(in_hw)})")
+    if int(in_hw[0]) == 80:
+        return XcitSpec("xcit_test_80", 80, 3, 48, 4, 8)
+    return XcitSpec("xcit_test", int(in_hw[0]), 3, 32, 4, 8)
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -1984,6 +2194,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return cait_named(model_name, in_hw)
     if is_convit_name(model_name):      # extension: timm's ConViT family (gated positional attention, a class token that joins at block 10)
         return convit_named(model_name, in_hw)
+    if is_xcit_name(model_name):        # extension: timm's XCiT family (cross-covariance attention, a convolutional stem, LPI)
+        return xcit_named(model_name, in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -2031,4 +2243,6 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return cait_tiny_twin(in_hw)
     if model_name in CONVIT_MODELS:
         return convit_tiny_twin(in_hw)
+    if model_name in XCIT_MODELS:
+        return xcit_tiny_twin(in_hw)
     return build(model_name, in_hw)

@@ -263,6 +263,30 @@ _CONVIT_PROTOS = {
 CONVIT_EXPORTS = tuple(_CONVIT_PROTOS)
 
 
+class XcitConfig(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("img", "in_chans", "dim", "heads", "mlp", "blocks")] + [("ln_eps", C.c_float)])
+
+
+# The XCiT surrogates (`include/i2v_xcit.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it: the
+# planner runs there on scalar restatements, and so do the kernel entries on their own -- cross-covariance attention forward and
+# backward, the depthwise 3 x 3 launch, and the stem's gather / scatter pair.
+_XCIT_PROTOS = {
+    "i2v_xcit_create": ([_I, C.POINTER(XcitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    "i2v_xcit_destroy": ([_P], _I),
+    "i2v_xcit_workspace_bytes": ([_P], _L),
+    "i2v_xcit_forward": ([_P, _P, _I, _P], _I),
+    "i2v_xcit_backward": ([_P, _P, _I, _P], _I),
+    "i2v_xcit_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+    "i2v_xcit_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    "i2v_xcit_attention_f32": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
+    "i2v_xcit_attention_bwd_f32": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P], _I),
+    "i2v_xcit_dw3_f32": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "i2v_xcit_stem_gather_f32": ([_P, _P, _I, _I, _I, _I, _I, _P], _I),
+    "i2v_xcit_stem_scatter_f32": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
+}
+XCIT_EXPORTS = tuple(_XCIT_PROTOS)
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
@@ -292,6 +316,7 @@ def load():
         bind(lib, _MIXER_PROTOS)
         bind(lib, _CAIT_PROTOS)
         bind(lib, _CONVIT_PROTOS)
+        bind(lib, _XCIT_PROTOS)
         _lib = lib
     return _lib
 

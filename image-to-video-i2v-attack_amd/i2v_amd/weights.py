@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec
+from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec, XcitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -183,6 +183,41 @@ def _convit_synthetic(spec: ConvitSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _xcit_synthetic(spec: XcitSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained XCiT, drawn per key as `_cait_synthetic` draws: Linears and convolutions ~ fan_in^-0.5 N(0, 1)
+    (`attn.proj` and `mlp.fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1) -- the depthwise convolutions' 0.1
+    N(0, 1), so that a dropped bias shows --, BatchNorm gains uniform on (0.5, 1.5), shifts and running means 0.1 N(0, 1), running
+    variances uniform on (0.5, 1.5).  The LayerScales gamma1 / gamma2 / gamma3 are uniform on (0.5, 1.5) -- timm starts them at 1 (or
+    1e-5 for the 24-block models) and they train away from it --, each drawn on its own so that exchanging two of them shows;
+    `attn.temperature` is uniform on (0.5, 4), so that the softmax over channels is neither flat nor one-hot."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.endswith(("gamma1", "gamma2", "gamma3", "running_var")) or ".bn.weight" in k or (k.startswith("patch_embed") and k.endswith("1.weight")):
+            sd[k] = 0.5 + torch.rand(*shp, generator=g)
+        elif k.endswith("temperature"):
+            sd[k] = 0.5 + 3.5 * torch.rand(*shp, generator=g)
+        elif k.endswith("running_mean") or ".bn.bias" in k or (k.startswith("patch_embed") and k.endswith("1.bias")):
+            sd[k] = 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith(("norm1.weight", "norm2.weight", "norm3.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith(("conv1.bias", "conv2.bias")):
+            sd[k] = 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if k.endswith(("fc2.weight", "attn.proj.weight")) else 1.0) * fan_in ** -0.5)
+    return sd
+
+
+#: timm renamed XCiT's `pos_embeder` to `pos_embed` after 0.5.0: the later spelling of the same two arrays is accepted
+XCIT_KEY_ALIASES = {"pos_embed.token_projection.weight": "pos_embeder.token_projection.weight",
+                    "pos_embed.token_projection.bias": "pos_embeder.token_projection.bias"}
+
+
 def check_swin_buffers(spec: SwinSpec, sd, where: str) -> None:
     """timm's Swin checkpoints carry the buffers `relative_position_index` and `attn_mask`; they are computed from the geometry here
     and never loaded, so one that differs describes another model: refused by key name."""
@@ -221,6 +256,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _cait_synthetic(graph, seed)
     if isinstance(graph, ConvitSpec):
         return _convit_synthetic(graph, seed)
+    if isinstance(graph, XcitSpec):
+        return _xcit_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":
@@ -289,6 +326,8 @@ def load_state_dict(graph: Graph, seed=None, keep_head: bool = False) -> Dict[st
         if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):
             sd = sd["state_dict"]
         shapes = graph.param_shapes()
+        if isinstance(graph, XcitSpec):
+            sd = dict(sd, **{new: sd[old] for old, new in XCIT_KEY_ALIASES.items() if old in sd and new not in sd})
         missing = [k for k in shapes if k not in sd]
         if missing:
             raise KeyError(f"{path}: missing keys {missing[:4]}...")
