@@ -1,8 +1,9 @@
 // What the transformer planners need where there is no HIP (the host simulation's one-file build, g++): a stand-in for the few runtime
 // calls of i2v_xf.h on host memory, and the shared launches the ConvNeXt planner uses -- vit_gemm, the LayerNorm pair, vit_patchify and
 // the 2 x 2 gather / scatter -- as plain scalar C++, in the style of i2v_se_host.h and i2v_convnext_host.h.  The same definitions as the
-// kernels (i2v_vit_kernels.h, i2v_swin_kernels.h); the ORDER of their sums is the simplest one (one fma chain in increasing k; a plain
-// running sum over a row's channels) and is NOT the device's, so these are held to the float64 bound, not to the device's bits.
+// kernels (i2v_vit_kernels.h, i2v_swin_kernels.h); the ORDER of their sums is a simple one (one fma chain in increasing k; a row's
+// channels as 64 interleaved partial sums and a pairwise tree over them, xf_host_rowsum) and is NOT the device's, so these are held to
+// the float64 bound, not to the device's bits.
 // Window attention, softmax and the prefix rows have no host form: ViT and Swin stay device-only.
 #pragma once
 #include <math.h>
@@ -11,6 +12,7 @@
 #include <string.h>
 
 #include "i2v_hip_stub.h"
+#include "i2v_kernels.h"         // i2v_api_fail
 #include "i2v_vit_kernels.h"
 #include "i2v_swin_kernels.h"
 
@@ -24,6 +26,13 @@ inline int vit_launch_check(const char*) { return 0; }
 inline int vit_gemm(VitGemm p, hipStream_t) {
     if (p.M <= 0 || p.N <= 0 || p.batch <= 0) return 0;
     if (p.nb_in <= 0) p.nb_in = 1;
+    // the device launch's refusals, in its order and its words (i2v_vit.hip)
+    if (p.a_sk != 1 && p.a_sm != 1) return i2v_api_fail("vit_gemm: A must be contiguous along M or K");
+    if (p.b_sk != 1 && p.b_sn != 1) return i2v_api_fail("vit_gemm: B must be contiguous along K or N");
+    if (p.mode == VIT_EPI_GELU && !p.C2) return i2v_api_fail("vit_gemm: the GELU epilogue needs its second output");
+    if (p.mode == VIT_EPI_GELU_BWD && !p.H) return i2v_api_fail("vit_gemm: the GELU backward epilogue needs the pre-activation");
+    if (p.K <= 0) return i2v_api_fail("vit_gemm: K must be positive");
+    if (p.batch > 65535) return i2v_api_fail("vit_gemm: grid too large");
     for (int b = 0; b < p.batch; ++b) {
         const int64_t bo = b / p.nb_in, bi = b % p.nb_in;
         const float* A = p.A + bo * p.a_bo + bi * p.a_bi;
@@ -45,15 +54,26 @@ inline int vit_gemm(VitGemm p, hipStream_t) {
     return 0;
 }
 
+// The sum of term(c) over a row's C channels: 64 partial sums over the channels c % 64, then a pairwise tree.  One running sum over a
+// wide row loses what LayerNorm needs from it: over 770 channels of mean 100 and spread 0.01 its mean is off by 2e-5, a fifth of a
+// percent of the spread, which the variance then takes for signal (rstd off by 2.2e-6, dx by 8e-5 of its largest element, where plain
+// float32 torch is within 2.1e-7 and 1.5e-5: tests/xf_cases.py, ln-r4-C770-mean100).
+template <class Term>
+inline float xf_host_rowsum(int C, Term term) {
+    float part[64];
+    for (int l = 0; l < 64; ++l) part[l] = 0.f;
+    for (int c = 0; c < C; ++c) part[c & 63] = part[c & 63] + term(c);
+    for (int o = 32; o > 0; o >>= 1)
+        for (int l = 0; l < o; ++l) part[l] = part[l] + part[l + o];
+    return part[0];
+}
+
 inline int vit_layernorm(const float* x, int64_t rows, int C, const float* gamma, const float* beta, float eps, float* out, float* mean,
                          float* rstd, hipStream_t) {
     for (int64_t r = 0; r < rows; ++r) {
         const float* xr = x + r * C;
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s = s + xr[c];
-        const float mu = s / (float)C;
-        float q = 0.f;
-        for (int c = 0; c < C; ++c) q = fmaf(xr[c] - mu, xr[c] - mu, q);
+        const float mu = xf_host_rowsum(C, [&](int c) { return xr[c]; }) / (float)C;
+        const float q = xf_host_rowsum(C, [&](int c) { return (xr[c] - mu) * (xr[c] - mu); });
         const float rs = 1.f / sqrtf(q / (float)C + eps);
         for (int c = 0; c < C; ++c) out[r * C + c] = (xr[c] - mu) * rs * gamma[c] + beta[c];
         mean[r] = mu;
@@ -66,12 +86,8 @@ inline int vit_layernorm_bwd(const float* dy, const float* x, const float* mean,
                              const float* add0, const float* add1, float* dx, hipStream_t) {
     for (int64_t r = 0; r < rows; ++r) {
         const float mu = mean[r], rs = rstd[r];
-        float s1 = 0.f, s2 = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float g = dy[r * C + c] * gamma[c];
-            s1 = s1 + g;
-            s2 = fmaf(g, (x[r * C + c] - mu) * rs, s2);
-        }
+        const float s1 = xf_host_rowsum(C, [&](int c) { return dy[r * C + c] * gamma[c]; });
+        const float s2 = xf_host_rowsum(C, [&](int c) { return (dy[r * C + c] * gamma[c]) * ((x[r * C + c] - mu) * rs); });
         const float m1 = s1 / (float)C, m2 = s2 / (float)C;
         for (int c = 0; c < C; ++c) {
             const int64_t o = r * C + c;

@@ -287,6 +287,26 @@ _XCIT_PROTOS = {
 XCIT_EXPORTS = tuple(_XCIT_PROTOS)
 
 
+class XfGemmDesc(C.Structure):
+    _fields_ = ([("A", _P)] + [(n, _L) for n in ("a_bo", "a_bi", "a_sm", "a_sk")] + [("B", _P)] + [(n, _L) for n in ("b_bo", "b_bi", "b_sk", "b_sn")]
+                + [("C", _P)] + [(n, _L) for n in ("c_bo", "c_bi", "c_sm")] + [(n, _P) for n in ("bias", "R", "C2", "H")]
+                + [(n, C.c_int32) for n in ("M", "N", "K", "batch", "nb_in")] + [("alpha", _F), ("mode", C.c_int32)])
+
+
+# The shared transformer launches on their own (`include/i2v_xf_launch.h`): a header of its own, kept apart from EXPORTS.  The host
+# simulation exports XF_HOST_PROTOS -- the launches that have a scalar restatement; the softmax pair is the device library's alone.
+_XF_PROTOS = {
+    "i2v_xf_gemm_f32": ([C.POINTER(XfGemmDesc), _P], _I),
+    "i2v_xf_layernorm_f32": ([_P, _L, _I, _P, _P, _F, _P, _P, _P, _P], _I),
+    "i2v_xf_layernorm_bwd_f32": ([_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P], _I),
+    "i2v_xf_patchify_f32": ([_P, _P, _I, _I, _I, _I, _I, _P, _I, _P], _I),
+    "i2v_xf_softmax_f32": ([_P, _L, _I, _I, _P], _I),
+    "i2v_xf_softmax_bwd_f32": ([_P, _P, _L, _I, _I, _F, _P], _I),
+}
+XF_EXPORTS = tuple(_XF_PROTOS)
+XF_HOST_PROTOS = {k: v for k, v in _XF_PROTOS.items() if "softmax" not in k}
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
@@ -317,6 +337,7 @@ def load():
         bind(lib, _CAIT_PROTOS)
         bind(lib, _CONVIT_PROTOS)
         bind(lib, _XCIT_PROTOS)
+        bind(lib, _XF_PROTOS)
         _lib = lib
     return _lib
 
