@@ -127,6 +127,8 @@ class _ImageGuided(Attack):
                 nets.append(self.engine.build_convit_net(g, sd, hooks, frames))
             elif isinstance(g, _graphs.XcitSpec):       # XCiT on the transformer stack: cross-covariance blocks, hooked as ViT's
                 nets.append(self.engine.build_xcit_net(g, sd, hooks, frames))
+            elif isinstance(g, _graphs.TwinsSpec):      # Twins on the transformer stack: stages, hooked as Swin's
+                nets.append(self.engine.build_twins_net(g, sd, hooks, frames))
             else:
                 nets.append(self.engine.build_net(g, sd, hooks, frames))
         self._nets, self._net_key, self._max_frames = nets, key, frames

@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec, XcitSpec
+from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -259,6 +259,62 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_xcit_stem_scatter_f32(_ptr(drows, self), None if pre is None else _ptr(pre, self), _ptr(dst, self),
                                                                   n, H, W, Cn, int(nchw), int(into is not None), self.stream()))
         return dst
+
+    def build_twins_net(self, spec: TwinsSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "TwinsNet":
+        """A Twins surrogate (`include/i2v_twins.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
+        return self._build(TwinsNet, spec, state_dict, list(hook_stages), max_frames)
+
+    def twins_attention(self, q: torch.Tensor, kv: torch.Tensor, heads: int, scale: float = None) -> torch.Tensor:
+        """Sub-sampled attention on its own (`i2v_twins_attention_f32`): q (frames, Tq, heads dh), kv (frames, Tk, 2 heads dh) ->
+        out (frames, Tq, heads dh); `scale` defaults to dh^-0.5."""
+        n, Tq, Cn = q.shape
+        dh = Cn // heads
+        assert heads * dh == Cn and kv.shape[0] == n and kv.shape[2] == 2 * Cn
+        out = torch.empty_like(q)
+        _lib.check(self.capi, self.capi.i2v_twins_attention_f32(_ptr(q, self), _ptr(kv, self), n, Tq, kv.shape[1], heads, dh,
+                                                                dh ** -0.5 if scale is None else scale, _ptr(out, self), self.stream()))
+        return out
+
+    def twins_attention_bwd(self, q: torch.Tensor, kv: torch.Tensor, dout: torch.Tensor, heads: int, scale: float = None):
+        """The input gradients of that launch (`i2v_twins_attention_bwd_f32`) from dout = d(out): (dq as q, dkv as kv)."""
+        n, Tq, Cn = q.shape
+        dh = Cn // heads
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        _lib.check(self.capi, self.capi.i2v_twins_attention_bwd_f32(_ptr(q, self), _ptr(kv, self), _ptr(dout, self), n, Tq, kv.shape[1], heads,
+                                                                    dh, dh ** -0.5 if scale is None else scale, _ptr(dq, self),
+                                                                    _ptr(dkv, self), self.stream()))
+        return dq, dkv
+
+    def twins_block_gather(self, x: torch.Tensor, s: int) -> torch.Tensor:
+        """The s x s block gather on its own (`i2v_twins_block_gather_f32`): x (n, H, W, C) -> rows (n H/s W/s, s s C)."""
+        n, H, W, Cn = x.shape
+        rows = torch.empty(n * (H // s) * (W // s), s * s * Cn, dtype=torch.float32, device=x.device)
+        _lib.check(self.capi, self.capi.i2v_twins_block_gather_f32(_ptr(x, self), _ptr(rows, self), n, H, W, Cn, s, self.stream()))
+        return rows
+
+    def twins_block_scatter(self, drows: torch.Tensor, shape, s: int, into=None) -> torch.Tensor:
+        """Its inverse (`i2v_twins_block_scatter_f32`): drows (n H/s W/s, s s C) -> a plane of `shape` (n, H, W, C); `into` is added to."""
+        n, H, W, Cn = shape
+        dst = into if into is not None else torch.empty(*shape, dtype=torch.float32, device=drows.device)
+        _lib.check(self.capi, self.capi.i2v_twins_block_scatter_f32(_ptr(drows, self), _ptr(dst, self), n, H, W, Cn, s, int(into is not None),
+                                                                    self.stream()))
+        return dst
+
+    def twins_window_attention(self, qkv: torch.Tensor, grid: int, window: int, heads: int, dout: torch.Tensor = None) -> torch.Tensor:
+        """Window attention at shift 0 without a table (`i2v_twins_window_attention_f32`; with `dout` its input gradient,
+        `i2v_twins_window_attention_bwd_f32`): qkv (frames, grid^2, 3 heads dh) -> out (frames, grid^2, heads dh), or dqkv as qkv."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        zeros = torch.zeros((2 * window - 1) ** 2 * heads, dtype=torch.float32, device=qkv.device)
+        if dout is None:
+            out = torch.empty(n, T, heads * dh, dtype=torch.float32, device=qkv.device)
+            _lib.check(self.capi, self.capi.i2v_twins_window_attention_f32(_ptr(qkv, self), n, grid, grid, window, heads, dh, _ptr(zeros, self),
+                                                                           _ptr(out, self), self.stream()))
+            return out
+        dqkv = torch.empty_like(qkv)
+        _lib.check(self.capi, self.capi.i2v_twins_window_attention_bwd_f32(_ptr(qkv, self), _ptr(dout, self), n, grid, grid, window, heads, dh,
+                                                                           _ptr(zeros, self), _ptr(dqkv, self), self.stream()))
+        return dqkv
 
     # ---- measurement ----
     KINDS = ("conv_igemm_fwd", "conv_igemm_imggrad", "pool_fwd", "pool_bwd", "addmask", "conv_igemm_dgrad")
@@ -969,3 +1025,29 @@ class XcitNet(TokenNet):
 
     def hook_shape(self, i):
         return (self.graph.tokens, self.graph.dim, 1)
+
+
+class TwinsNet(TokenNet):
+    """A Twins surrogate: a hook is the stream after the last block of a stage, before the next patch embedding, (grid^2 * width) floats
+    per frame."""
+    _api = "twins"
+
+    def _create(self, spec: TwinsSpec, sd, hook_stages, max_frames):
+        eng, capi = self.eng, self.eng.capi
+        ns = min(max(hook_stages) + 1, spec.stages)      # (a hook outside the stages is the library's to refuse)
+        # native order (include/i2v_twins.h): per stage the embedding, the blocks with the sr convolution repacked to the block gather's
+        # column order, and the position encoding's filter as (9, dim) behind block 0; kept alive until the upload
+        w = spec.native_arrays(sd, ns)
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
+        four = lambda v: (C.c_int32 * 4)(*v)      # noqa: E731
+        dims, heads, mlp, depths, sr = spec.config_lists()
+        cfg = _lib.TwinsConfig(spec.img, spec.in_chans, spec.patch, spec.stages, spec.window, four(dims), four(heads), four(mlp), four(depths),
+                               four(sr), spec.ln_eps, spec.pe_eps)
+        hs = (C.c_int32 * len(hook_stages))(*hook_stages)
+        h = C.c_void_p()
+        _lib.check(capi, capi.i2v_twins_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hs, len(hook_stages), max_frames, C.byref(h)))
+        return h
+
+    def hook_shape(self, i):
+        st = self.hook_tensors[i]
+        return (self.graph.tokens(st), self.graph.width(st), 1)

@@ -2152,6 +2152,275 @@ def xcit_tiny_twin(in_hw=(64, 64)) -> XcitSpec:
 
 
 # ---------------------------------------------------------------------------
+# the Twins surrogates: a four-stage pyramid whose global attention takes its keys from a sub-sampled plane (rectangular attention),
+# with a depthwise conditional position encoding per stage, planned on the transformer stack (include/i2v_twins.h)
+# ---------------------------------------------------------------------------
+#: timm 0.5.0's `Twins` models at 224 x 224 (patch sizes 4, 2, 2, 2; sr_ratios 8, 4, 2, 1): name -> (dims, heads, MLP ratios, depths,
+#: window).  Window 0 (PCPVT): every block is global sub-sampled attention; window 7 (SVT): block j of a stage is locally-grouped
+#: attention for even j and global sub-sampled attention for odd j.
+TWINS_MODELS: Dict[str, Tuple[Tuple[int, ...], Tuple[int, ...], Tuple[int, ...], Tuple[int, ...], int]] = {
+    "twins_pcpvt_small": ((64, 128, 320, 512), (1, 2, 5, 8), (8, 8, 4, 4), (3, 4, 6, 3), 0),
+    "twins_pcpvt_base": ((64, 128, 320, 512), (1, 2, 5, 8), (8, 8, 4, 4), (3, 4, 18, 3), 0),
+    "twins_pcpvt_large": ((64, 128, 320, 512), (1, 2, 5, 8), (8, 8, 4, 4), (3, 8, 27, 3), 0),
+    "twins_svt_small": ((64, 128, 256, 512), (2, 4, 8, 16), (4, 4, 4, 4), (2, 2, 10, 4), 7),
+    "twins_svt_base": ((96, 192, 384, 768), (3, 6, 12, 24), (4, 4, 4, 4), (2, 2, 18, 2), 7),
+    "twins_svt_large": ((128, 256, 512, 1024), (4, 8, 16, 32), (4, 4, 4, 4), (2, 2, 18, 2), 7),
+}
+
+
+@dataclass
+class TwinsSpec:
+    """timm 0.5.0 `Twins` up to its last block.  Stage k: `patch_embeds.k`, a convolution with kernel = stride =
+    patch (4 for stage 0, 2 after) and LayerNorm eps `pe_eps`; then `depths[k]` pre-norm blocks at width `dims[k]` (norms eps `ln_eps`,
+    exact GELU, MLP ratio `mlp_ratios[k]`); `pos_block.k` after block 0: x += dwconv3x3(x) + bias on the grid.
+    Block j's attention is global sub-sampled attention (GSA) where `window` is 0 or j is odd: `attn.q`, and `attn.kv` applied to the
+    plane after `attn.sr` (a convolution with kernel = stride = sr_ratios[k]) and `attn.norm` (eps `pe_eps`) where sr > 1 -- grid^2
+    queries against (grid / sr)^2 keys --; else locally-grouped attention (LSA): `attn.qkv` inside window x window windows, no shift
+    and no bias table.
+    `hooks`: depth d (1..4) -> zero-based stage d - 1, whose last block's OUTPUT, before the next patch embedding, is the hooked
+    feature: grid_k^2 * dims[k] floats per frame, token-major.  `norm.*` and `head.*` lie behind every hook."""
+    arch: str
+    img: int
+    dims: Tuple[int, ...] = (64, 128, 320, 512)
+    heads: Tuple[int, ...] = (1, 2, 5, 8)
+    mlp_ratios: Tuple[int, ...] = (8, 8, 4, 4)
+    depths: Tuple[int, ...] = (3, 4, 6, 3)
+    window: int = 0
+    sr_ratios: Tuple[int, ...] = (8, 4, 2, 1)
+    in_chans: int = 3
+    patch: int = 4
+    ln_eps: float = 1e-6
+    pe_eps: float = 1e-5
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        self.dims, self.heads, self.mlp_ratios = tuple(self.dims), tuple(self.heads), tuple(self.mlp_ratios)
+        self.depths, self.sr_ratios = tuple(self.depths), tuple(self.sr_ratios)
+        if not (len(self.dims) == len(self.heads) == len(self.mlp_ratios) == len(self.depths) == len(self.sr_ratios) == 4):
+            raise ValueError(f"{self.arch}: dims, heads, MLP ratios, depths and sr_ratios must name the same 4 stages")
+        for k in range(4):
+            g, sr, dh = self.grid(k), self.sr_ratios[k], self.dims[k] // self.heads[k]
+            if g * (self.patch << k) != self.img or g % sr or (g // sr) ** 2 > 64:
+                raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame does not give stage {k} a grid of whole {sr} x {sr} "
+                                 "blocks with at most 64 of them")
+            if self.dims[k] % self.heads[k] or dh % 4 or dh > 64:
+                raise ValueError(f"{self.arch}: width {self.dims[k]} of stage {k} under {self.heads[k]} heads: the head width must be "
+                                 "a multiple of 4 up to 64")
+            if self.window and (g % self.window or (self.window, dh) not in ((7, 32), (4, 16))):
+                raise ValueError(f"{self.arch}: stage {k} (grid {g}, head width {dh}) under window {self.window}: whole windows of 7 "
+                                 "at head width 32 or of 4 at head width 16")
+        if not self.hooks:
+            self.hooks = {d: d - 1 for d in (1, 2, 3, 4)}
+
+    stages = 4
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    def grid(self, k: int) -> int:
+        return (self.img // self.patch) >> k
+
+    def width(self, k: int) -> int:
+        return self.dims[k]
+
+    def tokens(self, k: int) -> int:
+        return self.grid(k) ** 2
+
+    def keys_per_frame(self, k: int) -> int:
+        """Keys (and values) a query of stage k's global sub-sampled attention attends to."""
+        return (self.grid(k) // self.sr_ratios[k]) ** 2
+
+    def mlp(self, k: int) -> int:
+        return self.mlp_ratios[k] * self.dims[k]
+
+    def is_lsa(self, k: int, j: int) -> bool:
+        """Block j of stage k is locally-grouped (window) attention."""
+        return bool(self.window) and j % 2 == 0
+
+    def hook_dim(self, k: int) -> int:
+        """Floats per frame of the feature hooked at stage k."""
+        return self.tokens(k) * self.dims[k]
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based stage whose last block depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def embed_keys(self, k: int) -> List[str]:
+        p = f"patch_embeds.{k}."
+        return [p + "proj.weight", p + "proj.bias", p + "norm.weight", p + "norm.bias"]
+
+    def block_keys(self, k: int, j: int) -> List[str]:
+        """timm's order: norm1, attn (GSA: q, kv, proj, then sr and norm where sr > 1; LSA: qkv, proj), norm2, mlp."""
+        if self.is_lsa(k, j):
+            attn = ["attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias"]
+        else:
+            attn = ["attn.q.weight", "attn.q.bias", "attn.kv.weight", "attn.kv.bias", "attn.proj.weight", "attn.proj.bias"]
+            if self.sr_ratios[k] > 1:
+                attn += ["attn.sr.weight", "attn.sr.bias", "attn.norm.weight", "attn.norm.bias"]
+        p = f"blocks.{k}.{j}."
+        return [p + n for n in ["norm1.weight", "norm1.bias"] + attn + ["norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias",
+                                                                       "mlp.fc2.weight", "mlp.fc2.bias"]]
+
+    def peg_keys(self, k: int) -> List[str]:
+        return [f"pos_block.{k}.proj.0.weight", f"pos_block.{k}.proj.0.bias"]
+
+    def native_block_keys(self, k: int, j: int) -> List[str]:
+        """The block's keys in the order `i2v_twins_create` takes them: as timm's, but `attn.sr` and `attn.norm` in front of
+        `attn.proj`, where the forward runs them."""
+        keys = self.block_keys(k, j)
+        sub = [key for key in keys if ".attn.sr." in key or ".attn.norm." in key]
+        rest = [key for key in keys if key not in sub]
+        at = next(i for i, key in enumerate(rest) if key.endswith("attn.proj.weight"))
+        return rest[:at] + sub + rest[at:]
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block, in timm's order: all patch embeddings, all blocks,
+        all position encodings."""
+        out = {}
+        for k in range(4):
+            D, Cin, P = self.dims[k], self.dims[k - 1] if k else self.in_chans, 2 if k else self.patch
+            out.update(zip(self.embed_keys(k), [(D, Cin, P, P), (D,), (D,), (D,)]))
+        for k in range(4):
+            D, M, sr = self.dims[k], self.mlp(k), self.sr_ratios[k]
+            tail = {"norm2.weight": (D,), "norm2.bias": (D,), "mlp.fc1.weight": (M, D), "mlp.fc1.bias": (M,), "mlp.fc2.weight": (D, M),
+                    "mlp.fc2.bias": (D,), "norm1.weight": (D,), "norm1.bias": (D,), "attn.qkv.weight": (3 * D, D), "attn.qkv.bias": (3 * D,),
+                    "attn.q.weight": (D, D), "attn.q.bias": (D,), "attn.kv.weight": (2 * D, D), "attn.kv.bias": (2 * D,),
+                    "attn.proj.weight": (D, D), "attn.proj.bias": (D,), "attn.sr.weight": (D, D, sr, sr), "attn.sr.bias": (D,),
+                    "attn.norm.weight": (D,), "attn.norm.bias": (D,)}
+            for j in range(self.depths[k]):
+                for key in self.block_keys(k, j):
+                    out[key] = tail[key.split(".", 3)[3]]
+        for k in range(4):
+            out.update(zip(self.peg_keys(k), [(self.dims[k], 1, 3, 3), (self.dims[k],)]))
+        return out
+
+    def native_arrays(self, sd, n_stages: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_twins_create` takes for the first `n_stages` stages, from a timm-layout state dict, as float32 host tensors.
+        Repacked to the gathers' column orders: `patch_embeds.0.proj` flattened as it stands (column (c patch + dy) patch + dx); the later
+        embeddings (D, C, 2, 2) -> (D, 4 C) with column (dy + 2 dx) C + c, the 2 x 2 merge gather's order; `attn.sr` (D, D, s, s) ->
+        (D, s s D) with column (dy s + dx) D + c, the block gather's order; `pos_block` (D, 1, 3, 3) -> (9, D).  Behind block 0's arrays
+        of each stage come its position encoding's filter and bias."""
+        f32 = lambda k: sd[k].detach().float().cpu().contiguous()      # noqa: E731
+        out = []
+        for k in range(n_stages):
+            w = f32(f"patch_embeds.{k}.proj.weight")
+            out.append(w.reshape(w.shape[0], -1) if k == 0 else w.permute(0, 3, 2, 1).reshape(w.shape[0], -1).contiguous())
+            out += [f32(key) for key in self.embed_keys(k)[1:]]
+            for j in range(self.depths[k]):
+                for key in self.native_block_keys(k, j):
+                    t = f32(key)
+                    out.append(t.permute(0, 2, 3, 1).reshape(t.shape[0], -1).contiguous() if key.endswith("attn.sr.weight") else t)
+                if j == 0:
+                    out += [f32(self.peg_keys(k)[0]).reshape(self.dims[k], 9).t().contiguous(), f32(self.peg_keys(k)[1])]
+        return out
+
+    def config_lists(self):
+        """(dims, heads, MLP widths, depths, sr) as `i2v_twins_config` takes them."""
+        return list(self.dims), list(self.heads), [self.mlp(k) for k in range(4)], list(self.depths), list(self.sr_ratios)
+
+    def macs_per_frame(self) -> int:
+        total = 0
+        for k in range(4):
+            T, Tk, D, M, sr = self.tokens(k), self.keys_per_frame(k), self.dims[k], self.mlp(k), self.sr_ratios[k]
+            total += T * D * (self.dims[k - 1] * 4 if k else self.in_chans * self.patch ** 2) + 9 * T * D
+            for j in range(self.depths[k]):
+                if self.is_lsa(k, j):
+                    total += T * D * 4 * D + 2 * T * self.window ** 2 * D
+                else:
+                    total += T * D * 2 * D + Tk * D * 2 * D + 2 * T * Tk * D + (Tk * sr * sr * D * D if sr > 1 else 0)
+                total += 2 * T * D * M
+        return total
+
+    def workspace_bytes(self, hook_stages: Sequence[int], frames: int, composed: Optional[bool] = None) -> int:
+        """Device bytes `i2v_twins_create` plans for these hooked stages and `frames` frames (the formula of csrc/i2v_twins.cpp).
+        `composed`: the plan of the shared-launch route of the GSA core (`I2V_TWINS_ATTN=0`; None reads the environment as the planner
+        does), which keeps per GSA block the probabilities -- queries x keys rounded up to 4, per head and frame -- and one such array
+        of scratch.  Otherwise: the
+        weights of the stages run, with one tap-reversed copy of each position-encoding filter; per stage the embedding before its
+        LayerNorm with two statistics per token, and its output stream; per block its input, the mid stream, the fc1 pre-activation and
+        four statistics per token, and qkv (LSA) or q, kv and -- where sr > 1 -- the sub-sampled plane before its LayerNorm with two
+        statistics per key (GSA); the shared scratch -- the patch rows, four streams of the largest stage, one MLP-wide, the attention
+        gradient (three streams with windows, one without), four key-side planes -- and the zero table the window launch takes; one
+        gradient view per hook."""
+        import os
+        if composed is None:
+            composed = os.environ.get("I2V_TWINS_ATTN") == "0"
+        F, ns = frames, max(hook_stages) + 1
+        KP = self.in_chans * self.patch ** 2
+        weights = acts = m_ftd = m_ftm = m_kv = m_p = 0
+        for k in range(ns):
+            D, M, sr, T, Tk = self.dims[k], self.mlp(k), self.sr_ratios[k], self.tokens(k), self.keys_per_frame(k)
+            weights += D * (4 * self.dims[k - 1] if k else KP) + 3 * D + 2 * 9 * D + D
+            acts += F * T * (D + 2) + F * T * D
+            for j in range(self.depths[k]):
+                weights += 2 * D + D * D + D + 2 * D + 2 * M * D + M + D
+                if self.is_lsa(k, j):
+                    weights += 3 * D * D + 3 * D
+                    acts += 3 * F * T * D
+                else:
+                    weights += 3 * D * D + 3 * D + (sr * sr * D * D + 3 * D if sr > 1 else 0)
+                    acts += F * T * D + 2 * F * Tk * D + (F * Tk * (D + 2) if sr > 1 else 0)
+                    if composed:
+                        probs = F * T * self.heads[k] * ((Tk + 3) // 4 * 4)
+                        acts, m_p = acts + probs, max(m_p, probs)
+                acts += F * T * (2 * D + M + 4)
+            m_ftd, m_ftm, m_kv = max(m_ftd, F * T * D), max(m_ftm, F * T * M), max(m_kv, 2 * F * Tk * D)
+        ni = (2 * self.window - 1) ** 2 * max(self.heads[:ns]) if self.window else 0
+        acts += F * self.tokens(0) * KP + (7 if self.window else 5) * m_ftd + m_ftm + 2 * m_kv + ni + m_p
+        acts += sum(F * self.hook_dim(s) for s in hook_stages)
+        return 4 * (weights + acts)
+
+
+def is_twins_name(model_name: str) -> bool:
+    """A name of timm's Twins vocabulary (`twins.py`), served (`TWINS_MODELS`) or not: `graphs.build` routes these to `twins_named`,
+    which refuses the ones that are not offered with a message that lists the served names."""
+    return model_name.startswith("twins_")
+
+
+def twins_named(model_name: str, in_hw=(224, 224)) -> TwinsSpec:
+    """Any row of `TWINS_MODELS`, at 224 x 224 only; names outside the table are refused with the reason."""
+    served = "; served: " + ", ".join(TWINS_MODELS)
+    if model_name not in TWINS_MODELS:
+        raise ValueError(f"Twins surrogate {model_name!r}: not a model of this table" + served)
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}): its sub-sampling and "
+                         "window-7 stages need the 56 / 28 / 14 / 7 grids" + served)
+    dims, heads, ratios, depths, window = TWINS_MODELS[model_name]
+    return TwinsSpec(model_name, 224, dims, heads, ratios, depths, window)
+
+
+def twins_tiny_twin(model_name: str = "twins_pcpvt_small", in_hw=(64, 64)) -> TwinsSpec:
+    """The same topology at test size, four stages of two blocks each, so that both block kinds, the position encoding and every sr in
+    (8, 4, 2, 1) are real and depths 1..4 hook different stages.  Not rows of `TWINS_MODELS`.
+      PCPVT names, square frames of a multiple of 32 pixels: "twins_pcpvt_test" -- at 64 x 64 grids 16 / 8 / 4 / 2, 4 keys; widths 16,
+        32, 40, 64 under 1, 2, 5, 8 heads (head widths 16, 16, 8, 8), MLP ratios 4, 4, 2, 2
+      PCPVT names at 96 x 96: "twins_pcpvt_test_96" -- grids 24 / 12 / 6 / 3 (an odd last plane), 9 keys (odd, no multiple of 4), 576 /
+        144 / 36 / 9 queries; widths 24, 48, 60, 96 under 2, 4, 5, 8 heads of width 12, MLP ratio 2
+      SVT names, square frames of a multiple of 128 pixels: "twins_svt_test" -- window 4 and head width 16, Swin's other served window
+        shape; at 128 x 128 grids 32 / 16 / 8 / 4, 16 keys; widths 16, 32, 64, 128 under 1, 2, 4, 8 heads, MLP ratio 2
+      SVT names at 224 x 224 (the size the attack classes probe a builder with): "twins_svt_test_224" -- window 7 and head width 32 on
+        the 56 / 28 / 14 / 7 grids, widths 32, 64, 128, 256, MLP ratio 2"""
+    side = int(in_hw[0])
+    if in_hw[0] != in_hw[1]:
+        raise ValueError(f"the test-size Twins take square frames (got {tuple(in_hw)})")
+    if "svt" in model_name:
+        if side == 224:
+            return TwinsSpec("twins_svt_test_224", 224, (32, 64, 128, 256), (1, 2, 4, 8), (2, 2, 2, 2), (2, 2, 2, 2), 7)
+        if side % 128:
+            raise ValueError(f"the test-size Twins-SVT takes square frames of a multiple of 128 pixels, or 224 x 224 (got {tuple(in_hw)})")
+        return TwinsSpec("twins_svt_test", side, (16, 32, 64, 128), (1, 2, 4, 8), (2, 2, 2, 2), (2, 2, 2, 2), 4)
+    if side == 96:
+        return TwinsSpec("twins_pcpvt_test_96", 96, (24, 48, 60, 96), (2, 4, 5, 8), (2, 2, 2, 2), (2, 2, 2, 2), 0)
+    if side % 32:
+        raise ValueError(f"the test-size Twins-PCPVT takes square frames of a multiple of 32 pixels (got {tuple(in_hw)})")
+    return TwinsSpec("twins_pcpvt_test", side, (16, 32, 40, 64), (1, 2, 5, 8), (4, 4, 2, 2), (2, 2, 2, 2), 0)
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -2196,6 +2465,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return convit_named(model_name, in_hw)
     if is_xcit_name(model_name):        # extension: timm's XCiT family (cross-covariance attention, a convolutional stem, LPI)
         return xcit_named(model_name, in_hw)
+    if is_twins_name(model_name):       # extension: timm's Twins family (sub-sampled global attention, window attention, PEG)
+        return twins_named(model_name, in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -2245,4 +2516,6 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return convit_tiny_twin(in_hw)
     if model_name in XCIT_MODELS:
         return xcit_tiny_twin(in_hw)
+    if model_name in TWINS_MODELS:
+        return twins_tiny_twin(model_name, in_hw)
     return build(model_name, in_hw)

@@ -287,6 +287,32 @@ _XCIT_PROTOS = {
 XCIT_EXPORTS = tuple(_XCIT_PROTOS)
 
 
+class TwinsConfig(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("img", "in_chans", "patch", "stages", "window")]
+                + [(n, C.c_int32 * 4) for n in ("dims", "heads", "mlp", "depths", "sr")] + [("ln_eps", C.c_float), ("pe_eps", C.c_float)])
+
+
+# The Twins surrogates (`include/i2v_twins.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it: the
+# planner runs there on scalar restatements, and so do the kernel entries on their own -- sub-sampled attention forward and backward,
+# the block gather / scatter pair, and window attention at shift 0 without a table (which the host simulation has in no other form).
+_TWINS_PROTOS = {
+    "i2v_twins_create": ([_I, C.POINTER(TwinsConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    "i2v_twins_destroy": ([_P], _I),
+    "i2v_twins_workspace_bytes": ([_P], _L),
+    "i2v_twins_forward": ([_P, _P, _I, _P], _I),
+    "i2v_twins_backward": ([_P, _P, _I, _P], _I),
+    "i2v_twins_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+    "i2v_twins_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    "i2v_twins_attention_f32": ([_P, _P, _I, _I, _I, _I, _I, _F, _P, _P], _I),
+    "i2v_twins_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P], _I),
+    "i2v_twins_block_gather_f32": ([_P, _P, _I, _I, _I, _I, _I, _P], _I),
+    "i2v_twins_block_scatter_f32": ([_P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
+    "i2v_twins_window_attention_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    "i2v_twins_window_attention_bwd_f32": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+}
+TWINS_EXPORTS = tuple(_TWINS_PROTOS)
+
+
 class XfGemmDesc(C.Structure):
     _fields_ = ([("A", _P)] + [(n, _L) for n in ("a_bo", "a_bi", "a_sm", "a_sk")] + [("B", _P)] + [(n, _L) for n in ("b_bo", "b_bi", "b_sk", "b_sn")]
                 + [("C", _P)] + [(n, _L) for n in ("c_bo", "c_bi", "c_sm")] + [(n, _P) for n in ("bias", "R", "C2", "H")]
@@ -337,6 +363,7 @@ def load():
         bind(lib, _CAIT_PROTOS)
         bind(lib, _CONVIT_PROTOS)
         bind(lib, _XCIT_PROTOS)
+        bind(lib, _TWINS_PROTOS)
         bind(lib, _XF_PROTOS)
         _lib = lib
     return _lib

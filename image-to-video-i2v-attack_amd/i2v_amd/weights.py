@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, VitSpec, XcitSpec
+from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -213,6 +213,34 @@ def _xcit_synthetic(spec: XcitSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _twins_synthetic(spec: TwinsSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained Twins, drawn per key as `_xcit_synthetic` draws: Linears and the patch and sub-sampling
+    convolutions ~ fan_in^-0.5 N(0, 1) (`attn.proj` and `mlp.fc2` at half that), the blocks' LayerNorm gains 1 + 0.1 N(0, 1), biases
+    0.02 N(0, 1).  What is new shows: `attn.norm` and the patch embeddings' norms have gains uniform on (0.5, 1.5) and shifts 0.1
+    N(0, 1), so that a sub-sampled plane that skipped its LayerNorm is seen; `attn.sr.bias` is 0.1 N(0, 1); the position encoding's
+    depthwise filter is N(0, 1) / 3 with a bias of 0.1 N(0, 1), so that its term is of the size of the stream it is added to."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.endswith("attn.norm.weight") or (k.startswith("patch_embeds") and k.endswith("norm.weight")):
+            sd[k] = 0.5 + torch.rand(*shp, generator=g)
+        elif k.endswith("attn.norm.bias") or (k.startswith("patch_embeds") and k.endswith("norm.bias")) or k.endswith("attn.sr.bias") \
+                or (k.startswith("pos_block") and k.endswith("bias")):
+            sd[k] = 0.1 * torch.randn(*shp, generator=g)
+        elif k.startswith("pos_block"):
+            sd[k] = torch.randn(*shp, generator=g) / 3.0
+        elif k.endswith(("norm1.weight", "norm2.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if k.endswith(("fc2.weight", "attn.proj.weight")) else 1.0) * fan_in ** -0.5)
+    return sd
+
+
 #: timm renamed XCiT's `pos_embeder` to `pos_embed` after 0.5.0: the later spelling of the same two arrays is accepted
 XCIT_KEY_ALIASES = {"pos_embed.token_projection.weight": "pos_embeder.token_projection.weight",
                     "pos_embed.token_projection.bias": "pos_embeder.token_projection.bias"}
@@ -258,6 +286,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _convit_synthetic(graph, seed)
     if isinstance(graph, XcitSpec):
         return _xcit_synthetic(graph, seed)
+    if isinstance(graph, TwinsSpec):
+        return _twins_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":
