@@ -129,6 +129,8 @@ class _ImageGuided(Attack):
                 nets.append(self.engine.build_xcit_net(g, sd, hooks, frames))
             elif isinstance(g, _graphs.TwinsSpec):      # Twins on the transformer stack: stages, hooked as Swin's
                 nets.append(self.engine.build_twins_net(g, sd, hooks, frames))
+            elif isinstance(g, _graphs.BeitSpec):       # BEiT on the transformer stack: biased global attention, hooked as ViT's
+                nets.append(self.engine.build_beit_net(g, sd, hooks, frames))
             else:
                 nets.append(self.engine.build_net(g, sd, hooks, frames))
         self._nets, self._net_key, self._max_frames = nets, key, frames

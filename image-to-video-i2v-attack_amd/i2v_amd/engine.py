@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
+from .graphs import BeitSpec, CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -315,6 +315,38 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_twins_window_attention_bwd_f32(_ptr(qkv, self), _ptr(dout, self), n, grid, grid, window, heads, dh,
                                                                            _ptr(zeros, self), _ptr(dqkv, self), self.stream()))
         return dqkv
+
+    def build_beit_net(self, spec: BeitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "BeitNet":
+        """A BEiT surrogate (`include/i2v_beit.h`): weights packed and uploaded and the arena planned for up to `max_frames` frames."""
+        return self._build(BeitNet, spec, state_dict, list(hook_blocks), max_frames)
+
+    def beit_attention(self, qkv: torch.Tensor, bias, heads: int, scale: float = None) -> torch.Tensor:
+        """Biased global attention on its own (`i2v_beit_attention_f32`): qkv (frames, T, 3 heads dh), bias (heads, T, T) or None ->
+        out (frames, T, heads dh); `scale` defaults to dh^-0.5."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        assert 3 * heads * dh == C3 and (bias is None or tuple(bias.shape) == (heads, T, T))
+        out = torch.empty(n, T, heads * dh, dtype=torch.float32, device=qkv.device)
+        _lib.check(self.capi, self.capi.i2v_beit_attention_f32(_ptr(qkv, self), None if bias is None else _ptr(bias, self), n, T, heads, dh,
+                                                               dh ** -0.5 if scale is None else scale, _ptr(out, self), self.stream()))
+        return out
+
+    def beit_attention_bwd(self, qkv: torch.Tensor, bias, dout: torch.Tensor, heads: int, scale: float = None) -> torch.Tensor:
+        """The input gradient of that launch (`i2v_beit_attention_bwd_f32`) from dout = d(out): dqkv as qkv."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        dqkv = torch.empty_like(qkv)
+        _lib.check(self.capi, self.capi.i2v_beit_attention_bwd_f32(_ptr(qkv, self), None if bias is None else _ptr(bias, self), _ptr(dout, self),
+                                                                   n, T, heads, dh, dh ** -0.5 if scale is None else scale, _ptr(dqkv, self),
+                                                                   self.stream()))
+        return dqkv
+
+    def beit_bias_add(self, S: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+        """The bias-add launch of the shared-launch route on its own (`i2v_beit_bias_add_f32`): S (frames, heads, T, ld) += bias
+        (heads, T, ld), in place."""
+        assert tuple(S.shape[1:]) == tuple(bias.shape)
+        _lib.check(self.capi, self.capi.i2v_beit_bias_add_f32(_ptr(S, self), _ptr(bias, self), S.shape[0], bias.numel(), self.stream()))
+        return S
 
     # ---- measurement ----
     KINDS = ("conv_igemm_fwd", "conv_igemm_imggrad", "pool_fwd", "pool_bwd", "addmask", "conv_igemm_dgrad")
@@ -1051,3 +1083,25 @@ class TwinsNet(TokenNet):
     def hook_shape(self, i):
         st = self.hook_tensors[i]
         return (self.graph.tokens(st), self.graph.width(st), 1)
+
+
+class BeitNet(TokenNet):
+    """A BEiT surrogate: a hook is the residual stream after one block, all tokens with the class token, (tokens * dim) floats per
+    frame."""
+    _api = "beit"
+
+    def _create(self, spec: BeitSpec, sd, hook_blocks, max_frames):
+        eng, capi = self.eng, self.eng.capi
+        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
+        # native order (include/i2v_beit.h): the embedding, the class token, then 13 arrays per block with the qkv bias built, LayerScale
+        # folded and the position bias dense; kept alive until the upload
+        w = spec.native_arrays(sd, nb)
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
+        cfg = _lib.BeitConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.ln_eps)
+        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
+        h = C.c_void_p()
+        _lib.check(capi, capi.i2v_beit_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames, C.byref(h)))
+        return h
+
+    def hook_shape(self, i):
+        return (self.graph.tokens, self.graph.dim, 1)

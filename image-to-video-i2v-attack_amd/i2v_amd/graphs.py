@@ -2421,6 +2421,205 @@ def twins_tiny_twin(model_name: str = "twins_pcpvt_small", in_hw=(64, 64)) -> Tw
 
 
 # ---------------------------------------------------------------------------
+# the BEiT surrogates: a ViT-shaped stack without a position embedding, whose every block adds a learned relative position bias to its
+# attention scores and scales its two branches by LayerScale vectors, planned on the transformer stack (include/i2v_beit.h)
+# ---------------------------------------------------------------------------
+#: timm 0.5.0's `Beit` models at 224 x 224 (head width 64): name -> (patch, dim, heads, mlp, blocks)
+BEIT_MODELS: Dict[str, Tuple[int, int, int, int, int]] = {
+    "beit_base_patch16_224": (16, 768, 12, 3072, 12),
+    "beit_large_patch16_224": (16, 1024, 16, 4096, 24),
+}
+
+
+@dataclass
+class BeitSpec:
+    """timm 0.5.0 `Beit` up to its last block: `patch_embed.proj`, a patch x patch convolution at stride patch
+    with bias; one `cls_token` prepended; NO `pos_embed` and no shared `rel_pos_bias`; then `blocks` pre-norm blocks (LayerNorm eps
+    `ln_eps`, exact GELU)  x += gamma_1 * proj(attn(norm1 x));  x += gamma_2 * fc2(gelu(fc1(norm2 x))).
+    attn: qkv = F.linear(x, qkv.weight, cat(q_bias, 0, v_bias)); q * dh ** -0.5; the scores get
+    `relative_position_bias_table[relative_position_index]`, permuted to (heads, T, T), added; softmax over the keys; the product with
+    v; proj.  The table has (2 g - 1)^2 + 3 rows for a grid of g a side.
+    `hooks`: depth d (1..4) -> zero-based block d * blocks / 4 - 1 (ViT's rule: 2, 5, 8, 11 of 12 blocks; 5, 11, 17, 23 of 24), whose
+    OUTPUT (the residual stream after it, all tokens, the class token included) is the hooked feature: tokens * dim floats per frame.
+    `norm` / `fc_norm` and `head` lie behind every hook."""
+    arch: str
+    img: int
+    patch: int = 16
+    in_chans: int = 3
+    dim: int = 768
+    heads: int = 12
+    mlp: int = 3072
+    blocks: int = 12
+    ln_eps: float = 1e-6
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        dh = self.dim // self.heads
+        if self.img % self.patch or self.tokens > 208:
+            raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame under patch {self.patch} must be whole patches and at most "
+                             "208 tokens with the class token")
+        if self.dim % self.heads or dh % 4 or dh > 64:
+            raise ValueError(f"{self.arch}: width {self.dim} under {self.heads} heads: the head width must be a multiple of 4 up to 64")
+        if self.blocks % 4:
+            raise ValueError(f"{self.arch}: {self.blocks} blocks: the hooks sit at every quarter of the stack")
+        if not self.hooks:
+            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def grid(self) -> int:
+        return self.img // self.patch
+
+    @property
+    def tokens(self) -> int:
+        return 1 + self.grid ** 2
+
+    @property
+    def table_rows(self) -> int:
+        return (2 * self.grid - 1) ** 2 + 3
+
+    @property
+    def hook_dim(self) -> int:
+        """Floats per frame of a hooked feature."""
+        return self.tokens * self.dim
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def block_keys(self, i: int) -> List[str]:
+        """The block's PARAMETERS in timm's state-dict order (the buffer `attn.relative_position_index` sits behind the table there:
+        `index_key`)."""
+        p = f"blocks.{i}."
+        return [p + k for k in ("gamma_1", "gamma_2", "norm1.weight", "norm1.bias", "attn.q_bias", "attn.v_bias",
+                                "attn.relative_position_bias_table", "attn.qkv.weight", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
+                                "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
+
+    def index_key(self, i: int) -> str:
+        return f"blocks.{i}.attn.relative_position_index"
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block, in timm's order.  The int64 buffers
+        `attn.relative_position_index` (tokens, tokens) are not parameters: they are computed (`relative_position_index`), never loaded."""
+        D, M = self.dim, self.mlp
+        out = {"cls_token": (1, 1, D), "patch_embed.proj.weight": (D, self.in_chans, self.patch, self.patch), "patch_embed.proj.bias": (D,)}
+        shapes = [(D,), (D,), (D,), (D,), (D,), (D,), (self.table_rows, self.heads), (3 * D, D), (D, D), (D,), (D,), (D,), (M, D), (M,),
+                  (D, M), (D,)]
+        for i in range(self.blocks):
+            out.update(zip(self.block_keys(i), shapes))
+        return out
+
+    def relative_position_index(self) -> "torch.Tensor":
+        """The (tokens, tokens) int64 index into a block's bias table, as `beit.py` defines it, from coordinate differences: the pair of
+        patches (yi, xi), (yj, xj) -> (yi - yj + g - 1) (2 g - 1) + (xi - xj + g - 1); the class token's row -> n - 3, its column ->
+        n - 2, its own element -> n - 1, for a table of n rows."""
+        import torch
+        g, n = self.grid, self.table_rows
+        y = torch.arange(g).repeat_interleave(g)
+        x = torch.arange(g).repeat(g)
+        idx = torch.empty(self.tokens, self.tokens, dtype=torch.int64)
+        idx[1:, 1:] = (y[:, None] - y[None, :] + g - 1) * (2 * g - 1) + (x[:, None] - x[None, :] + g - 1)
+        idx[0, :] = n - 3
+        idx[:, 0] = n - 2
+        idx[0, 0] = n - 1
+        return idx
+
+    def native_arrays(self, sd, n_blocks: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_beit_create` takes for the first `n_blocks` blocks, from a timm-layout state dict, as float32 host tensors:
+        the patch weight flattened as it stands, its bias, `cls_token` as (dim); per block 13 arrays -- the qkv bias built as
+        [q_bias | 0 | v_bias], the table expanded through the index to a dense (heads, T, T) array, `gamma_1` folded into `attn.proj`
+        and `gamma_2` into `mlp.fc2` (weight rows and bias; products in float64, rounded once)."""
+        import torch
+        f32 = lambda k: sd[k].detach().float().cpu().contiguous()      # noqa: E731
+        f64 = lambda k: sd[k].detach().double().cpu()                  # noqa: E731
+        T, idx = self.tokens, self.relative_position_index().reshape(-1)
+        out = [f32("patch_embed.proj.weight").reshape(self.dim, -1), f32("patch_embed.proj.bias"), f32("cls_token").reshape(self.dim)]
+        for i in range(n_blocks):
+            p = f"blocks.{i}."
+            g1, g2 = f64(p + "gamma_1"), f64(p + "gamma_2")
+            dense = f32(p + "attn.relative_position_bias_table")[idx].reshape(T, T, self.heads).permute(2, 0, 1).contiguous()
+            out += [f32(p + "norm1.weight"), f32(p + "norm1.bias"), f32(p + "attn.qkv.weight"),
+                    torch.cat([f32(p + "attn.q_bias"), torch.zeros(self.dim), f32(p + "attn.v_bias")]), dense,
+                    (g1[:, None] * f64(p + "attn.proj.weight")).float().contiguous(), (g1 * f64(p + "attn.proj.bias")).float().contiguous(),
+                    f32(p + "norm2.weight"), f32(p + "norm2.bias"), f32(p + "mlp.fc1.weight"), f32(p + "mlp.fc1.bias"),
+                    (g2[:, None] * f64(p + "mlp.fc2.weight")).float().contiguous(), (g2 * f64(p + "mlp.fc2.bias")).float().contiguous()]
+        return out
+
+    def macs_per_frame(self) -> int:
+        T, D, M = self.tokens, self.dim, self.mlp
+        per_block = T * D * (3 * D + D + 2 * M) + 2 * T * T * D
+        return (T - 1) * D * self.in_chans * self.patch ** 2 + self.blocks * per_block
+
+    def workspace_bytes(self, hook_blocks: Sequence[int], frames: int, composed: Optional[bool] = None) -> int:
+        """Device bytes `i2v_beit_create` plans for these hooks and `frames` frames (the formula of csrc/i2v_beit.cpp): the weights of
+        the blocks run, the dense bias of each among them; per block its input, qkv, the mid stream, the fc1 pre-activation and four
+        statistics per token; the shared scratch -- the top stream, two streams, one MLP-wide, the qkv gradient, the patch rows and
+        their embedding, and the table of zeros the assemble launch takes --; one gradient view per hook.  `composed`: the plan of the
+        shared-launch route of the attention core (`I2V_BEIT_ATTN=0`; None reads the environment as the planner does), which keeps per
+        block the probabilities -- tokens x tokens rounded up to 4, per head and frame -- and the bias padded to that row stride, and
+        one array of scratch the size of a block's probabilities."""
+        import os
+        if composed is None:
+            composed = os.environ.get("I2V_BEIT_ATTN") == "0"
+        D, M, T, H, F, nb = self.dim, self.mlp, self.tokens, self.heads, frames, max(hook_blocks) + 1
+        KP, NP, FT, ld = self.in_chans * self.patch ** 2, T - 1, frames * T, (T + 3) // 4 * 4
+        probs, padded = (F * H * T * ld, H * T * ld) if composed else (0, 0)
+        weights = D * KP + 2 * D + nb * (4 * D * D + 2 * D * M + 9 * D + M + H * T * T)
+        per_block = 5 * FT * D + FT * M + 4 * FT + probs + padded
+        shared = 6 * FT * D + FT * M + F * NP * (KP + D) + T * D + probs
+        return 4 * (weights + nb * per_block + shared + len(hook_blocks) * FT * D)
+
+
+def is_beit_name(model_name: str) -> bool:
+    """A name of timm's BEiT vocabulary (`beit.py`), served (`BEIT_MODELS`) or not: `graphs.build` routes these to `beit_named`, which
+    refuses the ones that are not offered with a message that lists the served names."""
+    return model_name.startswith("beit_")
+
+
+def beit_named(model_name: str, in_hw=(224, 224)) -> BeitSpec:
+    """Any row of `BEIT_MODELS`, at 224 x 224 only.  Refused, each with the reason: the 384 x 384 and 512 x 512 checkpoints (other
+    bias-table sizes), the `_in22k` names (ViT's rule for `in21k`), names outside the table, and every other input size."""
+    served = "; served: " + ", ".join(BEIT_MODELS)
+    if model_name not in BEIT_MODELS:
+        if "384" in model_name or "512" in model_name:
+            why = "the 384 x 384 and 512 x 512 checkpoints carry bias tables of other sizes and are not offered (224 x 224 only)"
+        elif "in22k" in model_name:
+            why = "the in22k checkpoints (21841-class heads) are not offered"
+        else:
+            why = "not a model of this table"
+        raise ValueError(f"BEiT surrogate {model_name!r}: {why}" + served)
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}): its relative position "
+                         "bias tables are those of the 14 x 14 grid" + served)
+    patch, dim, heads, mlp, blocks = BEIT_MODELS[model_name]
+    return BeitSpec(model_name, 224, patch, 3, dim, heads, mlp, blocks)
+
+
+def beit_tiny_twin(model_name: str = "beit_base_patch16_224", in_hw=(64, 64)) -> BeitSpec:
+    """The same topology at test size, by frame size (every served name maps to the same twins).  Not rows of `BEIT_MODELS`.
+      64 x 64: "beit_test" -- grid 4, 17 tokens, a table of 52 rows; dim 64 under 2 heads of width 32, MLP 256, 8 blocks, so that depths
+        1..4 hook blocks 1, 3, 5, 7
+      96 x 96: "beit_test_96" -- grid 6, 37 tokens (a multiple of neither 4 nor 16), 124 table rows; dim 48 under 4 heads of width 12 (no
+        multiple of 16), MLP 96, 8 blocks
+      224 x 224 (the size the attack classes probe a builder with): "beit_test_224" -- 197 tokens, dim 64 under 1 head of width 64, MLP
+        128, 4 blocks"""
+    if in_hw[0] != in_hw[1] or int(in_hw[0]) not in (64, 96, 224):
+        raise ValueError(f"the test-size BEiTs take 64 x 64, 96 x 96 or 224 x 224 frames (got {tuple(in_hw)})")
+    side = int(in_hw[0])
+    if side == 64:
+        return BeitSpec("beit_test", 64, 16, 3, 64, 2, 256, 8)
+    if side == 96:
+        return BeitSpec("beit_test_96", 96, 16, 3, 48, 4, 96, 8)
+    return BeitSpec("beit_test_224", 224, 16, 3, 64, 1, 128, 4)
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -2467,6 +2666,8 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return xcit_named(model_name, in_hw)
     if is_twins_name(model_name):       # extension: timm's Twins family (sub-sampled global attention, window attention, PEG)
         return twins_named(model_name, in_hw)
+    if is_beit_name(model_name):        # extension: timm's BEiT family (relative position bias in every block, LayerScale, no pos_embed)
+        return beit_named(model_name, in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -2518,4 +2719,6 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return xcit_tiny_twin(in_hw)
     if model_name in TWINS_MODELS:
         return twins_tiny_twin(model_name, in_hw)
+    if model_name in BEIT_MODELS:
+        return beit_tiny_twin(model_name, in_hw)
     return build(model_name, in_hw)

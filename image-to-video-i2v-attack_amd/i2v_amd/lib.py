@@ -313,6 +313,27 @@ _TWINS_PROTOS = {
 TWINS_EXPORTS = tuple(_TWINS_PROTOS)
 
 
+class BeitConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("img", "patch", "in_chans", "dim", "heads", "mlp", "blocks")] + [("ln_eps", C.c_float)]
+
+
+# The BEiT surrogates (`include/i2v_beit.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it: the
+# planner runs there on scalar restatements, and so do the two attention entries and the bias add on their own.
+_BEIT_PROTOS = {
+    "i2v_beit_create": ([_I, C.POINTER(BeitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    "i2v_beit_destroy": ([_P], _I),
+    "i2v_beit_workspace_bytes": ([_P], _L),
+    "i2v_beit_forward": ([_P, _P, _I, _P], _I),
+    "i2v_beit_backward": ([_P, _P, _I, _P], _I),
+    "i2v_beit_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+    "i2v_beit_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    "i2v_beit_attention_f32": ([_P, _P, _I, _I, _I, _I, _F, _P, _P], _I),
+    "i2v_beit_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P], _I),
+    "i2v_beit_bias_add_f32": ([_P, _P, _I, _L, _P], _I),
+}
+BEIT_EXPORTS = tuple(_BEIT_PROTOS)
+
+
 class XfGemmDesc(C.Structure):
     _fields_ = ([("A", _P)] + [(n, _L) for n in ("a_bo", "a_bi", "a_sm", "a_sk")] + [("B", _P)] + [(n, _L) for n in ("b_bo", "b_bi", "b_sk", "b_sn")]
                 + [("C", _P)] + [(n, _L) for n in ("c_bo", "c_bi", "c_sm")] + [(n, _P) for n in ("bias", "R", "C2", "H")]
@@ -364,6 +385,7 @@ def load():
         bind(lib, _CONVIT_PROTOS)
         bind(lib, _XCIT_PROTOS)
         bind(lib, _TWINS_PROTOS)
+        bind(lib, _BEIT_PROTOS)
         bind(lib, _XF_PROTOS)
         _lib = lib
     return _lib

@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
+from .graphs import BeitSpec, CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -241,6 +241,43 @@ def _twins_synthetic(spec: TwinsSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _beit_synthetic(spec: BeitSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained BEiT, drawn per key as `_twins_synthetic` draws: Linears and the patch convolution ~ fan_in^-0.5
+    N(0, 1) (`attn.proj` and `mlp.fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1), `cls_token` 0.02 N(0, 1).
+    timm's initial values would blind the tests -- a zero bias table makes the bias a no-op, a LayerScale of 0.1 or 1e-5 silences the
+    blocks -- so what is new shows: `relative_position_bias_table` is N(0, 1), `gamma_1` / `gamma_2` are uniform on (0.5, 1.5), and
+    `q_bias` / `v_bias` are 0.1 N(0, 1).  The index buffers are not emitted: they are computed from the geometry."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.endswith(("gamma_1", "gamma_2")):
+            sd[k] = 0.5 + torch.rand(*shp, generator=g)
+        elif k.endswith("relative_position_bias_table"):
+            sd[k] = torch.randn(*shp, generator=g)
+        elif k.endswith(("q_bias", "v_bias")):
+            sd[k] = 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith(("norm1.weight", "norm2.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias") or k == "cls_token":
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if k.endswith(("fc2.weight", "attn.proj.weight")) else 1.0) * fan_in ** -0.5)
+    return sd
+
+
+def check_beit_buffers(spec: BeitSpec, sd, where: str) -> None:
+    """timm's BEiT checkpoints carry the buffer `attn.relative_position_index` per block; it is computed from the geometry here and
+    never loaded, so one that differs describes another model: refused by key name.  An absent one is fine."""
+    idx = spec.relative_position_index()
+    for i in range(spec.blocks):
+        k = spec.index_key(i)
+        if k in sd and not (tuple(sd[k].shape) == tuple(idx.shape) and torch.equal(sd[k].long(), idx)):
+            raise ValueError(f"{where}: buffer {k} differs from the index computed for a {spec.grid} x {spec.grid} grid")
+
+
 #: timm renamed XCiT's `pos_embeder` to `pos_embed` after 0.5.0: the later spelling of the same two arrays is accepted
 XCIT_KEY_ALIASES = {"pos_embed.token_projection.weight": "pos_embeder.token_projection.weight",
                     "pos_embed.token_projection.bias": "pos_embeder.token_projection.bias"}
@@ -288,6 +325,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _xcit_synthetic(graph, seed)
     if isinstance(graph, TwinsSpec):
         return _twins_synthetic(graph, seed)
+    if isinstance(graph, BeitSpec):
+        return _beit_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":
@@ -363,6 +402,8 @@ def load_state_dict(graph: Graph, seed=None, keep_head: bool = False) -> Dict[st
             raise KeyError(f"{path}: missing keys {missing[:4]}...")
         if isinstance(graph, SwinSpec):
             check_swin_buffers(graph, sd, path)
+        if isinstance(graph, BeitSpec):
+            check_beit_buffers(graph, sd, path)
         for k, shp in shapes.items():
             if tuple(sd[k].shape) != tuple(shp):
                 raise ValueError(f"{path}: {k} has shape {tuple(sd[k].shape)}, expected {shp}")
