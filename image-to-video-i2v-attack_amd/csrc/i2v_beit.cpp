@@ -26,83 +26,20 @@
 #include "i2v_beit_host.h"      // (the host simulation's one-file build: the launches as scalar code)
 #endif
 
-namespace {
-
-int beit_probs_ld(int T) { return (T + 3) / 4 * 4; }
-
-// C[f, h] (M, N) = alpha A[f, h] (M, K) B[f, h] (K, N) over batch = frames x heads (outer = frame, inner = head)
-int beit_bgemm(const float* A, int64_t a_bo, int64_t a_bi, int64_t a_sm, int64_t a_sk, const float* B, int64_t b_bo, int64_t b_bi, int64_t b_sk,
-               int64_t b_sn, float* C, int64_t c_bo, int64_t c_bi, int64_t c_sm, int M, int N, int K, int frames, int heads, float alpha,
-               hipStream_t s) {
-    VitGemm g{};
-    g.A = A; g.a_bo = a_bo; g.a_bi = a_bi; g.a_sm = a_sm; g.a_sk = a_sk;
-    g.B = B; g.b_bo = b_bo; g.b_bi = b_bi; g.b_sk = b_sk; g.b_sn = b_sn;
-    g.C = C; g.c_bo = c_bo; g.c_bi = c_bi; g.c_sm = c_sm;
-    g.M = M; g.N = N; g.K = K; g.batch = frames * heads; g.nb_in = heads; g.alpha = alpha;
-    g.mode = VIT_EPI_PLAIN;
-    return vit_gemm(g, s);
-}
-
-// The attention core on the shared launches (I2V_BEIT_ATTN=0): out = softmax(scale q k^T + B) v with P (F, heads, T, ld) kept;
-// `biasp`: the bias padded to (heads, T, ld)
-int beit_composed(const float* qkv, const float* biasp, int F, int T, int heads, int dh, float scale, float* P, float* out, hipStream_t s) {
-    const int C = heads * dh, ld = beit_probs_ld(T);
-    const int64_t qs = 3LL * C * T, ps = (int64_t)T * ld;
-    VCHK(beit_bgemm(qkv, qs, dh, 3 * C, 1, qkv + C, qs, dh, 1, 3 * C, P, heads * ps, ps, ld, T, T, dh, F, heads, scale, s));
-    VCHK(beit_bias_add(P, biasp, F, heads * ps, s));
-    VCHK(beit_softmax(P, (int64_t)F * heads * T, T, ld, s));
-    return beit_bgemm(P, heads * ps, ps, ld, 1, qkv + 2 * C, qs, dh, 3 * C, 1, out, (int64_t)T * C, dh, C, T, dh, T, F, heads, 1.f, s);
-}
-
-// ... and its backward: dout -> dqkv, with dS (F, heads, T, ld) as scratch
-int beit_composed_bwd(const float* qkv, const float* P, const float* dout, int F, int T, int heads, int dh, float scale, float* dS, float* dqkv,
-                      hipStream_t s) {
-    const int C = heads * dh, ld = beit_probs_ld(T);
-    const int64_t qs = 3LL * C * T, ps = (int64_t)T * ld, os = (int64_t)T * C;
-    VCHK(beit_bgemm(dout, os, dh, C, 1, qkv + 2 * C, qs, dh, 1, 3 * C, dS, heads * ps, ps, ld, T, T, dh, F, heads, 1.f, s));      // dP = dout v^T
-    VCHK(beit_softmax_bwd(dS, P, (int64_t)F * heads * T, T, ld, scale, s));
-    VCHK(beit_bgemm(dS, heads * ps, ps, ld, 1, qkv + C, qs, dh, 3 * C, 1, dqkv, qs, dh, 3 * C, T, dh, T, F, heads, 1.f, s));      // dq = dS k
-    VCHK(beit_bgemm(dS, heads * ps, ps, 1, ld, qkv, qs, dh, 3 * C, 1, dqkv + C, qs, dh, 3 * C, T, dh, T, F, heads, 1.f, s));      // dk = dS^T q
-    return beit_bgemm(P, heads * ps, ps, 1, ld, dout, os, dh, C, 1, dqkv + 2 * C, qs, dh, 3 * C, T, dh, T, F, heads, 1.f, s);     // dv = P^T dout
-}
-
-// the patch rows' gradient is the token gradient without the class row (a slice from row 1 of each frame, read in place by the GEMM),
-// times W
-int beit_embed_bwd(const float* dtok, int F, int Cin, int gsz, int P, const float* W, int dim, float* patches, float* gimg, int accumulate,
-                   hipStream_t s) {
-    const int np = gsz * gsz, KP = Cin * P * P;
-    VitGemm g{};
-    g.A = dtok + dim; g.a_bo = (int64_t)(np + 1) * dim; g.a_sm = dim; g.a_sk = 1;
-    g.B = W; g.b_sk = KP; g.b_sn = 1;
-    g.C = patches; g.c_bo = (int64_t)np * KP; g.c_sm = KP;
-    g.M = np; g.N = KP; g.K = dim; g.batch = F; g.nb_in = 1; g.alpha = 1.f;
-    VCHK(vit_gemm(g, s));
-    return vit_patchify(nullptr, patches, F, Cin, gsz, gsz, P, gimg, accumulate, s);
-}
-
-}  // namespace
-
-struct i2v_beit : XfNet {
-    i2v_beit_config cfg{};
-    int T = 0, gsz = 0, nb = 0, ld = 0;
-    float scale = 0.f;
+struct i2v_beit : XfStack<i2v_beit_config> {
+    int ld = 0;
     const float *pe_w = nullptr, *pe_b = nullptr, *cls = nullptr, *zpos = nullptr;
-    std::vector<Block> blocks;
     std::vector<const float*> bias, biasp;       // per block: the dense (heads, T, T) bias; padded to (heads, T, ld) on the composed route
-    float* x_top = nullptr;                      // stream after the last block run
     float *patches = nullptr, *emb = nullptr;
     bool composed = false;                       // I2V_BEIT_ATTN=0 at plan time: the core on the shared launches, P saved per block
     float* dS = nullptr;                         // ... and its score-gradient scratch
 
-    float* stream_after(int b) { return b + 1 < nb ? blocks[b + 1].x : x_top; }
-    BlockRun run(int frames, hipStream_t s) const {
-        return {frames, T, cfg.dim, cfg.mlp, (int64_t)max_frames * T, cfg.ln_eps, t1, t2, dqkv, G, s};
-    }
     BeitAttn attn(int b, int frames) const {
         BeitAttn a{};
         a.qkv = blocks[b].qkv; a.bias = bias[b]; a.F = frames; a.T = T; a.H = cfg.heads; a.dh = cfg.dim / cfg.heads; a.scale = scale;
         return a;
     }
+    XfAttn shared(int b, int frames) const { return xf_attn_qkv(blocks[b].qkv, frames, T, cfg.heads, cfg.dim / cfg.heads, scale); }
 };
 
 namespace {
@@ -110,8 +47,7 @@ namespace {
 int beit_plan(i2v_beit* n, const float* const* w, int nw, const int32_t* hooks, int n_hooks) {
     const i2v_beit_config& c = n->cfg;
     Arena& A = n->arena;
-    if (c.img <= 0 || c.patch <= 0 || c.img % c.patch != 0 || c.patch % 4 != 0 || c.in_chans <= 0 || c.dim <= 0 || c.heads <= 0 ||
-        c.dim % c.heads != 0 || c.dim % 4 != 0 || c.mlp <= 0 || c.mlp % 4 != 0 || c.blocks <= 0)
+    if (!vit_shape_ok(c))
         return fail("i2v_beit_create: unsupported configuration (img %d patch %d dim %d heads %d mlp %d blocks %d)", c.img, c.patch, c.dim, c.heads,
                     c.mlp, c.blocks);
     const int dh = c.dim / c.heads;
@@ -125,7 +61,7 @@ int beit_plan(i2v_beit* n, const float* const* w, int nw, const int32_t* hooks, 
     n->nb = A.depth = deepest + 1;
     if (nw != 3 + 13 * n->nb) return fail("i2v_beit_create: %d weight arrays given, %d expected for %d blocks", nw, 3 + 13 * n->nb, n->nb);
     n->T = (int)Tl;
-    n->ld = beit_probs_ld(n->T);
+    n->ld = xf_probs_ld(n->T);
     n->scale = 1.f / sqrtf((float)dh);                    // dh^-0.5 (exactly 0.125 for dh = 64)
     const char* sw = getenv("I2V_BEIT_ATTN");
     n->composed = sw && !strcmp(sw, "0");
@@ -152,9 +88,7 @@ int beit_plan(i2v_beit* n, const float* const* w, int nw, const int32_t* hooks, 
         Block& B = n->blocks[b];
         B.weights(&dev[3 + 13 * b], &dev[8 + 13 * b]);    // (the dense bias sits between the qkv bias and proj)
         n->bias[b] = dev[7 + 13 * b];
-        if (!(B.x = A.alloc(FT * D)) || !(B.qkv = A.alloc(FT * 3 * D)) || !(B.y = A.alloc(FT * D)) || !(B.h = A.alloc(FT * Hm)) ||
-            !(B.stats = A.alloc(4 * FT)))
-            return A.oom("saved activations of a block");
+        VCHK(B.alloc_saves(A, FT, D, Hm, 0));             // (P of the composed route follows its padded bias, below)
         if (n->composed) {
             float* bp = A.alloc(padded);
             if (!(B.P = A.alloc(probs)) || !bp) return A.oom("saved probabilities of a block");
@@ -176,75 +110,62 @@ int beit_plan(i2v_beit* n, const float* const* w, int nw, const int32_t* hooks, 
     return 0;
 }
 
+int beit_forward(i2v_beit* n, const float* x, int frames, hipStream_t s) {
+    const i2v_beit_config& c = n->cfg;
+    VCHK(patch_rows(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, c.dim, n->patches, n->emb, s));
+    VCHK(vit_assemble(n->emb, n->cls, 1, n->zpos, n->blocks[0].x, frames, n->T, c.dim, s));
+    return n->forward_blocks(frames, s, [&](int b, float* o) {
+        if (n->composed)      // P = softmax(scale q k^T + B): the bias add between the score product and the softmax
+            return xf_attention(n->shared(b, frames), n->blocks[b].P, o, s, [&] {
+                return beit_bias_add(n->blocks[b].P, n->biasp[b], frames, (int64_t)c.heads * n->T * n->ld, s);
+            });
+        BeitAttn a = n->attn(b, frames);
+        a.out = o;
+        return beit_attention(a, s);
+    });
+}
+
+int beit_backward(i2v_beit* n, float* gx, int accumulate, hipStream_t s) {
+    const i2v_beit_config& c = n->cfg;
+    const int frames = n->frames;
+    VCHK(n->backward_blocks(frames, s, [&](int b, const float* dout) {
+        if (n->composed)
+            return xf_attention_bwd(n->shared(b, frames), n->blocks[b].P, dout, n->dS, n->dqkv, n->dqkv + c.dim, n->dqkv + 2 * c.dim, s);
+        BeitAttn a = n->attn(b, frames);
+        a.dout = dout; a.dqkv = n->dqkv;
+        return beit_attention_bwd(a, s);
+    }));
+    return patch_rows_bwd_prefix(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, c.dim, 1, n->patches, gx, accumulate, s);
+}
+
 }  // namespace
 
 extern "C" int i2v_beit_create(int device, const i2v_beit_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_blocks,
                                int n_hooks, int max_frames, i2v_beit_handle* out) {
-    if (!cfg || !weights || !hook_blocks || !out) return fail("i2v_beit_create: null argument");
-    return create_net("i2v_beit_create", "block", device, max_frames, out, [&](i2v_beit* n) {
+    return xf_create("i2v_beit_create", "block", device, cfg, weights, hook_blocks, max_frames, out, [&](i2v_beit* n) {
         n->cfg = *cfg;
         return beit_plan(n, weights, n_weights, hook_blocks, n_hooks);
     });
 }
 
-extern "C" int i2v_beit_destroy(i2v_beit_handle net) {
-    delete net;
-    return 0;
-}
+extern "C" int i2v_beit_destroy(i2v_beit_handle net) { return xf_destroy(net); }
 
-extern "C" int64_t i2v_beit_workspace_bytes(i2v_beit_handle net) { return net ? net->arena.bytes : -1; }
+extern "C" int64_t i2v_beit_workspace_bytes(i2v_beit_handle net) { return xf_workspace_bytes(net); }
 
 extern "C" int i2v_beit_forward(i2v_beit_handle n, const float* x, int frames, void* stream) {
-    if (!n || !x) return fail("i2v_beit_forward: null argument");
-    if (frames <= 0 || frames > n->max_frames) return fail("i2v_beit_forward: %d frames, the net is planned for 1..%d", frames, n->max_frames);
-    hipStream_t s = (hipStream_t)stream;
-    const i2v_beit_config& c = n->cfg;
-    const int heads = c.heads, dh = c.dim / heads, np = n->gsz * n->gsz;
-    const BlockRun r = n->run(frames, s);
-    n->frames = frames;
-    VCHK(vit_patchify(x, n->patches, frames, c.in_chans, n->gsz, n->gsz, c.patch, nullptr, 0, s));
-    VCHK(linear(n->patches, frames * np, c.in_chans * c.patch * c.patch, n->pe_w, n->pe_b, c.dim, nullptr, n->emb, nullptr, s));
-    VCHK(beit_assemble(n->emb, n->cls, n->zpos, n->blocks[0].x, frames, n->T, c.dim, s));
-    for (int b = 0; b < n->nb; ++b)
-        VCHK(block_forward(n->blocks[b], r, n->stream_after(b), [&](const Block& B, float* o) {
-            if (n->composed) return beit_composed(B.qkv, n->biasp[b], frames, n->T, heads, dh, n->scale, B.P, o, s);
-            BeitAttn a = n->attn(b, frames);
-            a.out = o;
-            return beit_attention(a, s);
-        }));
-    return 0;
+    return xf_forward("i2v_beit_forward", n, x, frames, stream, beit_forward);
 }
 
 extern "C" int i2v_beit_backward(i2v_beit_handle n, float* gx, int accumulate, void* stream) {
-    if (!n || !gx) return fail("i2v_beit_backward: null argument");
-    if (n->frames <= 0) return fail("i2v_beit_backward: no forward pass to differentiate");
-    hipStream_t s = (hipStream_t)stream;
-    const i2v_beit_config& c = n->cfg;
-    const int frames = n->frames, heads = c.heads, dh = c.dim / heads;
-    const BlockRun r = n->run(frames, s);
-    for (int b = n->nb - 1; b >= 0; --b) {
-        // gradient of the stream after block b: the top hook's view for the deepest block, the running gradient G below it (where
-        // the LN1 backward of block b + 1 has already added the hook at that stream)
-        const float* gin = b == n->nb - 1 ? n->hooks.grad_at(b) : n->G;
-        VCHK(block_backward(n->blocks[b], r, gin, b > 0 ? n->hooks.grad_at(b - 1) : nullptr, [&](const Block& B, const float* dout) {
-            if (n->composed) return beit_composed_bwd(B.qkv, B.P, dout, frames, n->T, heads, dh, n->scale, n->dS, n->dqkv, s);
-            BeitAttn a = n->attn(b, frames);
-            a.dout = dout; a.dqkv = n->dqkv;
-            return beit_attention_bwd(a, s);
-        }));
-    }
-    return beit_embed_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, c.dim, n->patches, gx, accumulate, s);
+    return xf_backward("i2v_beit_backward", n, gx, accumulate, stream, beit_backward);
 }
 
 extern "C" int i2v_beit_hook_info(i2v_beit_handle n, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride, int64_t* D) {
-    if (!n || !n->hooks.has(hook)) return fail("i2v_beit_hook_info: no hook %d", hook);
-    return hook_info(n->stream_after(n->hooks.at[hook]), n->hooks.grad[hook], (int64_t)n->T * n->cfg.dim, act, act_stride, grad, grad_stride, D);
+    return xf_hook_info("i2v_beit_hook_info", n, hook, act, act_stride, grad, grad_stride, D);
 }
 
 extern "C" int i2v_beit_read_hook(i2v_beit_handle n, int hook, int which, float* out, int frames, void* stream) {
-    if (!n || !out || !n->hooks.has(hook)) return fail("i2v_beit_read_hook: no hook %d", hook);
-    return read_hook("i2v_beit_read_hook", which ? n->hooks.grad[hook] : n->stream_after(n->hooks.at[hook]), (int64_t)n->T * n->cfg.dim, out,
-                     frames, n->max_frames, stream);
+    return xf_read_hook("i2v_beit_read_hook", n, hook, which, out, frames, stream);
 }
 
 // ---- the kernel on its own ----

@@ -44,7 +44,7 @@
 
 #include "i2v_be.h"
 #include "i2v_beit_kernels.h"
-#include "i2v_vit_kernels.h"     // vit_launch_check, vit_softmax, vit_assemble
+#include "i2v_vit_kernels.h"     // vit_launch_check
 
 long long g_stat_beit = 0;
 
@@ -437,14 +437,4 @@ int beit_bias_add(float* S, const float* bias, int F, int64_t per_frame, hipStre
     const int64_t n = (int64_t)F * (per_frame / 4);
     hipLaunchKernelGGL(beit_bias_add_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65536)), dim3(256), 0, s, S, bias, n, per_frame / 4);
     return vit_launch_check("beit_bias_add");
-}
-
-int beit_softmax(float* X, int64_t rows, int N, int ld, hipStream_t s) { return vit_softmax(X, rows, N, ld, s); }
-
-int beit_softmax_bwd(float* dX, const float* P, int64_t rows, int N, int ld, float scale, hipStream_t s) {
-    return vit_softmax_bwd(dX, P, rows, N, ld, scale, s);
-}
-
-int beit_assemble(const float* E, const float* cls, const float* zero_pos, float* x, int F, int T, int C, hipStream_t s) {
-    return vit_assemble(E, cls, 1, zero_pos, x, F, T, C, s);
 }

@@ -1,6 +1,5 @@
 // The BEiT launches (i2v_beit_kernels.h) as plain scalar C++ on the backend's memory: what the planner runs where the library has no
-// i2v_beit.hip (no -DI2V_HAVE_BEIT: the host simulation's one-file build, whose backend memory is host memory), and the row softmax pair
-// and the token assembly, which the host simulation has in no other form.  The same definitions and the same refusals as the kernels;
+// i2v_beit.hip (no -DI2V_HAVE_BEIT: the host simulation's one-file build, whose backend memory is host memory).  The same definitions and the same refusals as the kernels;
 // the ORDER of the sums is the simplest one (one fma chain in increasing index, a plain running sum over a row) and is NOT the device's,
 // so these are held to the float64 bound, not to the device's bits.  Only expf is the host's own.
 #pragma once
@@ -95,35 +94,3 @@ inline int beit_bias_add(float* S, const float* bias, int F, int64_t per_frame, 
     return 0;
 }
 
-inline int beit_softmax(float* X, int64_t rows, int N, int ld, hipStream_t) {
-    if (ld % 4 != 0 || ld < N || ((uintptr_t)X & 15)) return beit_host_refuse("beit_softmax", "rows must be 16-byte aligned (ld % 4 == 0, ld >= N)");
-    for (int64_t r = 0; r < rows; ++r) {
-        float* x = X + r * ld;
-        float m = -INFINITY, sum = 0.f;
-        for (int j = 0; j < N; ++j) m = fmaxf(m, x[j]);
-        for (int j = 0; j < N; ++j) { x[j] = expf(x[j] - m); sum = sum + x[j]; }
-        for (int j = 0; j < N; ++j) x[j] = x[j] / sum;
-    }
-    return 0;
-}
-
-inline int beit_softmax_bwd(float* dX, const float* P, int64_t rows, int N, int ld, float scale, hipStream_t) {
-    if (ld % 4 != 0 || ld < N || (((uintptr_t)dX | (uintptr_t)P) & 15))
-        return beit_host_refuse("beit_softmax_bwd", "rows must be 16-byte aligned (ld % 4 == 0, ld >= N)");
-    for (int64_t r = 0; r < rows; ++r) {
-        float* d = dX + r * ld;
-        const float* p = P + r * ld;
-        float sum = 0.f;
-        for (int j = 0; j < N; ++j) sum = sum + d[j] * p[j];
-        for (int j = 0; j < N; ++j) d[j] = scale * (p[j] * (d[j] - sum));
-    }
-    return 0;
-}
-
-inline int beit_assemble(const float* E, const float* cls, const float*, float* x, int F, int T, int C, hipStream_t) {
-    if (!E || !cls || !x || T < 2) return beit_host_refuse("beit_assemble", "null argument, or no patch row behind the class token");
-    for (int64_t f = 0; f < F; ++f)
-        for (int t = 0; t < T; ++t)
-            for (int c = 0; c < C; ++c) x[(f * T + t) * C + c] = t == 0 ? cls[c] : E[(f * (T - 1) + t - 1) * C + c];
-    return 0;
-}

@@ -26,16 +26,9 @@ struct BeitAttn {
 int beit_attention(const BeitAttn& p, hipStream_t s);             // one launch
 int beit_attention_bwd(const BeitAttn& p, hipStream_t s);         // two launches: dq by (frame, head), then dk / dv by (frame, head)
 
-// The launches of the shared-launch route of the planner (I2V_BEIT_ATTN=0) that the shared interface does not carry:
+// The launch of the shared-launch route of the planner (I2V_BEIT_ATTN=0) that the shared interface does not carry:
 //   beit_bias_add   S (F, H, T, ld) += bias (H, T, ld), ld % 4 == 0: every element, the padding columns included
-//   beit_softmax    X (rows, ld) = softmax over the first N of each row, in place;  _bwd: dX = scale P (dX - rowsum(dX P)) in place
-// On the device the softmax pair is vit_softmax / vit_softmax_bwd; the host simulation has no other form of them.
 int beit_bias_add(float* S, const float* bias, int F, int64_t per_frame, hipStream_t s);
-int beit_softmax(float* X, int64_t rows, int N, int ld, hipStream_t s);
-int beit_softmax_bwd(float* dX, const float* P, int64_t rows, int N, int ld, float scale, hipStream_t s);
-// x (F, T, C) = [cls (C); E (F, T - 1, C)].  On the device this is vit_assemble with `zero_pos`, (T, C) zeros, as its position table
-// (that launch requires one); the host form does not read it.
-int beit_assemble(const float* E, const float* cls, const float* zero_pos, float* x, int F, int T, int C, hipStream_t s);
 
 // What both forms of the attention launches refuse, with the text.  Returns the message or null.
 inline const char* beit_attn_refusal(const BeitAttn& p, bool bwd) {

@@ -25,19 +25,11 @@ struct CaitBlock : Block {
 
 }  // namespace
 
-struct i2v_cait : XfNet {
-    i2v_cait_config cfg{};
-    int T = 0, gsz = 0, nb = 0, ld = 0;
-    float scale = 0.f;
+struct i2v_cait : XfStack<i2v_cait_config, CaitBlock> {
+    int ld = 0;
     const float *pe_w = nullptr, *pe_b = nullptr, *pos = nullptr;
-    std::vector<CaitBlock> blocks;
-    float* x_top = nullptr;                      // stream after the last block run
     float *dS = nullptr, *Pm = nullptr, *patches = nullptr;
 
-    float* stream_after(int b) { return b + 1 < nb ? blocks[b + 1].x : x_top; }
-    BlockRun run(int frames, hipStream_t s) const {
-        return {frames, T, cfg.dim, cfg.mlp, (int64_t)max_frames * T, cfg.ln_eps, t1, t2, dqkv, G, s};
-    }
     CaitAttn attn(const CaitBlock& B, int frames) const {
         CaitAttn a{};
         a.qkv = B.qkv; a.F = frames; a.T = T; a.H = cfg.heads; a.dh = cfg.dim / cfg.heads; a.scale = scale;
@@ -51,8 +43,7 @@ namespace {
 int cait_plan(i2v_cait* n, const float* const* w, int nw, const int32_t* hooks, int n_hooks) {
     const i2v_cait_config& c = n->cfg;
     Arena& A = n->arena;
-    if (c.img <= 0 || c.patch <= 0 || c.img % c.patch != 0 || c.patch % 4 != 0 || c.in_chans <= 0 || c.dim <= 0 || c.heads <= 0 ||
-        c.dim % c.heads != 0 || c.dim % 4 != 0 || (c.dim / c.heads) % 4 != 0 || c.mlp <= 0 || c.mlp % 4 != 0 || c.blocks <= 0)
+    if (!vit_shape_ok(c) || (c.dim / c.heads) % 4 != 0)
         return fail("i2v_cait_create: unsupported configuration (img %d patch %d dim %d heads %d mlp %d blocks %d)", c.img, c.patch, c.dim,
                     c.heads, c.mlp, c.blocks);
     n->gsz = c.img / c.patch;
@@ -88,9 +79,7 @@ int cait_plan(i2v_cait* n, const float* const* w, int nw, const int32_t* hooks, 
         const float* const* q = &dev[3 + 16 * b];
         B.weights(q, q + 8);
         B.wl = q[4]; B.bl = q[5]; B.ww = q[6]; B.bw = q[7];
-        if (!(B.x = A.alloc(FT * D)) || !(B.qkv = A.alloc(FT * 3 * D)) || !(B.P = A.alloc(probs)) ||
-            !(B.y = A.alloc(FT * D)) || !(B.h = A.alloc(FT * Hm)) || !(B.stats = A.alloc(4 * FT)))
-            return A.oom("saved activations of a block");
+        VCHK(B.alloc_saves(A, FT, D, Hm, probs));
     }
     if (!(n->x_top = A.alloc(FT * D)) || !(n->t1 = A.alloc(FT * D)) || !(n->t2 = A.alloc(FT * Hm)) || !(n->dS = A.alloc(probs)) ||
         !(n->Pm = A.alloc(probs)) || !(n->dqkv = A.alloc(FT * 3 * D)) || !(n->G = A.alloc(FT * D)) || !(n->patches = A.alloc(FT * KP)))
@@ -99,78 +88,58 @@ int cait_plan(i2v_cait* n, const float* const* w, int nw, const int32_t* hooks, 
     return 0;
 }
 
+int cait_forward(i2v_cait* n, const float* x, int frames, hipStream_t s) {
+    const i2v_cait_config& c = n->cfg;
+    float* x0 = n->blocks[0].x;
+    VCHK(patch_rows(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, c.dim, n->patches, x0, s));
+    VCHK(cait_add_pos(x0, n->pos, frames, n->T, c.dim, s));
+    return n->forward_blocks(frames, s, [&](int b, float* o) {
+        CaitAttn a = n->attn(n->blocks[b], frames);
+        a.out = o;
+        return cait_attention(a, s);
+    });
+}
+
+int cait_backward(i2v_cait* n, float* gx, int accumulate, hipStream_t s) {
+    const i2v_cait_config& c = n->cfg;
+    const int frames = n->frames;
+    VCHK(n->backward_blocks(frames, s, [&](int b, const float* dout) {
+        CaitAttn a = n->attn(n->blocks[b], frames);
+        a.dout = dout; a.dS = n->dS; a.Pm = n->Pm; a.dqkv = n->dqkv;
+        return cait_attention_bwd(a, s);
+    }));
+    // pos_embed is an addend: the patch rows' gradient is the stream's, times the patch weight
+    return patch_rows_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, c.dim, n->patches, gx, accumulate, s);
+}
+
 }  // namespace
 
 extern "C" int i2v_cait_create(int device, const i2v_cait_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_blocks,
                                int n_hooks, int max_frames, i2v_cait_handle* out) {
-    if (!cfg || !weights || !hook_blocks || !out) return fail("i2v_cait_create: null argument");
-    return create_net("i2v_cait_create", "block", device, max_frames, out, [&](i2v_cait* n) {
+    return xf_create("i2v_cait_create", "block", device, cfg, weights, hook_blocks, max_frames, out, [&](i2v_cait* n) {
         n->cfg = *cfg;
         return cait_plan(n, weights, n_weights, hook_blocks, n_hooks);
     });
 }
 
-extern "C" int i2v_cait_destroy(i2v_cait_handle net) {
-    delete net;
-    return 0;
-}
+extern "C" int i2v_cait_destroy(i2v_cait_handle net) { return xf_destroy(net); }
 
-extern "C" int64_t i2v_cait_workspace_bytes(i2v_cait_handle net) { return net ? net->arena.bytes : -1; }
+extern "C" int64_t i2v_cait_workspace_bytes(i2v_cait_handle net) { return xf_workspace_bytes(net); }
 
 extern "C" int i2v_cait_forward(i2v_cait_handle n, const float* x, int frames, void* stream) {
-    if (!n || !x) return fail("i2v_cait_forward: null argument");
-    if (frames <= 0 || frames > n->max_frames) return fail("i2v_cait_forward: %d frames, the net is planned for 1..%d", frames, n->max_frames);
-    hipStream_t s = (hipStream_t)stream;
-    const i2v_cait_config& c = n->cfg;
-    const BlockRun r = n->run(frames, s);
-    n->frames = frames;
-    float* x0 = n->blocks[0].x;
-    VCHK(vit_patchify(x, n->patches, frames, c.in_chans, n->gsz, n->gsz, c.patch, nullptr, 0, s));
-    VCHK(linear(n->patches, frames * n->T, c.in_chans * c.patch * c.patch, n->pe_w, n->pe_b, c.dim, nullptr, x0, nullptr, s));
-    VCHK(cait_add_pos(x0, n->pos, frames, n->T, c.dim, s));
-    for (int b = 0; b < n->nb; ++b) {
-        const CaitBlock& CB = n->blocks[b];
-        VCHK(block_forward(CB, r, n->stream_after(b), [&](const Block&, float* o) {
-            CaitAttn a = n->attn(CB, frames);
-            a.out = o;
-            return cait_attention(a, s);
-        }));
-    }
-    return 0;
+    return xf_forward("i2v_cait_forward", n, x, frames, stream, cait_forward);
 }
 
 extern "C" int i2v_cait_backward(i2v_cait_handle n, float* gx, int accumulate, void* stream) {
-    if (!n || !gx) return fail("i2v_cait_backward: null argument");
-    if (n->frames <= 0) return fail("i2v_cait_backward: no forward pass to differentiate");
-    hipStream_t s = (hipStream_t)stream;
-    const i2v_cait_config& c = n->cfg;
-    const int frames = n->frames;
-    const BlockRun r = n->run(frames, s);
-    for (int b = n->nb - 1; b >= 0; --b) {
-        // gradient of the stream after block b: the top hook's view for the deepest block, the running gradient G below it (where
-        // the LN1 backward of block b + 1 has already added the hook at that stream)
-        const float* gin = b == n->nb - 1 ? n->hooks.grad_at(b) : n->G;
-        const CaitBlock& CB = n->blocks[b];
-        VCHK(block_backward(CB, r, gin, b > 0 ? n->hooks.grad_at(b - 1) : nullptr, [&](const Block&, const float* dout) {
-            CaitAttn a = n->attn(CB, frames);
-            a.dout = dout; a.dS = n->dS; a.Pm = n->Pm; a.dqkv = n->dqkv;
-            return cait_attention_bwd(a, s);
-        }));
-    }
-    // pos_embed is an addend: the patch rows' gradient is the stream's, times the patch weight
-    VCHK(linear_bwd(n->G, frames * n->T, c.dim, n->pe_w, c.in_chans * c.patch * c.patch, nullptr, n->patches, s));
-    return vit_patchify(nullptr, n->patches, frames, c.in_chans, n->gsz, n->gsz, c.patch, gx, accumulate, s);
+    return xf_backward("i2v_cait_backward", n, gx, accumulate, stream, cait_backward);
 }
 
 extern "C" int i2v_cait_hook_info(i2v_cait_handle n, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride, int64_t* D) {
-    if (!n || !n->hooks.has(hook)) return fail("i2v_cait_hook_info: no hook %d", hook);
-    return hook_info(n->stream_after(n->hooks.at[hook]), n->hooks.grad[hook], (int64_t)n->T * n->cfg.dim, act, act_stride, grad, grad_stride, D);
+    return xf_hook_info("i2v_cait_hook_info", n, hook, act, act_stride, grad, grad_stride, D);
 }
 
 extern "C" int i2v_cait_read_hook(i2v_cait_handle n, int hook, int which, float* out, int frames, void* stream) {
-    if (!n || !out || !n->hooks.has(hook)) return fail("i2v_cait_read_hook: no hook %d", hook);
-    return read_hook("i2v_cait_read_hook", which ? n->hooks.grad[hook] : n->stream_after(n->hooks.at[hook]), (int64_t)n->T * n->cfg.dim, out,
-                     frames, n->max_frames, stream);
+    return xf_read_hook("i2v_cait_read_hook", n, hook, which, out, frames, stream);
 }
 
 // ---- the kernel on its own ----

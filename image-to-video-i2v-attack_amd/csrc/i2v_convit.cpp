@@ -44,6 +44,8 @@ struct i2v_convit : XfNet {
     bool joined() const { return nb > nl; }
     int tokens_at(int b) const { return b < nl ? T : T + 1; }
     float* stream_after(int b) { return b + 1 == nl && joined() ? x_join : b + 1 < nb ? blocks[b + 1].x : x_top; }
+    float* hook_stream(int b) { return stream_after(b); }
+    int64_t hook_floats(int b) const { return (int64_t)tokens_at(b) * cfg.dim; }
     BlockRun run(int frames, int tokens, hipStream_t s) const {
         return {frames, tokens, cfg.dim, cfg.mlp, (int64_t)max_frames * tokens, cfg.ln_eps, t1, t2, dqkv, G, s};
     }
@@ -60,9 +62,7 @@ namespace {
 int convit_plan(i2v_convit* n, const float* const* w, int nw, const int32_t* hooks, int n_hooks) {
     const i2v_convit_config& c = n->cfg;
     Arena& A = n->arena;
-    if (c.img <= 0 || c.patch <= 0 || c.img % c.patch != 0 || c.patch % 4 != 0 || c.in_chans <= 0 || c.dim <= 0 || c.heads <= 0 ||
-        c.dim % c.heads != 0 || c.dim % 4 != 0 || (c.dim / c.heads) % 4 != 0 || c.mlp <= 0 || c.mlp % 4 != 0 || c.blocks <= 0 ||
-        c.local_blocks < 1 || c.local_blocks > c.blocks)
+    if (!vit_shape_ok(c) || (c.dim / c.heads) % 4 != 0 || c.local_blocks < 1 || c.local_blocks > c.blocks)
         return fail("i2v_convit_create: unsupported configuration (img %d patch %d dim %d heads %d mlp %d blocks %d local_blocks %d)", c.img,
                     c.patch, c.dim, c.heads, c.mlp, c.blocks, c.local_blocks);
     n->gsz = c.img / c.patch;
@@ -110,10 +110,7 @@ int convit_plan(i2v_convit* n, const float* const* w, int nw, const int32_t* hoo
         if (local) { B.c = q[4]; B.tab = q[5]; }
         q += local ? 14 : 12;
         B.T = n->tokens_at(b);
-        const int64_t FTb = F * B.T;
-        if (!(B.x = A.alloc(FTb * D)) || !(B.qkv = A.alloc(FTb * 3 * D)) || !(B.P = A.alloc(F * H * B.T * convit_probs_ld(B.T))) ||
-            !(B.y = A.alloc(FTb * D)) || !(B.h = A.alloc(FTb * Hm)) || !(B.stats = A.alloc(4 * FTb)))
-            return A.oom("saved activations of a block");
+        VCHK(B.alloc_saves(A, F * B.T, D, Hm, F * H * B.T * convit_probs_ld(B.T)));
     }
     if (!(n->x_top = A.alloc(FTm * D)) || !(n->t1 = A.alloc(FTm * D)) || !(n->t2 = A.alloc(FTm * Hm)) || !(n->dS = A.alloc(probs_m)) ||
         !(n->dqkv = A.alloc(FTm * 3 * D)) || !(n->G = A.alloc(FTm * D)) || !(n->patches = A.alloc(FT * KP)))
@@ -123,33 +120,10 @@ int convit_plan(i2v_convit* n, const float* const* w, int nw, const int32_t* hoo
     return 0;
 }
 
-}  // namespace
-
-extern "C" int i2v_convit_create(int device, const i2v_convit_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_blocks,
-                                 int n_hooks, int max_frames, i2v_convit_handle* out) {
-    if (!cfg || !weights || !hook_blocks || !out) return fail("i2v_convit_create: null argument");
-    return create_net("i2v_convit_create", "block", device, max_frames, out, [&](i2v_convit* n) {
-        n->cfg = *cfg;
-        return convit_plan(n, weights, n_weights, hook_blocks, n_hooks);
-    });
-}
-
-extern "C" int i2v_convit_destroy(i2v_convit_handle net) {
-    delete net;
-    return 0;
-}
-
-extern "C" int64_t i2v_convit_workspace_bytes(i2v_convit_handle net) { return net ? net->arena.bytes : -1; }
-
-extern "C" int i2v_convit_forward(i2v_convit_handle n, const float* x, int frames, void* stream) {
-    if (!n || !x) return fail("i2v_convit_forward: null argument");
-    if (frames <= 0 || frames > n->max_frames) return fail("i2v_convit_forward: %d frames, the net is planned for 1..%d", frames, n->max_frames);
-    hipStream_t s = (hipStream_t)stream;
+int convit_forward(i2v_convit* n, const float* x, int frames, hipStream_t s) {
     const i2v_convit_config& c = n->cfg;
-    n->frames = frames;
     float* x0 = n->blocks[0].x;
-    VCHK(vit_patchify(x, n->patches, frames, c.in_chans, n->gsz, n->gsz, c.patch, nullptr, 0, s));
-    VCHK(linear(n->patches, frames * n->T, c.in_chans * c.patch * c.patch, n->pe_w, n->pe_b, c.dim, nullptr, x0, nullptr, s));
+    VCHK(patch_rows(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, c.dim, n->patches, x0, s));
     VCHK(cait_add_pos(x0, n->pos, frames, n->T, c.dim, s));
     for (int b = 0; b < n->nb; ++b) {
         const ConvitBlock& CB = n->blocks[b];
@@ -163,10 +137,7 @@ extern "C" int i2v_convit_forward(i2v_convit_handle n, const float* x, int frame
     return 0;
 }
 
-extern "C" int i2v_convit_backward(i2v_convit_handle n, float* gx, int accumulate, void* stream) {
-    if (!n || !gx) return fail("i2v_convit_backward: null argument");
-    if (n->frames <= 0) return fail("i2v_convit_backward: no forward pass to differentiate");
-    hipStream_t s = (hipStream_t)stream;
+int convit_backward(i2v_convit* n, float* gx, int accumulate, hipStream_t s) {
     const i2v_convit_config& c = n->cfg;
     const int frames = n->frames;
     for (int b = n->nb - 1; b >= 0; --b) {
@@ -174,9 +145,9 @@ extern "C" int i2v_convit_backward(i2v_convit_handle n, float* gx, int accumulat
         // LN1 backward of block b + 1 has already added the hook at that stream) -- except across the join, where the stream after
         // block nl - 1 has T tokens and the gradient of block nl's input T + 1: rows 1 .. T of G plus that hook go to g_join
         const bool below_join = n->joined() && b == n->nl - 1, at_join = n->joined() && b == n->nl;
-        const float* gin = b == n->nb - 1 ? n->hooks.grad_at(b) : below_join ? n->g_join : n->G;
+        const float* gin = below_join ? n->g_join : n->grad_in(b, n->nb);
         const ConvitBlock& CB = n->blocks[b];
-        VCHK(block_backward(CB, n->run(frames, CB.T, s), gin, b > 0 && !at_join ? n->hooks.grad_at(b - 1) : nullptr,
+        VCHK(block_backward(CB, n->run(frames, CB.T, s), gin, at_join ? nullptr : n->grad_below(b),
                             [&](const Block&, const float* dout) {
                                 ConvitAttn a = n->attn(CB, frames);
                                 a.dout = dout; a.dS = n->dS; a.dqkv = n->dqkv;
@@ -185,22 +156,38 @@ extern "C" int i2v_convit_backward(i2v_convit_handle n, float* gx, int accumulat
         if (at_join) VCHK(convit_join_cls_bwd(n->G, n->hooks.grad_at(b - 1), n->g_join, frames, n->T, c.dim, s));
     }
     // pos_embed is an addend: the patch rows' gradient is the stream's, times the patch weight
-    VCHK(linear_bwd(n->G, frames * n->T, c.dim, n->pe_w, c.in_chans * c.patch * c.patch, nullptr, n->patches, s));
-    return vit_patchify(nullptr, n->patches, frames, c.in_chans, n->gsz, n->gsz, c.patch, gx, accumulate, s);
+    return patch_rows_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, c.dim, n->patches, gx, accumulate, s);
+}
+
+}  // namespace
+
+extern "C" int i2v_convit_create(int device, const i2v_convit_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_blocks,
+                                 int n_hooks, int max_frames, i2v_convit_handle* out) {
+    return xf_create("i2v_convit_create", "block", device, cfg, weights, hook_blocks, max_frames, out, [&](i2v_convit* n) {
+        n->cfg = *cfg;
+        return convit_plan(n, weights, n_weights, hook_blocks, n_hooks);
+    });
+}
+
+extern "C" int i2v_convit_destroy(i2v_convit_handle net) { return xf_destroy(net); }
+
+extern "C" int64_t i2v_convit_workspace_bytes(i2v_convit_handle net) { return xf_workspace_bytes(net); }
+
+extern "C" int i2v_convit_forward(i2v_convit_handle n, const float* x, int frames, void* stream) {
+    return xf_forward("i2v_convit_forward", n, x, frames, stream, convit_forward);
+}
+
+extern "C" int i2v_convit_backward(i2v_convit_handle n, float* gx, int accumulate, void* stream) {
+    return xf_backward("i2v_convit_backward", n, gx, accumulate, stream, convit_backward);
 }
 
 extern "C" int i2v_convit_hook_info(i2v_convit_handle n, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride,
                                     int64_t* D) {
-    if (!n || !n->hooks.has(hook)) return fail("i2v_convit_hook_info: no hook %d", hook);
-    const int b = n->hooks.at[hook];
-    return hook_info(n->stream_after(b), n->hooks.grad[hook], (int64_t)n->tokens_at(b) * n->cfg.dim, act, act_stride, grad, grad_stride, D);
+    return xf_hook_info("i2v_convit_hook_info", n, hook, act, act_stride, grad, grad_stride, D);
 }
 
 extern "C" int i2v_convit_read_hook(i2v_convit_handle n, int hook, int which, float* out, int frames, void* stream) {
-    if (!n || !out || !n->hooks.has(hook)) return fail("i2v_convit_read_hook: no hook %d", hook);
-    const int b = n->hooks.at[hook];
-    return read_hook("i2v_convit_read_hook", which ? n->hooks.grad[hook] : n->stream_after(b), (int64_t)n->tokens_at(b) * n->cfg.dim, out,
-                     frames, n->max_frames, stream);
+    return xf_read_hook("i2v_convit_read_hook", n, hook, which, out, frames, stream);
 }
 
 // ---- the kernel on its own ----

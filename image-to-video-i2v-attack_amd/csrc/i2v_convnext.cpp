@@ -2,7 +2,7 @@
 // the forward as a fixed launch sequence up to the deepest hooked stage, and the input-gradient pass -- no weight gradients.  In
 // token-major layout everything of a block behind its depthwise convolution is the LayerNorm + MLP half of a transformer block, so the
 // arena, the hook list, the two linear launches (with their bias, GELU and residual epilogues) and the LayerNorm pair are the shared ones
-// of i2v_xf.h, the stem is the Swin patch embedding (the same three launches) and the downsample's 2 x 2 gather is the Swin patch-merging permutation; this file
+// of i2v_xf.h, the stem is its LayerNorm stem (the one Swin runs) and the downsample's 2 x 2 gather is the Swin patch-merging permutation; this file
 // brings the block's launch order, the downsample and the ConvNeXt sizes.  The depthwise kernel is in i2v_convnext.hip.
 //
 // A block runs in place on its stage's stream x (F, plane^2, w):
@@ -42,6 +42,9 @@ struct i2v_convnext : XfNet {
     const float *pe_w = nullptr, *pe_b = nullptr, *pe_nw = nullptr, *pe_nb = nullptr;
     std::vector<CnStage> stages;
     float *patches = nullptr, *emb = nullptr, *estats = nullptr;
+
+    float* hook_stream(int i) { return stages[i].x; }
+    int64_t hook_floats(int i) const { return stages[i].T() * stages[i].width; }
 };
 
 namespace {
@@ -70,21 +73,6 @@ int dw_run(I2VCnDwParams p, int frames, hipStream_t s) {
     if (eng::convnext_host::dw(p) != 0) return fail("convnext_host::dw: launch not planned");
 #endif
     return 0;
-}
-
-// the stem: Swin's patch embedding -- patch rows, Linear with bias, LayerNorm -- and its backward (as i2v_swin.cpp runs them)
-int embed(const float* img, int F, int Cin, int gsz, int P, const float* W, const float* b, const float* nw, const float* nb, float eps,
-          int dim, float* patches, float* emb, float* mean, float* rstd, float* tokens, hipStream_t s) {
-    VCHK(vit_patchify(img, patches, F, Cin, gsz, gsz, P, nullptr, 0, s));
-    VCHK(linear(patches, F * gsz * gsz, Cin * P * P, W, b, dim, nullptr, emb, nullptr, s));
-    return vit_layernorm(emb, (int64_t)F * gsz * gsz, dim, nw, nb, eps, tokens, mean, rstd, s);
-}
-
-int embed_bwd(const float* dtok, int F, int Cin, int gsz, int P, const float* W, const float* nw, int dim, const float* emb,
-              const float* mean, const float* rstd, float* demb, float* patches, float* gimg, int accumulate, hipStream_t s) {
-    VCHK(vit_layernorm_bwd(dtok, emb, mean, rstd, nw, (int64_t)F * gsz * gsz, dim, nullptr, nullptr, demb, s));
-    VCHK(linear_bwd(demb, F * gsz * gsz, dim, W, Cin * P * P, nullptr, patches, s));
-    return vit_patchify(nullptr, patches, F, Cin, gsz, gsz, P, gimg, accumulate, s);
 }
 
 int convnext_plan(i2v_convnext* n, const float* const* w, int nw, const int32_t* hooks, int n_hooks) {
@@ -179,32 +167,10 @@ int convnext_plan(i2v_convnext* n, const float* const* w, int nw, const int32_t*
     return 0;
 }
 
-}  // namespace
-
-extern "C" int i2v_convnext_create(int device, const i2v_convnext_config* cfg, const float* const* weights, int n_weights,
-                                   const int32_t* hook_stages, int n_hooks, int max_frames, i2v_convnext_handle* out) {
-    if (!cfg || !weights || !hook_stages || !out) return fail("i2v_convnext_create: null argument");
-    return create_net("i2v_convnext_create", "stage", device, max_frames, out, [&](i2v_convnext* n) {
-        n->cfg = *cfg;
-        return convnext_plan(n, weights, n_weights, hook_stages, n_hooks);
-    });
-}
-
-extern "C" int i2v_convnext_destroy(i2v_convnext_handle net) {
-    delete net;
-    return 0;
-}
-
-extern "C" int64_t i2v_convnext_workspace_bytes(i2v_convnext_handle net) { return net ? net->arena.bytes : -1; }
-
-extern "C" int i2v_convnext_forward(i2v_convnext_handle n, const float* x, int frames, void* stream) {
-    if (!n || !x) return fail("i2v_convnext_forward: null argument");
-    if (frames <= 0 || frames > n->max_frames) return fail("i2v_convnext_forward: %d frames, the net is planned for 1..%d", frames, n->max_frames);
-    hipStream_t s = (hipStream_t)stream;
+int convnext_forward(i2v_convnext* n, const float* x, int frames, hipStream_t s) {
     const i2v_convnext_config& c = n->cfg;
-    n->frames = frames;
     const int64_t esp = (int64_t)n->max_frames * n->gsz * n->gsz;
-    VCHK(embed(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, n->pe_nw, n->pe_nb, c.ln_eps, c.dim, n->patches, n->emb,
+    VCHK(ln_stem(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, n->pe_nw, n->pe_nb, c.ln_eps, c.dim, n->patches, n->emb,
                             n->estats, n->estats + esp, n->stages[0].x, s));
     for (int i = 0; i < n->ns; ++i) {
         CnStage& S = n->stages[i];
@@ -226,10 +192,7 @@ extern "C" int i2v_convnext_forward(i2v_convnext_handle n, const float* x, int f
     return 0;
 }
 
-extern "C" int i2v_convnext_backward(i2v_convnext_handle n, float* gx, int accumulate, void* stream) {
-    if (!n || !gx) return fail("i2v_convnext_backward: null argument");
-    if (n->frames <= 0) return fail("i2v_convnext_backward: no forward pass to differentiate");
-    hipStream_t s = (hipStream_t)stream;
+int convnext_backward(i2v_convnext* n, float* gx, int accumulate, hipStream_t s) {
     const i2v_convnext_config& c = n->cfg;
     const int frames = n->frames;
     for (int i = n->ns - 1; i >= 0; --i) {
@@ -255,19 +218,37 @@ extern "C" int i2v_convnext_backward(i2v_convnext_handle n, float* gx, int accum
         }
     }
     const int64_t esp = (int64_t)n->max_frames * n->gsz * n->gsz;
-    return embed_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_nw, c.dim, n->emb, n->estats, n->estats + esp,
+    return ln_stem_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_nw, c.dim, n->emb, n->estats, n->estats + esp,
                                   n->t1, n->patches, gx, accumulate, s);
+}
+
+}  // namespace
+
+extern "C" int i2v_convnext_create(int device, const i2v_convnext_config* cfg, const float* const* weights, int n_weights,
+                                   const int32_t* hook_stages, int n_hooks, int max_frames, i2v_convnext_handle* out) {
+    return xf_create("i2v_convnext_create", "stage", device, cfg, weights, hook_stages, max_frames, out, [&](i2v_convnext* n) {
+        n->cfg = *cfg;
+        return convnext_plan(n, weights, n_weights, hook_stages, n_hooks);
+    });
+}
+
+extern "C" int i2v_convnext_destroy(i2v_convnext_handle net) { return xf_destroy(net); }
+
+extern "C" int64_t i2v_convnext_workspace_bytes(i2v_convnext_handle net) { return xf_workspace_bytes(net); }
+
+extern "C" int i2v_convnext_forward(i2v_convnext_handle n, const float* x, int frames, void* stream) {
+    return xf_forward("i2v_convnext_forward", n, x, frames, stream, convnext_forward);
+}
+
+extern "C" int i2v_convnext_backward(i2v_convnext_handle n, float* gx, int accumulate, void* stream) {
+    return xf_backward("i2v_convnext_backward", n, gx, accumulate, stream, convnext_backward);
 }
 
 extern "C" int i2v_convnext_hook_info(i2v_convnext_handle n, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride,
                                       int64_t* D) {
-    if (!n || !n->hooks.has(hook)) return fail("i2v_convnext_hook_info: no hook %d", hook);
-    const CnStage& S = n->stages[n->hooks.at[hook]];
-    return hook_info(S.x, n->hooks.grad[hook], S.T() * S.width, act, act_stride, grad, grad_stride, D);
+    return xf_hook_info("i2v_convnext_hook_info", n, hook, act, act_stride, grad, grad_stride, D);
 }
 
 extern "C" int i2v_convnext_read_hook(i2v_convnext_handle n, int hook, int which, float* out, int frames, void* stream) {
-    if (!n || !out || !n->hooks.has(hook)) return fail("i2v_convnext_read_hook: no hook %d", hook);
-    const CnStage& S = n->stages[n->hooks.at[hook]];
-    return read_hook("i2v_convnext_read_hook", which ? n->hooks.grad[hook] : S.x, S.T() * S.width, out, frames, n->max_frames, stream);
+    return xf_read_hook("i2v_convnext_read_hook", n, hook, which, out, frames, stream);
 }

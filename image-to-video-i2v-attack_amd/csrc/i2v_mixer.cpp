@@ -36,8 +36,10 @@ struct i2v_mixer : XfNet {
     int nb = 0, gsz = 0, S = 0;
     const float *pe_w = nullptr, *pe_b = nullptr;
     std::vector<MxBlock> blocks;
-    std::vector<float*> hook_act;                // per hook: the stream after its block
     float *patches = nullptr, *stream = nullptr;
+
+    float* hook_stream(int b) { return blocks[b].out; }      // (a hooked ResMLP block writes a buffer of its own)
+    int64_t hook_floats(int) const { return (int64_t)S * cfg.dim; }
 };
 
 namespace {
@@ -64,18 +66,6 @@ int tok_run(I2VMixTokParams p, int frames, hipStream_t s) {
     if (eng::mixer_host::tokens(p) != 0) return fail("mixer_host::tokens: launch not planned");
 #endif
     return 0;
-}
-
-// dx (M, K) = dy (M, N) W + add, W (N, K): linear_bwd with vit_gemm's residual operand (which may be dx itself)
-int linear_bwd_add(const float* dy, int M, int N, const float* W, int K, const float* add, float* dx, hipStream_t s) {
-    VitGemm g{};
-    g.A = dy; g.a_sm = N; g.a_sk = 1;
-    g.B = W; g.b_sk = K; g.b_sn = 1;
-    g.C = dx; g.c_sm = K;
-    g.R = add;
-    g.M = M; g.N = K; g.K = N; g.batch = 1; g.nb_in = 1; g.alpha = 1.f;
-    g.mode = VIT_EPI_PLAIN;
-    return vit_gemm(g, s);
 }
 
 // the (rows, cols) host matrix transposed onto the device
@@ -159,14 +149,12 @@ int mixer_plan(i2v_mixer* n, const float* const* w, int nw, const int32_t* hooks
             B.out = n->stream;                                                  // (a hooked block: its hook's buffer, below)
         }
     }
-    n->hook_act.resize(n_hooks);
     for (int i = 0; i < n_hooks; ++i) {
         MxBlock& B = n->blocks[hooks[i]];
         if (res) {
             if (!(B.out = A.alloc(FT * D))) return A.oom("a hooked stream");
             if (hooks[i] + 1 < n->nb) n->blocks[hooks[i] + 1].x = B.out;
         }
-        n->hook_act[i] = B.out;
         VCHK(n->hooks.add(A, hooks[i], FT * D));
     }
     // the token launches
@@ -192,34 +180,11 @@ int mixer_plan(i2v_mixer* n, const float* const* w, int nw, const int32_t* hooks
     return 0;
 }
 
-}  // namespace
-
-extern "C" int i2v_mixer_create(int device, const i2v_mixer_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_blocks,
-                                int n_hooks, int max_frames, i2v_mixer_handle* out) {
-    if (!cfg || !weights || !hook_blocks || !out) return fail("i2v_mixer_create: null argument");
-    return create_net("i2v_mixer_create", "block", device, max_frames, out, [&](i2v_mixer* n) {
-        n->cfg = *cfg;
-        return mixer_plan(n, weights, n_weights, hook_blocks, n_hooks);
-    });
-}
-
-extern "C" int i2v_mixer_destroy(i2v_mixer_handle net) {
-    delete net;
-    return 0;
-}
-
-extern "C" int64_t i2v_mixer_workspace_bytes(i2v_mixer_handle net) { return net ? net->arena.bytes : -1; }
-
-extern "C" int i2v_mixer_forward(i2v_mixer_handle n, const float* x, int frames, void* stream) {
-    if (!n || !x) return fail("i2v_mixer_forward: null argument");
-    if (frames <= 0 || frames > n->max_frames) return fail("i2v_mixer_forward: %d frames, the net is planned for 1..%d", frames, n->max_frames);
-    hipStream_t s = (hipStream_t)stream;
+int mixer_forward(i2v_mixer* n, const float* x, int frames, hipStream_t s) {
     const i2v_mixer_config& c = n->cfg;
-    n->frames = frames;
     const int D = c.dim, M = frames * n->S;
     const int64_t FT = (int64_t)frames * n->S, sp = (int64_t)n->max_frames * n->S;
-    VCHK(vit_patchify(x, n->patches, frames, c.in_chans, n->gsz, n->gsz, c.patch, nullptr, 0, s));
-    VCHK(linear(n->patches, M, c.in_chans * c.patch * c.patch, n->pe_w, n->pe_b, D, nullptr, n->blocks[0].x, nullptr, s));
+    VCHK(patch_rows(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, D, n->patches, n->blocks[0].x, s));
     for (MxBlock& B : n->blocks) {
         if (c.kind == 0) {
             float* st = B.stats;                                                  // [mean1 | rstd1 | mean2 | rstd2] at max_frames spacing
@@ -237,18 +202,15 @@ extern "C" int i2v_mixer_forward(i2v_mixer_handle n, const float* x, int frames,
     return 0;
 }
 
-extern "C" int i2v_mixer_backward(i2v_mixer_handle n, float* gx, int accumulate, void* stream) {
-    if (!n || !gx) return fail("i2v_mixer_backward: null argument");
-    if (n->frames <= 0) return fail("i2v_mixer_backward: no forward pass to differentiate");
-    hipStream_t s = (hipStream_t)stream;
+int mixer_backward(i2v_mixer* n, float* gx, int accumulate, hipStream_t s) {
     const i2v_mixer_config& c = n->cfg;
     const int frames = n->frames, D = c.dim, M = frames * n->S;
     const int64_t FT = (int64_t)frames * n->S, sp = (int64_t)n->max_frames * n->S;
     for (int b = n->nb - 1; b >= 0; --b) {
         MxBlock& B = n->blocks[b];
         // gradient of the block's output: the deepest block's hook view, the running gradient G (which holds the later hooks' too) below it
-        const float* gin = b == n->nb - 1 ? n->hooks.grad_at(b) : n->G;
-        const float* below = b ? n->hooks.grad_at(b - 1) : nullptr;              // a hook at the stream this block reads
+        const float* gin = n->grad_in(b, n->nb);
+        const float* below = n->grad_below(b);                                   // a hook at the stream this block reads
         VCHK(linear_bwd(gin, M, D, B.fc2w, c.mlp, B.h, n->t2, s));               // dh = (g fc2) * gelu'(h)
         if (c.kind == 0) {
             float* st = B.stats;
@@ -262,18 +224,36 @@ extern "C" int i2v_mixer_backward(i2v_mixer_handle n, float* gx, int accumulate,
             VCHK(tok_run(B.bwd, frames, s));                                     // G = dy + a1 * W^T (ls1 * dy) (+ hook)
         }
     }
-    VCHK(linear_bwd(n->G, M, D, n->pe_w, c.in_chans * c.patch * c.patch, nullptr, n->patches, s));
-    return vit_patchify(nullptr, n->patches, frames, c.in_chans, n->gsz, n->gsz, c.patch, gx, accumulate, s);
+    return patch_rows_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, D, n->patches, gx, accumulate, s);
+}
+
+}  // namespace
+
+extern "C" int i2v_mixer_create(int device, const i2v_mixer_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_blocks,
+                                int n_hooks, int max_frames, i2v_mixer_handle* out) {
+    return xf_create("i2v_mixer_create", "block", device, cfg, weights, hook_blocks, max_frames, out, [&](i2v_mixer* n) {
+        n->cfg = *cfg;
+        return mixer_plan(n, weights, n_weights, hook_blocks, n_hooks);
+    });
+}
+
+extern "C" int i2v_mixer_destroy(i2v_mixer_handle net) { return xf_destroy(net); }
+
+extern "C" int64_t i2v_mixer_workspace_bytes(i2v_mixer_handle net) { return xf_workspace_bytes(net); }
+
+extern "C" int i2v_mixer_forward(i2v_mixer_handle n, const float* x, int frames, void* stream) {
+    return xf_forward("i2v_mixer_forward", n, x, frames, stream, mixer_forward);
+}
+
+extern "C" int i2v_mixer_backward(i2v_mixer_handle n, float* gx, int accumulate, void* stream) {
+    return xf_backward("i2v_mixer_backward", n, gx, accumulate, stream, mixer_backward);
 }
 
 extern "C" int i2v_mixer_hook_info(i2v_mixer_handle n, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride,
                                    int64_t* D) {
-    if (!n || !n->hooks.has(hook)) return fail("i2v_mixer_hook_info: no hook %d", hook);
-    return hook_info(n->hook_act[hook], n->hooks.grad[hook], (int64_t)n->S * n->cfg.dim, act, act_stride, grad, grad_stride, D);
+    return xf_hook_info("i2v_mixer_hook_info", n, hook, act, act_stride, grad, grad_stride, D);
 }
 
 extern "C" int i2v_mixer_read_hook(i2v_mixer_handle n, int hook, int which, float* out, int frames, void* stream) {
-    if (!n || !out || !n->hooks.has(hook)) return fail("i2v_mixer_read_hook: no hook %d", hook);
-    return read_hook("i2v_mixer_read_hook", which ? n->hooks.grad[hook] : n->hook_act[hook], (int64_t)n->S * n->cfg.dim, out, frames,
-                     n->max_frames, stream);
+    return xf_read_hook("i2v_mixer_read_hook", n, hook, which, out, frames, stream);
 }

@@ -1,29 +1,13 @@
 // Planner and executor of the Swin surrogates (include/i2v_swin.h): one arena per (net, max frames), the forward as a fixed launch
 // sequence up to the deepest hooked stage, and the input-gradient pass -- no weight gradients, as the CNN and ViT paths.  The arena, the
-// hook list and the pre-norm block are shared with the ViT planner (i2v_xf.h); this file brings the embedding with its LayerNorm, the
-// stages with their window attention step and patch merging, and the Swin sizes.  The window attention and patch-merging kernels are in
+// hook list, the seven entries' guards, the LayerNorm stem and the pre-norm block are those of i2v_xf.h; this file brings the stages with
+// their window attention step and patch merging, and the Swin sizes.  The window attention and patch-merging kernels are in
 // i2v_swin.hip; the linear layers, LayerNorms and patch rows are the ViT kernels.
 #include "../../include/i2v_swin.h"
 #include "i2v_swin_kernels.h"
 #include "i2v_xf.h"
 
 namespace {
-
-int embed(const float* img, int F, int Cin, int gsz, int P, const float* W, const float* b, const float* nw, const float* nb, float eps,
-          int dim, float* patches, float* emb, float* mean, float* rstd, float* tokens, hipStream_t s) {
-    const int np = gsz * gsz, KP = Cin * P * P;
-    VCHK(vit_patchify(img, patches, F, Cin, gsz, gsz, P, nullptr, 0, s));
-    VCHK(linear(patches, F * np, KP, W, b, dim, nullptr, emb, nullptr, s));
-    return vit_layernorm(emb, (int64_t)F * np, dim, nw, nb, eps, tokens, mean, rstd, s);
-}
-
-int embed_bwd(const float* dtok, int F, int Cin, int gsz, int P, const float* W, const float* nw, int dim, const float* emb,
-              const float* mean, const float* rstd, float* demb, float* patches, float* gimg, int accumulate, hipStream_t s) {
-    const int np = gsz * gsz, KP = Cin * P * P;
-    VCHK(vit_layernorm_bwd(dtok, emb, mean, rstd, nw, (int64_t)F * np, dim, nullptr, nullptr, demb, s));
-    VCHK(linear_bwd(demb, F * np, dim, W, KP, nullptr, patches, s));
-    return vit_patchify(nullptr, patches, F, Cin, gsz, gsz, P, gimg, accumulate, s);
-}
 
 struct Stage {
     int grid = 0, width = 0, heads = 0, ws = 0;
@@ -45,6 +29,8 @@ struct i2v_swin : XfNet {
     std::vector<Stage> stages;
     float *patches = nullptr, *emb = nullptr, *estats = nullptr;
 
+    float* hook_stream(int i) { return stages[i].out; }
+    int64_t hook_floats(int i) const { return stages[i].T() * stages[i].width; }
     BlockRun run(const Stage& S, int frames, hipStream_t s) const {
         return {frames, (int)S.T(), S.width, 4 * S.width, max_frames * S.T(), cfg.ln_eps, t1, t2, dqkv, G, s};
     }
@@ -137,32 +123,10 @@ int swin_plan(i2v_swin* n, const float* const* w, int nw, const int32_t* hooks, 
     return 0;
 }
 
-}  // namespace
-
-extern "C" int i2v_swin_create(int device, const i2v_swin_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_stages,
-                               int n_hooks, int max_frames, i2v_swin_handle* out) {
-    if (!cfg || !weights || !hook_stages || !out) return fail("i2v_swin_create: null argument");
-    return create_net("i2v_swin_create", "stage", device, max_frames, out, [&](i2v_swin* n) {
-        n->cfg = *cfg;
-        return swin_plan(n, weights, n_weights, hook_stages, n_hooks);
-    });
-}
-
-extern "C" int i2v_swin_destroy(i2v_swin_handle net) {
-    delete net;
-    return 0;
-}
-
-extern "C" int64_t i2v_swin_workspace_bytes(i2v_swin_handle net) { return net ? net->arena.bytes : -1; }
-
-extern "C" int i2v_swin_forward(i2v_swin_handle n, const float* x, int frames, void* stream) {
-    if (!n || !x) return fail("i2v_swin_forward: null argument");
-    if (frames <= 0 || frames > n->max_frames) return fail("i2v_swin_forward: %d frames, the net is planned for 1..%d", frames, n->max_frames);
-    hipStream_t s = (hipStream_t)stream;
+int swin_forward(i2v_swin* n, const float* x, int frames, hipStream_t s) {
     const i2v_swin_config& c = n->cfg;
-    n->frames = frames;
     const int64_t esp = (int64_t)n->max_frames * n->gsz * n->gsz;
-    VCHK(embed(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, n->pe_nw, n->pe_nb, c.ln_eps, c.dim, n->patches, n->emb, n->estats,
+    VCHK(ln_stem(x, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_b, n->pe_nw, n->pe_nb, c.ln_eps, c.dim, n->patches, n->emb, n->estats,
                n->estats + esp, n->stages[0].blocks[0].x, s));
     for (int i = 0; i < n->ns; ++i) {
         Stage& S = n->stages[i];
@@ -182,10 +146,7 @@ extern "C" int i2v_swin_forward(i2v_swin_handle n, const float* x, int frames, v
     return 0;
 }
 
-extern "C" int i2v_swin_backward(i2v_swin_handle n, float* gx, int accumulate, void* stream) {
-    if (!n || !gx) return fail("i2v_swin_backward: null argument");
-    if (n->frames <= 0) return fail("i2v_swin_backward: no forward pass to differentiate");
-    hipStream_t s = (hipStream_t)stream;
+int swin_backward(i2v_swin* n, float* gx, int accumulate, hipStream_t s) {
     const i2v_swin_config& c = n->cfg;
     const int frames = n->frames;
     for (int i = n->ns - 1; i >= 0; --i) {
@@ -209,20 +170,38 @@ extern "C" int i2v_swin_backward(i2v_swin_handle n, float* gx, int accumulate, v
         }
     }
     const int64_t esp = (int64_t)n->max_frames * n->gsz * n->gsz;
-    return embed_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_nw, c.dim, n->emb, n->estats, n->estats + esp, n->t1, n->patches,
+    return ln_stem_bwd(n->G, frames, c.in_chans, n->gsz, c.patch, n->pe_w, n->pe_nw, c.dim, n->emb, n->estats, n->estats + esp, n->t1, n->patches,
                      gx, accumulate, s);
 }
 
+}  // namespace
+
+extern "C" int i2v_swin_create(int device, const i2v_swin_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_stages,
+                               int n_hooks, int max_frames, i2v_swin_handle* out) {
+    return xf_create("i2v_swin_create", "stage", device, cfg, weights, hook_stages, max_frames, out, [&](i2v_swin* n) {
+        n->cfg = *cfg;
+        return swin_plan(n, weights, n_weights, hook_stages, n_hooks);
+    });
+}
+
+extern "C" int i2v_swin_destroy(i2v_swin_handle net) { return xf_destroy(net); }
+
+extern "C" int64_t i2v_swin_workspace_bytes(i2v_swin_handle net) { return xf_workspace_bytes(net); }
+
+extern "C" int i2v_swin_forward(i2v_swin_handle n, const float* x, int frames, void* stream) {
+    return xf_forward("i2v_swin_forward", n, x, frames, stream, swin_forward);
+}
+
+extern "C" int i2v_swin_backward(i2v_swin_handle n, float* gx, int accumulate, void* stream) {
+    return xf_backward("i2v_swin_backward", n, gx, accumulate, stream, swin_backward);
+}
+
 extern "C" int i2v_swin_hook_info(i2v_swin_handle n, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride, int64_t* D) {
-    if (!n || !n->hooks.has(hook)) return fail("i2v_swin_hook_info: no hook %d", hook);
-    const Stage& S = n->stages[n->hooks.at[hook]];
-    return hook_info(S.out, n->hooks.grad[hook], S.T() * S.width, act, act_stride, grad, grad_stride, D);
+    return xf_hook_info("i2v_swin_hook_info", n, hook, act, act_stride, grad, grad_stride, D);
 }
 
 extern "C" int i2v_swin_read_hook(i2v_swin_handle n, int hook, int which, float* out, int frames, void* stream) {
-    if (!n || !out || !n->hooks.has(hook)) return fail("i2v_swin_read_hook: no hook %d", hook);
-    const Stage& S = n->stages[n->hooks.at[hook]];
-    return read_hook("i2v_swin_read_hook", which ? n->hooks.grad[hook] : S.out, S.T() * S.width, out, frames, n->max_frames, stream);
+    return xf_read_hook("i2v_swin_read_hook", n, hook, which, out, frames, stream);
 }
 
 // ---- the kernels on their own ----
@@ -243,10 +222,10 @@ extern "C" int i2v_swin_merge_bwd_f32(const float* dout, int frames, int H, int 
 extern "C" int i2v_swin_embed_f32(const float* img, int frames, int in_chans, int g, int patch, const float* W, const float* b,
                                   const float* norm_w, const float* norm_b, float eps, int dim, float* patches, float* emb, float* mean,
                                   float* rstd, float* tokens, void* stream) {
-    return embed(img, frames, in_chans, g, patch, W, b, norm_w, norm_b, eps, dim, patches, emb, mean, rstd, tokens, (hipStream_t)stream);
+    return ln_stem(img, frames, in_chans, g, patch, W, b, norm_w, norm_b, eps, dim, patches, emb, mean, rstd, tokens, (hipStream_t)stream);
 }
 extern "C" int i2v_swin_embed_bwd_f32(const float* dtokens, int frames, int in_chans, int g, int patch, const float* W, const float* norm_w,
                                       int dim, const float* emb, const float* mean, const float* rstd, float* demb, float* patches,
                                       float* gimg, int accumulate, void* stream) {
-    return embed_bwd(dtokens, frames, in_chans, g, patch, W, norm_w, dim, emb, mean, rstd, demb, patches, gimg, accumulate, (hipStream_t)stream);
+    return ln_stem_bwd(dtokens, frames, in_chans, g, patch, W, norm_w, dim, emb, mean, rstd, demb, patches, gimg, accumulate, (hipStream_t)stream);
 }

@@ -56,31 +56,6 @@ struct TwStage {
     float* stream_after(size_t b) { return b + 1 < blocks.size() ? blocks[b + 1].x : out; }
 };
 
-// dx (M, K) = dy (M, N) W + R; R may be dx
-int tw_linear_bwd_add(const float* dy, int M, int N, const float* W, int K, const float* R, float* dx, hipStream_t s) {
-    VitGemm g{};
-    g.A = dy; g.a_sm = N; g.a_sk = 1;
-    g.B = W; g.b_sk = K; g.b_sn = 1;
-    g.C = dx; g.c_sm = K;
-    g.R = R;
-    g.M = M; g.N = K; g.K = N; g.batch = 1; g.nb_in = 1; g.alpha = 1.f;
-    g.mode = VIT_EPI_PLAIN;
-    return vit_gemm(g, s);
-}
-
-// C[f, h] (M, N) = alpha A[f, h] (M, K) B[f, h] (K, N) over batch = frames x heads (outer = frame, inner = head)
-int tw_bgemm(const float* A, int64_t a_bo, int64_t a_bi, int64_t a_sm, int64_t a_sk, const float* B, int64_t b_bo, int64_t b_bi, int64_t b_sk,
-             int64_t b_sn, float* C, int64_t c_bo, int64_t c_bi, int64_t c_sm, int M, int N, int K, int frames, int heads, float alpha,
-             hipStream_t s) {
-    VitGemm g{};
-    g.A = A; g.a_bo = a_bo; g.a_bi = a_bi; g.a_sm = a_sm; g.a_sk = a_sk;
-    g.B = B; g.b_bo = b_bo; g.b_bi = b_bi; g.b_sk = b_sk; g.b_sn = b_sn;
-    g.C = C; g.c_bo = c_bo; g.c_bi = c_bi; g.c_sm = c_sm;
-    g.M = M; g.N = N; g.K = K; g.batch = frames * heads; g.nb_in = heads; g.alpha = alpha;
-    g.mode = VIT_EPI_PLAIN;
-    return vit_gemm(g, s);
-}
-
 }  // namespace
 
 struct i2v_twins : XfNet {
@@ -97,6 +72,14 @@ struct i2v_twins : XfNet {
         a.q = B.q; a.kv = B.kv; a.F = frames; a.Tq = (int)S.T(); a.Tk = (int)S.Tk(); a.H = S.heads; a.dh = S.width / S.heads;
         a.scale = 1.f / sqrtf((float)a.dh);
         return a;
+    }
+    float* hook_stream(int k) { return stages[k].out; }
+    int64_t hook_floats(int k) const { return stages[k].T() * stages[k].width; }
+    // the GSA core's operands for the shared launches: q (F, T, D), k and v the two halves of kv (F, Tk, 2 D)
+    XfAttn shared(const TwStage& S, const TwBlock& B, int frames) const {
+        const int64_t D = S.width;
+        return {B.q, B.kv, B.kv + D, S.T() * D, D, S.Tk() * 2 * D, 2 * D, frames, (int)S.T(), (int)S.Tk(), S.heads, S.width / S.heads,
+                1.f / sqrtf((float)(S.width / S.heads))};
     }
     XcitDw3 dw(const TwStage& S, const float* x, const float* w, const float* b, float* y, int frames) const {
         XcitDw3 d{};
@@ -141,7 +124,7 @@ int twins_plan(i2v_twins* n, const float* const* w, int nw, const int32_t* hooks
     n->composed = sw && !strcmp(sw, "0");
     for (int k = 0; k < n->ns; ++k) {
         const int64_t g = g0 >> k, D = c.dims[k], M = c.mlp[k], sr = c.sr[k], T = g * g, Tk = (g / sr) * (g / sr), FT = F * T;
-        const int64_t FP = n->composed ? FT * c.heads[k] * ((Tk + 3) / 4 * 4) : 0;      // one block's saved probabilities
+        const int64_t FP = n->composed ? FT * c.heads[k] * xf_probs_ld((int)Tk) : 0;      // one block's saved probabilities
         for (int64_t v : {D * (k ? 4 * c.dims[k - 1] : KP), D, D, D}) sizes.push_back(v);
         acts += FT * D + 2 * FT;                                            // the embedding before its LayerNorm, its statistics
         for (int b = 0; b < c.depths[k]; ++b) {
@@ -205,7 +188,7 @@ int twins_plan(i2v_twins* n, const float* const* w, int nw, const int32_t* hooks
                     if (!(B.srp = A.alloc(FK * D)) || !(B.sstats = A.alloc(2 * FK))) return A.oom("saved activations of a block");
                 }
                 if (!(B.q = A.alloc(FT * D)) || !(B.kv = A.alloc(2 * FK * D))) return A.oom("saved activations of a block");
-                if (n->composed && !(B.P = A.alloc(FT * S.heads * ((S.Tk() + 3) / 4 * 4)))) return A.oom("saved probabilities of a block");
+                if (n->composed && !(B.P = A.alloc(FT * S.heads * xf_probs_ld((int)S.Tk())))) return A.oom("saved probabilities of a block");
             }
             B.weights(&dev[w0], &dev[wi]);                                  // (an LSA block's qkv at [2..3]; a GSA block's are its own)
             wi += 8;
@@ -244,26 +227,6 @@ int twins_plan(i2v_twins* n, const float* const* w, int nw, const int32_t* hooks
     return 0;
 }
 
-// The GSA core on the shared launches (I2V_TWINS_ATTN=0): t1 = softmax(scale q k^T) v with P kept in B.P, rows of ld floats
-int tw_gsa_composed(i2v_twins* n, const TwStage& S, const TwBlock& B, int frames, hipStream_t s) {
-    const int D = S.width, H = S.heads, dh = D / H, T = (int)S.T(), Tk = (int)S.Tk(), ld = (Tk + 3) / 4 * 4;
-    const int64_t tok = (int64_t)T * D, key = (int64_t)Tk * 2 * D, sq = (int64_t)T * ld;
-    VCHK(tw_bgemm(B.q, tok, dh, D, 1, B.kv, key, dh, 1, 2 * D, B.P, H * sq, sq, ld, T, Tk, dh, frames, H, 1.f / sqrtf((float)dh), s));
-    VCHK(twins_softmax(B.P, (int64_t)frames * H * T, Tk, ld, s));
-    return tw_bgemm(B.P, H * sq, sq, ld, 1, B.kv + D, key, dh, 2 * D, 1, n->t1, tok, dh, D, T, dh, Tk, frames, H, 1.f, s);
-}
-
-// ... and its backward: dout in t1 -> dq in dqkv, (dk, dv) in skv
-int tw_gsa_composed_bwd(i2v_twins* n, const TwStage& S, const TwBlock& B, int frames, hipStream_t s) {
-    const int D = S.width, H = S.heads, dh = D / H, T = (int)S.T(), Tk = (int)S.Tk(), ld = (Tk + 3) / 4 * 4;
-    const int64_t tok = (int64_t)T * D, key = (int64_t)Tk * 2 * D, sq = (int64_t)T * ld;
-    VCHK(tw_bgemm(n->t1, tok, dh, D, 1, B.kv + D, key, dh, 1, 2 * D, n->dS, H * sq, sq, ld, T, Tk, dh, frames, H, 1.f, s));      // dP = dout v^T
-    VCHK(twins_softmax_bwd(n->dS, B.P, (int64_t)frames * H * T, Tk, ld, 1.f / sqrtf((float)dh), s));
-    VCHK(tw_bgemm(n->dS, H * sq, sq, ld, 1, B.kv, key, dh, 2 * D, 1, n->dqkv, tok, dh, D, T, dh, Tk, frames, H, 1.f, s));        // dq = dS k
-    VCHK(tw_bgemm(n->dS, H * sq, sq, 1, ld, B.q, tok, dh, D, 1, n->skv, key, dh, 2 * D, Tk, dh, T, frames, H, 1.f, s));          // dk = dS^T q
-    return tw_bgemm(B.P, H * sq, sq, 1, ld, n->t1, tok, dh, D, 1, n->skv + D, key, dh, 2 * D, Tk, dh, T, frames, H, 1.f, s);     // dv = P^T dout
-}
-
 int tw_block_forward(i2v_twins* n, const TwStage& S, const TwBlock& B, int frames, float* out, hipStream_t s) {
     const i2v_twins_config& c = n->cfg;
     const int D = S.width, g = S.grid, M = frames * (int)S.T(), Mk = frames * (int)S.Tk(), dh = D / S.heads;
@@ -284,7 +247,7 @@ int tw_block_forward(i2v_twins* n, const TwStage& S, const TwBlock& B, int frame
         }
         VCHK(linear(u, Mk, D, B.kvw, B.kvb, 2 * D, nullptr, B.kv, nullptr, s));
         if (n->composed) {
-            VCHK(tw_gsa_composed(n, S, B, frames, s));
+            VCHK(xf_attention(n->shared(S, B, frames), B.P, n->t1, s));             // P kept in B.P
         } else {
             TwinsAttn a = n->attn(S, B, frames);
             a.out = n->t1;
@@ -312,7 +275,7 @@ int tw_block_backward(i2v_twins* n, const TwStage& S, const TwBlock& B, int fram
         VCHK(linear_bwd(n->dqkv, M, 3 * D, B.qkvw, D, nullptr, n->t1, s));                     // d LN1 out
     } else {
         if (n->composed) {
-            VCHK(tw_gsa_composed_bwd(n, S, B, frames, s));
+            VCHK(xf_attention_bwd(n->shared(S, B, frames), B.P, n->t1, n->dS, n->dqkv, n->skv, n->skv + D, s));      // dq; (dk, dv) in skv
         } else {
             TwinsAttn a = n->attn(S, B, frames);
             a.dout = n->t1; a.dq = n->dqkv; a.dkv = n->skv;
@@ -325,43 +288,20 @@ int tw_block_backward(i2v_twins* n, const TwStage& S, const TwBlock& B, int fram
             VCHK(linear_bwd(n->st2, Mk, D, B.srw, S.sr * S.sr * D, nullptr, n->rows, s));
             VCHK(twins_block_scatter(n->rows, n->t1, frames, g, g, D, S.sr, 1, s));            // ... plus the kv path
         } else {                                                                               // (R is C: i2v_vit_kernels.h allows it)
-            VCHK(tw_linear_bwd_add(n->skv, M, 2 * D, B.kvw, D, n->t1, n->t1, s));
+            VCHK(linear_bwd_add(n->skv, M, 2 * D, B.kvw, D, n->t1, n->t1, s));
         }
     }
     return vit_layernorm_bwd(n->t1, B.x, st, st + sp, B.n1w, FT, D, n->G, nullptr, n->G, s);   // G = dx
 }
 
-}  // namespace
-
-extern "C" int i2v_twins_create(int device, const i2v_twins_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_stages,
-                                int n_hooks, int max_frames, i2v_twins_handle* out) {
-    if (!cfg || !weights || !hook_stages || !out) return fail("i2v_twins_create: null argument");
-    return create_net("i2v_twins_create", "stage", device, max_frames, out, [&](i2v_twins* n) {
-        n->cfg = *cfg;
-        return twins_plan(n, weights, n_weights, hook_stages, n_hooks);
-    });
-}
-
-extern "C" int i2v_twins_destroy(i2v_twins_handle net) {
-    delete net;
-    return 0;
-}
-
-extern "C" int64_t i2v_twins_workspace_bytes(i2v_twins_handle net) { return net ? net->arena.bytes : -1; }
-
-extern "C" int i2v_twins_forward(i2v_twins_handle n, const float* x, int frames, void* stream) {
-    if (!n || !x) return fail("i2v_twins_forward: null argument");
-    if (frames <= 0 || frames > n->max_frames) return fail("i2v_twins_forward: %d frames, the net is planned for 1..%d", frames, n->max_frames);
-    hipStream_t s = (hipStream_t)stream;
+int twins_forward(i2v_twins* n, const float* x, int frames, hipStream_t s) {
     const i2v_twins_config& c = n->cfg;
-    n->frames = frames;
     for (int k = 0; k < n->ns; ++k) {
         TwStage& S = n->stages[k];
         const int D = S.width, g = S.grid, M = frames * (int)S.T();
         const int64_t sp = (int64_t)n->max_frames * S.T();
         if (k == 0) {                                                       // the patch embedding: rows, Linear, LayerNorm
-            VCHK(vit_patchify(x, n->patches, frames, c.in_chans, g, g, c.patch, nullptr, 0, s));
-            VCHK(linear(n->patches, M, c.in_chans * c.patch * c.patch, S.pew, S.peb, D, nullptr, S.emb, nullptr, s));
+            VCHK(patch_rows(x, frames, c.in_chans, g, c.patch, S.pew, S.peb, D, n->patches, S.emb, s));
         } else {
             const TwStage& Pv = n->stages[k - 1];
             VCHK(swin_merge_gather(Pv.out, frames, Pv.grid, Pv.grid, Pv.width, n->rows, s));
@@ -376,10 +316,7 @@ extern "C" int i2v_twins_forward(i2v_twins_handle n, const float* x, int frames,
     return 0;
 }
 
-extern "C" int i2v_twins_backward(i2v_twins_handle n, float* gx, int accumulate, void* stream) {
-    if (!n || !gx) return fail("i2v_twins_backward: null argument");
-    if (n->frames <= 0) return fail("i2v_twins_backward: no forward pass to differentiate");
-    hipStream_t s = (hipStream_t)stream;
+int twins_backward(i2v_twins* n, float* gx, int accumulate, hipStream_t s) {
     const i2v_twins_config& c = n->cfg;
     const int frames = n->frames;
     for (int k = n->ns - 1; k >= 0; --k) {
@@ -402,23 +339,40 @@ extern "C" int i2v_twins_backward(i2v_twins_handle n, float* gx, int accumulate,
             VCHK(linear_bwd(n->t1, M, D, S.pew, 4 * Pv.width, nullptr, n->rows, s));
             VCHK(swin_merge_scatter(n->rows, frames, Pv.grid, Pv.grid, Pv.width, n->hooks.grad_at(k - 1), n->G, s));
         } else {
-            VCHK(linear_bwd(n->t1, M, D, S.pew, c.in_chans * c.patch * c.patch, nullptr, n->patches, s));
-            VCHK(vit_patchify(nullptr, n->patches, frames, c.in_chans, g, g, c.patch, gx, accumulate, s));
+            VCHK(patch_rows_bwd(n->t1, frames, c.in_chans, g, c.patch, S.pew, D, n->patches, gx, accumulate, s));
         }
     }
     return 0;
 }
 
+}  // namespace
+
+extern "C" int i2v_twins_create(int device, const i2v_twins_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_stages,
+                                int n_hooks, int max_frames, i2v_twins_handle* out) {
+    return xf_create("i2v_twins_create", "stage", device, cfg, weights, hook_stages, max_frames, out, [&](i2v_twins* n) {
+        n->cfg = *cfg;
+        return twins_plan(n, weights, n_weights, hook_stages, n_hooks);
+    });
+}
+
+extern "C" int i2v_twins_destroy(i2v_twins_handle net) { return xf_destroy(net); }
+
+extern "C" int64_t i2v_twins_workspace_bytes(i2v_twins_handle net) { return xf_workspace_bytes(net); }
+
+extern "C" int i2v_twins_forward(i2v_twins_handle n, const float* x, int frames, void* stream) {
+    return xf_forward("i2v_twins_forward", n, x, frames, stream, twins_forward);
+}
+
+extern "C" int i2v_twins_backward(i2v_twins_handle n, float* gx, int accumulate, void* stream) {
+    return xf_backward("i2v_twins_backward", n, gx, accumulate, stream, twins_backward);
+}
+
 extern "C" int i2v_twins_hook_info(i2v_twins_handle n, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride, int64_t* D) {
-    if (!n || !n->hooks.has(hook)) return fail("i2v_twins_hook_info: no hook %d", hook);
-    const TwStage& S = n->stages[n->hooks.at[hook]];
-    return hook_info(S.out, n->hooks.grad[hook], S.T() * S.width, act, act_stride, grad, grad_stride, D);
+    return xf_hook_info("i2v_twins_hook_info", n, hook, act, act_stride, grad, grad_stride, D);
 }
 
 extern "C" int i2v_twins_read_hook(i2v_twins_handle n, int hook, int which, float* out, int frames, void* stream) {
-    if (!n || !out || !n->hooks.has(hook)) return fail("i2v_twins_read_hook: no hook %d", hook);
-    const TwStage& S = n->stages[n->hooks.at[hook]];
-    return read_hook("i2v_twins_read_hook", which ? n->hooks.grad[hook] : S.out, S.T() * S.width, out, frames, n->max_frames, stream);
+    return xf_read_hook("i2v_twins_read_hook", n, hook, which, out, frames, stream);
 }
 
 // ---- the kernels on their own ----

@@ -361,9 +361,3 @@ int twins_window_attention_bwd(const float* qkv, const float* dout, int F, int H
     if (why) return refuse("twins_window_attention_bwd", why);
     return swin_window_attention_bwd(qkv, dout, F, H, W, ws, 0, heads, dh, zero_table, dqkv, s);
 }
-
-int twins_softmax(float* X, int64_t rows, int N, int ld, hipStream_t s) { return vit_softmax(X, rows, N, ld, s); }
-
-int twins_softmax_bwd(float* dX, const float* P, int64_t rows, int N, int ld, float scale, hipStream_t s) {
-    return vit_softmax_bwd(dX, P, rows, N, ld, scale, s);
-}

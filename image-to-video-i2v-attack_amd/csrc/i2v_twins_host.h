@@ -1,6 +1,6 @@
 // The Twins launches (i2v_twins_kernels.h) as plain scalar C++ on the backend's memory: what the planner runs where the library has no
 // i2v_twins.hip (no -DI2V_HAVE_TWINS: the host simulation's one-file build, whose backend memory is host memory), and window attention
-// at shift 0 without a table and the row softmax pair of the shared-launch route, which the host simulation has in no other form.  The same definitions and the same refusals as the
+// at shift 0 without a table, which the host simulation has in no other form.  The same definitions and the same refusals as the
 // kernels; the ORDER of the sums is the simplest one (one fma chain in increasing index, a plain running sum over a row) and is NOT
 // the device's, so these are held to the float64 bound, not to the device's bits.  Only expf is the host's own.
 #pragma once
@@ -186,27 +186,3 @@ inline int twins_window_attention_bwd(const float* qkv, const float* dout, int F
     return 0;
 }
 
-inline int twins_softmax(float* X, int64_t rows, int N, int ld, hipStream_t) {
-    if (ld % 4 != 0 || ld < N || ((uintptr_t)X & 15)) return twins_host_refuse("twins_softmax", "rows must be 16-byte aligned (ld % 4 == 0, ld >= N)");
-    for (int64_t r = 0; r < rows; ++r) {
-        float* x = X + r * ld;
-        float m = -INFINITY, sum = 0.f;
-        for (int j = 0; j < N; ++j) m = fmaxf(m, x[j]);
-        for (int j = 0; j < N; ++j) { x[j] = expf(x[j] - m); sum = sum + x[j]; }
-        for (int j = 0; j < N; ++j) x[j] = x[j] / sum;
-    }
-    return 0;
-}
-
-inline int twins_softmax_bwd(float* dX, const float* P, int64_t rows, int N, int ld, float scale, hipStream_t) {
-    if (ld % 4 != 0 || ld < N || (((uintptr_t)dX | (uintptr_t)P) & 15))
-        return twins_host_refuse("twins_softmax_bwd", "rows must be 16-byte aligned (ld % 4 == 0, ld >= N)");
-    for (int64_t r = 0; r < rows; ++r) {
-        float* d = dX + r * ld;
-        const float* p = P + r * ld;
-        float sum = 0.f;
-        for (int j = 0; j < N; ++j) sum = sum + d[j] * p[j];
-        for (int j = 0; j < N; ++j) d[j] = scale * (p[j] * (d[j] - sum));
-    }
-    return 0;
-}

@@ -40,12 +40,6 @@ int twins_window_attention(const float* qkv, int F, int H, int W, int ws, int he
 int twins_window_attention_bwd(const float* qkv, const float* dout, int F, int H, int W, int ws, int heads, int dh, const float* zero_table,
                                float* dqkv, hipStream_t s);
 
-// The row softmax pair of the shared-launch route of the planner (I2V_TWINS_ATTN=0) on X (rows, ld), the first N of each row:
-//   forward   X = softmax(X) in place        backward  dX = scale P (dX - rowsum(dX P)) in place
-// On the device these are vit_softmax / vit_softmax_bwd (ld % 4 == 0, 16-byte alignment); the host simulation has no other form of them.
-int twins_softmax(float* X, int64_t rows, int N, int ld, hipStream_t s);
-int twins_softmax_bwd(float* dX, const float* P, int64_t rows, int N, int ld, float scale, hipStream_t s);
-
 // What both forms of the launches refuse, with the text.  Returns the message or null.
 inline const char* twins_attn_refusal(const TwinsAttn& p, bool bwd) {
     const int64_t C = (int64_t)p.H * p.dh;

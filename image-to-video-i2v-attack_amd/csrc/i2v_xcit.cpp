@@ -50,6 +50,8 @@ struct i2v_xcit : XfNet {
     std::vector<XcBlock> blocks;
 
     float* stream_after(int b) { return b + 1 < nb ? blocks[b + 1].x : x_top; }
+    float* hook_stream(int b) { return stream_after(b); }
+    int64_t hook_floats(int) const { return (int64_t)T * cfg.dim; }
     XcitAttn attn(const XcBlock& B, int frames) const {
         XcitAttn a{};
         a.qkv = B.qkv; a.F = frames; a.T = T; a.H = cfg.heads; a.dh = cfg.dim / cfg.heads; a.temperature = B.temp; a.gram = B.gram; a.probs = B.P;
@@ -145,32 +147,10 @@ int xcit_plan(i2v_xcit* n, const float* const* w, int nw, const int32_t* hooks, 
     return 0;
 }
 
-}  // namespace
-
-extern "C" int i2v_xcit_create(int device, const i2v_xcit_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_blocks,
-                               int n_hooks, int max_frames, i2v_xcit_handle* out) {
-    if (!cfg || !weights || !hook_blocks || !out) return fail("i2v_xcit_create: null argument");
-    return create_net("i2v_xcit_create", "block", device, max_frames, out, [&](i2v_xcit* n) {
-        n->cfg = *cfg;
-        return xcit_plan(n, weights, n_weights, hook_blocks, n_hooks);
-    });
-}
-
-extern "C" int i2v_xcit_destroy(i2v_xcit_handle net) {
-    delete net;
-    return 0;
-}
-
-extern "C" int64_t i2v_xcit_workspace_bytes(i2v_xcit_handle net) { return net ? net->arena.bytes : -1; }
-
-extern "C" int i2v_xcit_forward(i2v_xcit_handle n, const float* x, int frames, void* stream) {
-    if (!n || !x) return fail("i2v_xcit_forward: null argument");
-    if (frames <= 0 || frames > n->max_frames) return fail("i2v_xcit_forward: %d frames, the net is planned for 1..%d", frames, n->max_frames);
-    hipStream_t s = (hipStream_t)stream;
+int xcit_forward(i2v_xcit* n, const float* x, int frames, hipStream_t s) {
     const i2v_xcit_config& c = n->cfg;
     const int D = c.dim, M = frames * n->T;
     const int64_t FT = (int64_t)frames * n->T, sp = (int64_t)n->max_frames * n->T;
-    n->frames = frames;
     const float* src = x;
     for (int k = 0; k < 4; ++k) {                                        // the stem: gather, Linear with the folded BN (+ GELU)
         const int P = n->side[k + 1], rowsM = frames * P * P, K = 9 * n->cs[k];
@@ -203,17 +183,14 @@ extern "C" int i2v_xcit_forward(i2v_xcit_handle n, const float* x, int frames, v
     return 0;
 }
 
-extern "C" int i2v_xcit_backward(i2v_xcit_handle n, float* gx, int accumulate, void* stream) {
-    if (!n || !gx) return fail("i2v_xcit_backward: null argument");
-    if (n->frames <= 0) return fail("i2v_xcit_backward: no forward pass to differentiate");
-    hipStream_t s = (hipStream_t)stream;
+int xcit_backward(i2v_xcit* n, float* gx, int accumulate, hipStream_t s) {
     const i2v_xcit_config& c = n->cfg;
     const int frames = n->frames, D = c.dim, M = frames * n->T;
     const int64_t FT = (int64_t)frames * n->T, sp = (int64_t)n->max_frames * n->T;
     for (int b = n->nb - 1; b >= 0; --b) {
         // gradient of the stream after block b: the top hook's view for the deepest block, the running gradient G below it (where the LN1
         // backward of block b + 1 has already added the hook at that stream)
-        const float* gin = b == n->nb - 1 ? n->hooks.grad_at(b) : n->G;
+        const float* gin = n->grad_in(b, n->nb);
         const XcBlock& B = n->blocks[b];
         const float* st = B.stats;
         VCHK(linear_bwd(gin, M, D, B.fc2w, c.mlp, B.h, n->t2, s));                               // dh = (g fc2') * gelu'(h)
@@ -229,7 +206,7 @@ extern "C" int i2v_xcit_backward(i2v_xcit_handle n, float* gx, int accumulate, v
         a.dout = n->t1; a.dqkv = n->dqkv;
         VCHK(xcit_attention_bwd(a, s));
         VCHK(linear_bwd(n->dqkv, M, 3 * D, B.qkvw, D, nullptr, n->t1, s));                       // d LN1 out
-        VCHK(vit_layernorm_bwd(n->t1, B.x, st, st + sp, B.n1w, FT, D, n->G, b > 0 ? n->hooks.grad_at(b - 1) : nullptr, n->G, s));   // G = dx (+ hook)
+        VCHK(vit_layernorm_bwd(n->t1, B.x, st, st + sp, B.n1w, FT, D, n->G, n->grad_below(b), n->G, s));   // G = dx (+ hook)
     }
     // the position table is an addend: the stem's output gradient is the stream's
     const float* g = n->G;
@@ -246,15 +223,34 @@ extern "C" int i2v_xcit_backward(i2v_xcit_handle n, float* gx, int accumulate, v
     return 0;
 }
 
+}  // namespace
+
+extern "C" int i2v_xcit_create(int device, const i2v_xcit_config* cfg, const float* const* weights, int n_weights, const int32_t* hook_blocks,
+                               int n_hooks, int max_frames, i2v_xcit_handle* out) {
+    return xf_create("i2v_xcit_create", "block", device, cfg, weights, hook_blocks, max_frames, out, [&](i2v_xcit* n) {
+        n->cfg = *cfg;
+        return xcit_plan(n, weights, n_weights, hook_blocks, n_hooks);
+    });
+}
+
+extern "C" int i2v_xcit_destroy(i2v_xcit_handle net) { return xf_destroy(net); }
+
+extern "C" int64_t i2v_xcit_workspace_bytes(i2v_xcit_handle net) { return xf_workspace_bytes(net); }
+
+extern "C" int i2v_xcit_forward(i2v_xcit_handle n, const float* x, int frames, void* stream) {
+    return xf_forward("i2v_xcit_forward", n, x, frames, stream, xcit_forward);
+}
+
+extern "C" int i2v_xcit_backward(i2v_xcit_handle n, float* gx, int accumulate, void* stream) {
+    return xf_backward("i2v_xcit_backward", n, gx, accumulate, stream, xcit_backward);
+}
+
 extern "C" int i2v_xcit_hook_info(i2v_xcit_handle n, int hook, float** act, int64_t* act_stride, float** grad, int64_t* grad_stride, int64_t* D) {
-    if (!n || !n->hooks.has(hook)) return fail("i2v_xcit_hook_info: no hook %d", hook);
-    return hook_info(n->stream_after(n->hooks.at[hook]), n->hooks.grad[hook], (int64_t)n->T * n->cfg.dim, act, act_stride, grad, grad_stride, D);
+    return xf_hook_info("i2v_xcit_hook_info", n, hook, act, act_stride, grad, grad_stride, D);
 }
 
 extern "C" int i2v_xcit_read_hook(i2v_xcit_handle n, int hook, int which, float* out, int frames, void* stream) {
-    if (!n || !out || !n->hooks.has(hook)) return fail("i2v_xcit_read_hook: no hook %d", hook);
-    return read_hook("i2v_xcit_read_hook", which ? n->hooks.grad[hook] : n->stream_after(n->hooks.at[hook]), (int64_t)n->T * n->cfg.dim, out,
-                     frames, n->max_frames, stream);
+    return xf_read_hook("i2v_xcit_read_hook", n, hook, which, out, frames, stream);
 }
 
 // ---- the kernels on their own ----

@@ -1,7 +1,7 @@
 // The shared transformer launches on their own (include/i2v_xf_launch.h): thin C entries over vit_gemm, the LayerNorm pair, vit_patchify
 // and the softmax pair, for tests and tools.  i2v_xf.h picks the kernels (i2v_vit.hip) or, where there is no HIP, their scalar
 // restatements (i2v_xf_host.h), so this unit is part of the library and of the host simulation's one-file build alike; the softmax
-// pair has no host form and is compiled for the device only.
+// pair's entries are the device library's only.
 #include "../../include/i2v_xf_launch.h"
 #include "i2v_xf.h"
 

@@ -1,10 +1,10 @@
 // What the transformer planners need where there is no HIP (the host simulation's one-file build, g++): a stand-in for the few runtime
-// calls of i2v_xf.h on host memory, and the shared launches the ConvNeXt planner uses -- vit_gemm, the LayerNorm pair, vit_patchify and
-// the 2 x 2 gather / scatter -- as plain scalar C++, in the style of i2v_se_host.h and i2v_convnext_host.h.  The same definitions as the
+// calls of i2v_xf.h on host memory, and the shared launches the planners use -- vit_gemm, the LayerNorm pair, the row softmax pair,
+// vit_patchify, vit_assemble and the 2 x 2 gather / scatter -- as plain scalar C++, in the style of i2v_se_host.h and i2v_convnext_host.h.  The same definitions as the
 // kernels (i2v_vit_kernels.h, i2v_swin_kernels.h); the ORDER of their sums is a simple one (one fma chain in increasing k; a row's
 // channels as 64 interleaved partial sums and a pairwise tree over them, xf_host_rowsum) and is NOT the device's, so these are held to
-// the float64 bound, not to the device's bits.
-// Window attention, softmax and the prefix rows have no host form: ViT and Swin stay device-only.
+// the float64 bound, not to the device's bits.  The softmax pair is one running sum over a row; only expf is the host's own.
+// Window attention has no host form, and the ViT and Swin planners are not part of the one-file build: they stay device-only.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -113,6 +113,47 @@ inline int vit_patchify(const float* img, float* patches, int F, int Cin, int gh
                             if (!gimg) patches[pi] = img[ii];
                             else gimg[ii] = accumulate ? gimg[ii] + patches[pi] : patches[pi];
                         }
+    return 0;
+}
+
+// X (rows, ld) = softmax over the first N of each row, in place
+inline int vit_softmax(float* X, int64_t rows, int N, int ld, hipStream_t) {
+    if (ld % 4 != 0 || ld < N || ((uintptr_t)X & 15)) return i2v_api_fail("vit_softmax: rows must be 16-byte aligned (ld % 4 == 0, ld >= N)");
+    for (int64_t r = 0; r < rows; ++r) {
+        float* x = X + r * ld;
+        float m = -INFINITY, sum = 0.f;
+        for (int j = 0; j < N; ++j) m = fmaxf(m, x[j]);
+        for (int j = 0; j < N; ++j) { x[j] = expf(x[j] - m); sum = sum + x[j]; }
+        for (int j = 0; j < N; ++j) x[j] = x[j] / sum;
+    }
+    return 0;
+}
+
+// dX = scale P (dX - rowsum(dX P)) in place
+inline int vit_softmax_bwd(float* dX, const float* P, int64_t rows, int N, int ld, float scale, hipStream_t) {
+    if (ld % 4 != 0 || ld < N || (((uintptr_t)dX | (uintptr_t)P) & 15))
+        return i2v_api_fail("vit_softmax_bwd: rows must be 16-byte aligned (ld % 4 == 0, ld >= N)");
+    for (int64_t r = 0; r < rows; ++r) {
+        float* d = dX + r * ld;
+        const float* p = P + r * ld;
+        float sum = 0.f;
+        for (int j = 0; j < N; ++j) sum = sum + d[j] * p[j];
+        for (int j = 0; j < N; ++j) d[j] = scale * (p[j] * (d[j] - sum));
+    }
+    return 0;
+}
+
+// x (F, T, C) = [prefix (n_prefix, C); E (F, T - n_prefix, C)] + pos (T, C)
+inline int vit_assemble(const float* E, const float* prefix, int n_prefix, const float* pos, float* x, int F, int T, int C, hipStream_t) {
+    if (!E || !prefix || !pos || !x) return i2v_api_fail("vit_assemble: null argument");
+    if (n_prefix < 1 || n_prefix >= T) return i2v_api_fail("vit_assemble: the prefix tokens must leave at least one patch row");
+    const int np = T - n_prefix;
+    for (int64_t f = 0; f < F; ++f)
+        for (int t = 0; t < T; ++t)
+            for (int c = 0; c < C; ++c) {
+                const float v = t < n_prefix ? prefix[(int64_t)t * C + c] : E[(f * np + t - n_prefix) * C + c];
+                x[(f * T + t) * C + c] = v + pos[(int64_t)t * C + c];
+            }
     return 0;
 }
 

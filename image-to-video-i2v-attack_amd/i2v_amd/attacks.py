@@ -113,26 +113,10 @@ class _ImageGuided(Attack):
             g = self._builder(m, hw)
             sd = _weights.load_state_dict(g, self._wseed)
             hooks = [g.hook_for(d, whole) for d in ds]
-            if isinstance(g, _graphs.VitSpec):          # the transformer surrogate: a planned block stack of its own
-                nets.append(self.engine.build_vit_net(g, sd, hooks, frames))
-            elif isinstance(g, _graphs.SwinSpec):       # the windowed transformer: stages, hooked before their patch merging
-                nets.append(self.engine.build_swin_net(g, sd, hooks, frames))
-            elif isinstance(g, _graphs.ConvNextSpec):   # ConvNeXt on the transformer stack: stages, hooked before the next downsample
-                nets.append(self.engine.build_convnext_net(g, sd, hooks, frames))
-            elif isinstance(g, _graphs.MixerSpec):      # MLP-Mixer / ResMLP on the transformer stack: blocks, hooked as ViT's
-                nets.append(self.engine.build_mixer_net(g, sd, hooks, frames))
-            elif isinstance(g, _graphs.CaitSpec):       # CaiT on the transformer stack: self-attention blocks, hooked as ViT's
-                nets.append(self.engine.build_cait_net(g, sd, hooks, frames))
-            elif isinstance(g, _graphs.ConvitSpec):     # ConViT on the transformer stack: blocks, hooked as ViT's; 197 tokens behind the join
-                nets.append(self.engine.build_convit_net(g, sd, hooks, frames))
-            elif isinstance(g, _graphs.XcitSpec):       # XCiT on the transformer stack: cross-covariance blocks, hooked as ViT's
-                nets.append(self.engine.build_xcit_net(g, sd, hooks, frames))
-            elif isinstance(g, _graphs.TwinsSpec):      # Twins on the transformer stack: stages, hooked as Swin's
-                nets.append(self.engine.build_twins_net(g, sd, hooks, frames))
-            elif isinstance(g, _graphs.BeitSpec):       # BEiT on the transformer stack: biased global attention, hooked as ViT's
-                nets.append(self.engine.build_beit_net(g, sd, hooks, frames))
-            else:
+            if isinstance(g, _graphs.Graph):
                 nets.append(self.engine.build_net(g, sd, hooks, frames))
+            else:                                   # a transformer surrogate: a planned block / stage stack of its family's own
+                nets.append(self.engine.build_token_net(g, sd, hooks, frames))
         self._nets, self._net_key, self._max_frames = nets, key, frames
         return nets
 

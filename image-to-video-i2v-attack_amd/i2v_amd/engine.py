@@ -87,17 +87,19 @@ class Engine:
     def build_net(self, graph: Graph, state_dict, hook_tensors: Sequence[int], max_frames: int, relu_gain=None) -> "Net":
         return self._build(Net, graph, state_dict, list(hook_tensors), max_frames, relu_gain)
 
+    def build_token_net(self, spec, state_dict, hooks: Sequence[int], max_frames: int) -> "TokenNet":
+        """A transformer surrogate of whichever family `spec` belongs to (`TOKEN_FAMILIES`; `include/i2v_<family>.h`): weights packed
+        and uploaded and the arena planned for up to `max_frames` frames.  The `build_<family>_net` methods are this call."""
+        return self._build(TOKEN_FAMILIES[type(spec)][0], spec, state_dict, list(hooks), max_frames)
+
     def build_vit_net(self, spec: VitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "VitNet":
-        """The ViT surrogate (`include/i2v_vit.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        return self._build(VitNet, spec, state_dict, list(hook_blocks), max_frames)
+        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def build_swin_net(self, spec: SwinSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "SwinNet":
-        """A Swin surrogate (`include/i2v_swin.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        return self._build(SwinNet, spec, state_dict, list(hook_stages), max_frames)
+        return self.build_token_net(spec, state_dict, hook_stages, max_frames)
 
     def build_convnext_net(self, spec: ConvNextSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "ConvNextNet":
-        """A ConvNeXt surrogate (`include/i2v_convnext.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        return self._build(ConvNextNet, spec, state_dict, list(hook_stages), max_frames)
+        return self.build_token_net(spec, state_dict, hook_stages, max_frames)
 
     def convnext_dw(self, x: torch.Tensor, filt: torch.Tensor, bias=None, add=None) -> torch.Tensor:
         """The ConvNeXt block's depthwise 7 x 7 launch on its own (`i2v_convnext_dw_f32`): x (frames, H, W, C) token-major, filt (49, C),
@@ -111,8 +113,7 @@ class Engine:
         return y
 
     def build_mixer_net(self, spec: MixerSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "MixerNet":
-        """An MLP-Mixer / ResMLP surrogate (`include/i2v_mixer.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        return self._build(MixerNet, spec, state_dict, list(hook_blocks), max_frames)
+        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def mixer_tokens(self, z: torch.Tensor, residual: torch.Tensor, w1, b1, w2=None, b2=None, in_scale=None, in_shift=None, out_scale=None,
                      channel_tile: int = 0) -> torch.Tensor:
@@ -145,8 +146,7 @@ class Engine:
         return dz
 
     def build_cait_net(self, spec: CaitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "CaitNet":
-        """A CaiT surrogate (`include/i2v_cait.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        return self._build(CaitNet, spec, state_dict, list(hook_blocks), max_frames)
+        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def cait_attention(self, qkv: torch.Tensor, heads: int, scale: float, wl, bl, ww, bw):
         """Talking-heads attention on its own (`i2v_cait_attention_f32`): qkv (frames, T, 3 heads dh) as the ViT entry takes it, wl / ww
@@ -174,8 +174,7 @@ class Engine:
         return dqkv
 
     def build_convit_net(self, spec: ConvitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "ConvitNet":
-        """A ConViT surrogate (`include/i2v_convit.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        return self._build(ConvitNet, spec, state_dict, list(hook_blocks), max_frames)
+        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def convit_attention(self, qkv: torch.Tensor, heads: int, scale: float, c=None, table=None):
         """Gated positional attention on its own (`i2v_convit_attention_f32`): qkv (frames, T, 3 heads dh) as the ViT entry takes it, c
@@ -206,8 +205,7 @@ class Engine:
         return dqkv
 
     def build_xcit_net(self, spec: XcitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "XcitNet":
-        """An XCiT surrogate (`include/i2v_xcit.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        return self._build(XcitNet, spec, state_dict, list(hook_blocks), max_frames)
+        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def xcit_attention(self, qkv: torch.Tensor, heads: int, temperature: torch.Tensor):
         """Cross-covariance attention on its own (`i2v_xcit_attention_f32`): qkv (frames, T, 3 heads dh) as the ViT entry takes it,
@@ -261,8 +259,7 @@ class Engine:
         return dst
 
     def build_twins_net(self, spec: TwinsSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "TwinsNet":
-        """A Twins surrogate (`include/i2v_twins.h`): weights uploaded and the arena planned for up to `max_frames` frames."""
-        return self._build(TwinsNet, spec, state_dict, list(hook_stages), max_frames)
+        return self.build_token_net(spec, state_dict, hook_stages, max_frames)
 
     def twins_attention(self, q: torch.Tensor, kv: torch.Tensor, heads: int, scale: float = None) -> torch.Tensor:
         """Sub-sampled attention on its own (`i2v_twins_attention_f32`): q (frames, Tq, heads dh), kv (frames, Tk, 2 heads dh) ->
@@ -317,8 +314,7 @@ class Engine:
         return dqkv
 
     def build_beit_net(self, spec: BeitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "BeitNet":
-        """A BEiT surrogate (`include/i2v_beit.h`): weights packed and uploaded and the arena planned for up to `max_frames` frames."""
-        return self._build(BeitNet, spec, state_dict, list(hook_blocks), max_frames)
+        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def beit_attention(self, qkv: torch.Tensor, bias, heads: int, scale: float = None) -> torch.Tensor:
         """Biased global attention on its own (`i2v_beit_attention_f32`): qkv (frames, T, 3 heads dh), bias (heads, T, T) or None ->
@@ -847,8 +843,8 @@ class Net:
 class TokenNet(Net):
     """A transformer surrogate behind the `Net` interface the attack loop uses (`forward`, `backward`, `save_hook`, `cossim`, `stdloss`,
     `scratch_bytes`, `hooks`): a hook is a residual stream of `hook_shape(i)[0]` tokens, `hook_shape(i)[1]` wide; the loss kernels are
-    the ones every backbone uses.  A family sets `_api` (its C entries are `i2v_<_api>_*`), packs its weights and calls its create entry
-    in `_create(spec, sd, hooks, max_frames)`, and gives `hook_shape(i)`."""
+    the ones every backbone uses.  A family is a row of `TOKEN_FAMILIES`: its subclass sets `_api` (its C entries are `i2v_<_api>_*`),
+    its config builder makes the ctypes config from the spec; the weights come packed from `spec.native_arrays(sd, depth)`."""
     _api = None
 
     def __init__(self, eng: Engine, spec, sd, hooks: List[int], max_frames: int):
@@ -867,6 +863,32 @@ class TokenNet(Net):
 
     def _c(self, name):
         return getattr(self.eng.capi, f"i2v_{self._api}_{name}")
+
+    def _weights(self, spec, sd, depth):
+        """The host arrays in the family's native order (`include/i2v_<_api>.h`), for blocks / stages 0 .. depth - 1."""
+        return spec.native_arrays(sd, depth)
+
+    def _create(self, spec, sd, hooks, max_frames, *extra):
+        """`extra`: arguments of the create entry between the config and the weight pointers (ViT's prefix count)."""
+        _, config, units = TOKEN_FAMILIES[type(spec)]
+        depth = min(max(hooks) + 1, units(spec))       # (a hook outside the blocks / stages is the library's to refuse)
+        w = self._weights(spec, sd, depth)              # kept alive until the upload in the create entry
+        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
+        cfg = config(spec)
+        hk = (C.c_int32 * len(hooks))(*hooks)
+        h = C.c_void_p()
+        _lib.check(self.eng.capi, self._c("create" + ("_ex" if extra else ""))(self.eng.device.index or 0, C.byref(cfg), *extra, ptrs, len(w),
+                                                                              hk, len(hooks), max_frames, C.byref(h)))
+        return h
+
+    def hook_shape(self, i):
+        """(tokens, width, 1) of hook i: per block behind ConViT's join, per stage of a staged family, else the spec's own."""
+        spec, where = self.graph, self.hook_tensors[i]
+        if hasattr(spec, "tokens_at"):
+            return (spec.tokens_at(where), spec.dim, 1)
+        if callable(spec.tokens):
+            return (spec.tokens(where), spec.width(where), 1)
+        return (spec.tokens, spec.dim, 1)
 
     def close(self):
         if getattr(self, "h", None) and self.eng.h:
@@ -902,26 +924,16 @@ class VitNet(TokenNet):
     """The ViT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame."""
     _api = "vit"
 
-    def _create(self, spec: VitSpec, sd, hook_blocks, max_frames):
-        eng, capi = self.eng, self.eng.capi
-        nb = max(hook_blocks) + 1
-        keys = [k for i in range(nb) for k in spec.block_keys(i)]
+    def _weights(self, spec: VitSpec, sd, nb):
         # native order: patch weight, patch bias, the prefix tokens as one (n_prefix, dim) array (cls_token, then dist_token), pos_embed,
-        # then the blocks; kept alive until the upload in i2v_vit_create_ex
+        # then the blocks
         prefix = torch.cat([sd[k].detach().float().cpu().reshape(1, spec.dim) for k in spec.prefix_keys], 0)
         w = [sd[k].detach().float().cpu().contiguous() for k in ("patch_embed.proj.weight", "patch_embed.proj.bias")]
         w += [prefix.contiguous(), sd["pos_embed"].detach().float().cpu().contiguous()]
-        w += [sd[k].detach().float().cpu().contiguous() for k in keys]
-        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        cfg = _lib.VitConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.ln_eps)
-        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
-        h = C.c_void_p()
-        _lib.check(capi, capi.i2v_vit_create_ex(eng.device.index or 0, C.byref(cfg), spec.n_prefix, ptrs, len(w), hb, len(hook_blocks),
-                                                max_frames, C.byref(h)))
-        return h
+        return w + [sd[k].detach().float().cpu().contiguous() for i in range(nb) for k in spec.block_keys(i)]
 
-    def hook_shape(self, i):
-        return (self.graph.tokens, self.graph.dim, 1)
+    def _create(self, spec: VitSpec, sd, hook_blocks, max_frames):
+        return super()._create(spec, sd, hook_blocks, max_frames, spec.n_prefix)      # i2v_vit_create_ex
 
 
 class SwinNet(TokenNet):
@@ -929,179 +941,84 @@ class SwinNet(TokenNet):
     per frame."""
     _api = "swin"
 
-    def _create(self, spec: SwinSpec, sd, hook_stages, max_frames):
-        eng, capi = self.eng, self.eng.capi
-        ns = max(hook_stages) + 1
-        # native order (include/i2v_swin.h): the embedding, then per stage its blocks and the merging behind it; kept alive until the upload
-        w = [sd[k].detach().float().cpu().contiguous() for k in spec.native_keys(ns)]
-        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        pad = lambda v: (C.c_int32 * 4)(*(list(v) + [0] * (4 - len(v))))
-        cfg = _lib.SwinConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.window, spec.stages, pad(spec.depths), pad(spec.heads),
-                              spec.ln_eps)
-        hs = (C.c_int32 * len(hook_stages))(*hook_stages)
-        h = C.c_void_p()
-        _lib.check(capi, capi.i2v_swin_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hs, len(hook_stages), max_frames, C.byref(h)))
-        return h
-
-    def hook_shape(self, i):
-        st = self.hook_tensors[i]
-        return (self.graph.tokens(st), self.graph.width(st), 1)
+    def _weights(self, spec: SwinSpec, sd, ns):
+        # native order (include/i2v_swin.h): the embedding, then per stage its blocks and the merging behind it
+        return [sd[k].detach().float().cpu().contiguous() for k in spec.native_keys(ns)]
 
 
 class ConvNextNet(TokenNet):
     """A ConvNeXt surrogate: a hook is the stream after the last block of a stage, before the next stage's downsample, (plane^2 * width)
-    floats per frame, token-major."""
+    floats per frame, token-major.  Packed with the filters transposed, downsamples as Linears, gamma folded into fc2."""
     _api = "convnext"
-
-    def _create(self, spec: ConvNextSpec, sd, hook_stages, max_frames):
-        eng, capi = self.eng, self.eng.capi
-        ns = min(max(hook_stages) + 1, spec.stages)      # (a hook outside the stages is the library's to refuse)
-        # native order (include/i2v_convnext.h): filters transposed, downsamples as Linears, gamma folded into fc2; kept alive until the upload
-        w = spec.native_arrays(sd, ns)
-        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        pad = lambda v: (C.c_int32 * 4)(*(list(v) + [0] * (4 - len(v))))      # noqa: E731
-        cfg = _lib.ConvNextConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.stages, pad(spec.depths), spec.ln_eps)
-        hs = (C.c_int32 * len(hook_stages))(*hook_stages)
-        h = C.c_void_p()
-        _lib.check(capi, capi.i2v_convnext_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hs, len(hook_stages), max_frames,
-                                                  C.byref(h)))
-        return h
-
-    def hook_shape(self, i):
-        st = self.hook_tensors[i]
-        return (self.graph.tokens(st), self.graph.width(st), 1)
 
 
 class MixerNet(TokenNet):
-    """An MLP-Mixer / ResMLP surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame."""
+    """An MLP-Mixer / ResMLP surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame.  ResMLP is
+    packed with its folds made."""
     _api = "mixer"
-
-    def _create(self, spec: MixerSpec, sd, hook_blocks, max_frames):
-        eng, capi = self.eng, self.eng.capi
-        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
-        # native order (include/i2v_mixer.h): the stem, then the blocks; ResMLP with its folds made; kept alive until the upload
-        w = spec.native_arrays(sd, nb)
-        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        cfg = _lib.MixerConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.blocks, spec.tokens_hidden, spec.mlp,
-                               1 if spec.kind == "resmlp" else 0, spec.ln_eps)
-        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
-        h = C.c_void_p()
-        _lib.check(capi, capi.i2v_mixer_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames,
-                                               C.byref(h)))
-        return h
-
-    def hook_shape(self, i):
-        return (self.graph.tokens, self.graph.dim, 1)
 
 
 class CaitNet(TokenNet):
-    """A CaiT surrogate: a hook is the residual stream after one self-attention block, (tokens * dim) floats per frame."""
+    """A CaiT surrogate: a hook is the residual stream after one self-attention block, (tokens * dim) floats per frame.  Packed with
+    gamma_1 / gamma_2 folded."""
     _api = "cait"
-
-    def _create(self, spec: CaitSpec, sd, hook_blocks, max_frames):
-        eng, capi = self.eng, self.eng.capi
-        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
-        # native order (include/i2v_cait.h): the stem, pos_embed, then the blocks with gamma_1 / gamma_2 folded; kept alive until the upload
-        w = spec.native_arrays(sd, nb)
-        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        cfg = _lib.CaitConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.ln_eps)
-        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
-        h = C.c_void_p()
-        _lib.check(capi, capi.i2v_cait_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames,
-                                              C.byref(h)))
-        return h
-
-    def hook_shape(self, i):
-        return (self.graph.tokens, self.graph.dim, 1)
 
 
 class ConvitNet(TokenNet):
     """A ConViT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame before the class token joins
-    and ((tokens + 1) * dim) behind it."""
+    and ((tokens + 1) * dim) behind it.  Packed with qk and v stacked, the gate folded into one table and one vector per GPSA block."""
     _api = "convit"
-
-    def _create(self, spec: ConvitSpec, sd, hook_blocks, max_frames):
-        eng, capi = self.eng, self.eng.capi
-        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
-        # native order (include/i2v_convit.h): the stem, pos_embed, cls_token, then the blocks -- qk and v stacked, the gate folded into
-        # one table and one vector per GPSA block; kept alive until the upload
-        w = spec.native_arrays(sd, nb)
-        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        cfg = _lib.ConvitConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.local_blocks, spec.ln_eps)
-        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
-        h = C.c_void_p()
-        _lib.check(capi, capi.i2v_convit_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames,
-                                                C.byref(h)))
-        return h
-
-    def hook_shape(self, i):
-        return (self.graph.tokens_at(self.hook_tensors[i]), self.graph.dim, 1)
 
 
 class XcitNet(TokenNet):
-    """An XCiT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame."""
+    """An XCiT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame.  Packed with the BatchNorm
+    folded into the stem and the three LayerScales folded, 21 arrays per block."""
     _api = "xcit"
-
-    def _create(self, spec: XcitSpec, sd, hook_blocks, max_frames):
-        eng, capi = self.eng, self.eng.capi
-        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
-        # native order (include/i2v_xcit.h): the BatchNorm-folded stem, the position table, then 21 arrays per block with the three
-        # LayerScales folded; kept alive until the upload
-        w = spec.native_arrays(sd, nb)
-        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        cfg = _lib.XcitConfig(spec.img, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.ln_eps)
-        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
-        h = C.c_void_p()
-        _lib.check(capi, capi.i2v_xcit_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames, C.byref(h)))
-        return h
-
-    def hook_shape(self, i):
-        return (self.graph.tokens, self.graph.dim, 1)
 
 
 class TwinsNet(TokenNet):
     """A Twins surrogate: a hook is the stream after the last block of a stage, before the next patch embedding, (grid^2 * width) floats
-    per frame."""
+    per frame.  Packed with the sr convolution in the block gather's column order and the position encoding's filter as (9, dim)."""
     _api = "twins"
-
-    def _create(self, spec: TwinsSpec, sd, hook_stages, max_frames):
-        eng, capi = self.eng, self.eng.capi
-        ns = min(max(hook_stages) + 1, spec.stages)      # (a hook outside the stages is the library's to refuse)
-        # native order (include/i2v_twins.h): per stage the embedding, the blocks with the sr convolution repacked to the block gather's
-        # column order, and the position encoding's filter as (9, dim) behind block 0; kept alive until the upload
-        w = spec.native_arrays(sd, ns)
-        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        four = lambda v: (C.c_int32 * 4)(*v)      # noqa: E731
-        dims, heads, mlp, depths, sr = spec.config_lists()
-        cfg = _lib.TwinsConfig(spec.img, spec.in_chans, spec.patch, spec.stages, spec.window, four(dims), four(heads), four(mlp), four(depths),
-                               four(sr), spec.ln_eps, spec.pe_eps)
-        hs = (C.c_int32 * len(hook_stages))(*hook_stages)
-        h = C.c_void_p()
-        _lib.check(capi, capi.i2v_twins_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hs, len(hook_stages), max_frames, C.byref(h)))
-        return h
-
-    def hook_shape(self, i):
-        st = self.hook_tensors[i]
-        return (self.graph.tokens(st), self.graph.width(st), 1)
 
 
 class BeitNet(TokenNet):
     """A BEiT surrogate: a hook is the residual stream after one block, all tokens with the class token, (tokens * dim) floats per
-    frame."""
+    frame.  Packed with the qkv bias built, LayerScale folded and the position bias dense, 13 arrays per block."""
     _api = "beit"
 
-    def _create(self, spec: BeitSpec, sd, hook_blocks, max_frames):
-        eng, capi = self.eng, self.eng.capi
-        nb = min(max(hook_blocks) + 1, spec.blocks)      # (a hook outside the blocks is the library's to refuse)
-        # native order (include/i2v_beit.h): the embedding, the class token, then 13 arrays per block with the qkv bias built, LayerScale
-        # folded and the position bias dense; kept alive until the upload
-        w = spec.native_arrays(sd, nb)
-        ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        cfg = _lib.BeitConfig(spec.img, spec.patch, spec.in_chans, spec.dim, spec.heads, spec.mlp, spec.blocks, spec.ln_eps)
-        hb = (C.c_int32 * len(hook_blocks))(*hook_blocks)
-        h = C.c_void_p()
-        _lib.check(capi, capi.i2v_beit_create(eng.device.index or 0, C.byref(cfg), ptrs, len(w), hb, len(hook_blocks), max_frames, C.byref(h)))
-        return h
 
-    def hook_shape(self, i):
-        return (self.graph.tokens, self.graph.dim, 1)
+def _four(v):
+    v = list(v)
+    return (C.c_int32 * 4)(*(v + [0] * (4 - len(v))))
+
+
+def _twins_config(s: TwinsSpec):
+    dims, heads, mlp, depths, sr = s.config_lists()
+    return _lib.TwinsConfig(s.img, s.in_chans, s.patch, s.stages, s.window, _four(dims), _four(heads), _four(mlp), _four(depths), _four(sr),
+                            s.ln_eps, s.pe_eps)
+
+
+def _blocks(s):
+    return s.blocks
+
+
+def _stages(s):
+    return s.stages
+
+
+# spec class -> (net class, ctypes config from the spec, how many blocks / stages the spec has)
+TOKEN_FAMILIES = {
+    VitSpec: (VitNet, lambda s: _lib.VitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
+    SwinSpec: (SwinNet, lambda s: _lib.SwinConfig(s.img, s.patch, s.in_chans, s.dim, s.window, s.stages, _four(s.depths), _four(s.heads),
+                                                  s.ln_eps), _stages),
+    ConvNextSpec: (ConvNextNet, lambda s: _lib.ConvNextConfig(s.img, s.patch, s.in_chans, s.dim, s.stages, _four(s.depths), s.ln_eps), _stages),
+    MixerSpec: (MixerNet, lambda s: _lib.MixerConfig(s.img, s.patch, s.in_chans, s.dim, s.blocks, s.tokens_hidden, s.mlp,
+                                                     1 if s.kind == "resmlp" else 0, s.ln_eps), _blocks),
+    CaitSpec: (CaitNet, lambda s: _lib.CaitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
+    ConvitSpec: (ConvitNet, lambda s: _lib.ConvitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.local_blocks, s.ln_eps),
+                 _blocks),
+    XcitSpec: (XcitNet, lambda s: _lib.XcitConfig(s.img, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
+    TwinsSpec: (TwinsNet, _twins_config, _stages),
+    BeitSpec: (BeitNet, lambda s: _lib.BeitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
+}

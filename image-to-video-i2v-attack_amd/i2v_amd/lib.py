@@ -129,20 +129,28 @@ _LOADER_PROTOS = {
 LOADER_EXPORTS = tuple(_LOADER_PROTOS)
 
 
+def _net_protos(fam, config):
+    """The seven entries every transformer family has (`include/i2v_<fam>.h`): create, destroy, workspace_bytes, forward, backward,
+    hook_info and read_hook, with the family's config struct."""
+    return {
+        f"i2v_{fam}_create": ([_I, C.POINTER(config), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+        f"i2v_{fam}_destroy": ([_P], _I),
+        f"i2v_{fam}_workspace_bytes": ([_P], _L),
+        f"i2v_{fam}_forward": ([_P, _P, _I, _P], _I),
+        f"i2v_{fam}_backward": ([_P, _P, _I, _P], _I),
+        f"i2v_{fam}_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
+        f"i2v_{fam}_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    }
+
+
 class VitConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("img", "patch", "in_chans", "dim", "heads", "mlp", "blocks")] + [("ln_eps", C.c_float)]
 
 
 # The ViT surrogate (`include/i2v_vit.h`): like the loader, a header of its own outside the host simulation's ABI.
 _VIT_PROTOS = {
-    "i2v_vit_create": ([_I, C.POINTER(VitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
+    **_net_protos("vit", VitConfig),
     "i2v_vit_create_ex": ([_I, C.POINTER(VitConfig), _I, C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
-    "i2v_vit_destroy": ([_P], _I),
-    "i2v_vit_workspace_bytes": ([_P], _L),
-    "i2v_vit_forward": ([_P, _P, _I, _P], _I),
-    "i2v_vit_backward": ([_P, _P, _I, _P], _I),
-    "i2v_vit_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
-    "i2v_vit_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
     "i2v_vit_linear_f32": ([_P, _I, _I, _P, _P, _I, _P, _P, _P, _P], _I),
     "i2v_vit_linear_bwd_f32": ([_P, _I, _I, _P, _I, _P, _P, _P], _I),
     "i2v_vit_layernorm_f32": ([_P, _L, _I, _P, _P, _F, _P, _P, _P, _P], _I),
@@ -165,13 +173,7 @@ class SwinConfig(C.Structure):
 
 # The Swin surrogates (`include/i2v_swin.h`): a header of its own as well, bound on the product library only.
 _SWIN_PROTOS = {
-    "i2v_swin_create": ([_I, C.POINTER(SwinConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
-    "i2v_swin_destroy": ([_P], _I),
-    "i2v_swin_workspace_bytes": ([_P], _L),
-    "i2v_swin_forward": ([_P, _P, _I, _P], _I),
-    "i2v_swin_backward": ([_P, _P, _I, _P], _I),
-    "i2v_swin_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
-    "i2v_swin_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    **_net_protos("swin", SwinConfig),
     "i2v_swin_window_attention_f32": ([_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     "i2v_swin_window_attention_bwd_f32": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     "i2v_swin_merge_f32": ([_P, _I, _I, _I, _I, _P, _P], _I),
@@ -189,13 +191,7 @@ class ConvNextConfig(C.Structure):
 # The ConvNeXt surrogates (`include/i2v_convnext.h`): a header of its own, bound on the product library only -- except the depthwise
 # launch on its own, `i2v_convnext_dw_f32`, which the host simulation exports as well (the same operations as scalar host code).
 _CONVNEXT_PROTOS = {
-    "i2v_convnext_create": ([_I, C.POINTER(ConvNextConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
-    "i2v_convnext_destroy": ([_P], _I),
-    "i2v_convnext_workspace_bytes": ([_P], _L),
-    "i2v_convnext_forward": ([_P, _P, _I, _P], _I),
-    "i2v_convnext_backward": ([_P, _P, _I, _P], _I),
-    "i2v_convnext_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
-    "i2v_convnext_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    **_net_protos("convnext", ConvNextConfig),
     "i2v_convnext_dw_f32": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P], _I),
 }
 CONVNEXT_EXPORTS = tuple(_CONVNEXT_PROTOS)
@@ -209,13 +205,7 @@ class MixerConfig(C.Structure):
 # The all-MLP surrogates, MLP-Mixer and ResMLP (`include/i2v_mixer.h`): a header of its own, kept apart from EXPORTS.  The host
 # simulation exports all of it: the planner runs there on scalar restatements, and so does the token-mixing launch on its own.
 _MIXER_PROTOS = {
-    "i2v_mixer_create": ([_I, C.POINTER(MixerConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
-    "i2v_mixer_destroy": ([_P], _I),
-    "i2v_mixer_workspace_bytes": ([_P], _L),
-    "i2v_mixer_forward": ([_P, _P, _I, _P], _I),
-    "i2v_mixer_backward": ([_P, _P, _I, _P], _I),
-    "i2v_mixer_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
-    "i2v_mixer_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    **_net_protos("mixer", MixerConfig),
     "i2v_mixer_tokens_f32": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P], _I),
     "i2v_mixer_tokens_bwd_f32": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P], _I),
 }
@@ -230,13 +220,7 @@ class CaitConfig(C.Structure):
 # The CaiT surrogates (`include/i2v_cait.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it: the
 # planner runs there on scalar restatements, and so do the two talking-heads attention entries on their own.
 _CAIT_PROTOS = {
-    "i2v_cait_create": ([_I, C.POINTER(CaitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
-    "i2v_cait_destroy": ([_P], _I),
-    "i2v_cait_workspace_bytes": ([_P], _L),
-    "i2v_cait_forward": ([_P, _P, _I, _P], _I),
-    "i2v_cait_backward": ([_P, _P, _I, _P], _I),
-    "i2v_cait_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
-    "i2v_cait_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    **_net_protos("cait", CaitConfig),
     "i2v_cait_attention_f32": ([_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P], _I),
     "i2v_cait_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P], _I),
 }
@@ -250,13 +234,7 @@ class ConvitConfig(C.Structure):
 # The ConViT surrogates (`include/i2v_convit.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it:
 # the planner runs there on scalar restatements, and so do the two gated positional attention entries on their own.
 _CONVIT_PROTOS = {
-    "i2v_convit_create": ([_I, C.POINTER(ConvitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
-    "i2v_convit_destroy": ([_P], _I),
-    "i2v_convit_workspace_bytes": ([_P], _L),
-    "i2v_convit_forward": ([_P, _P, _I, _P], _I),
-    "i2v_convit_backward": ([_P, _P, _I, _P], _I),
-    "i2v_convit_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
-    "i2v_convit_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    **_net_protos("convit", ConvitConfig),
     "i2v_convit_attention_f32": ([_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P], _I),
     "i2v_convit_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P], _I),
 }
@@ -271,13 +249,7 @@ class XcitConfig(C.Structure):
 # planner runs there on scalar restatements, and so do the kernel entries on their own -- cross-covariance attention forward and
 # backward, the depthwise 3 x 3 launch, and the stem's gather / scatter pair.
 _XCIT_PROTOS = {
-    "i2v_xcit_create": ([_I, C.POINTER(XcitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
-    "i2v_xcit_destroy": ([_P], _I),
-    "i2v_xcit_workspace_bytes": ([_P], _L),
-    "i2v_xcit_forward": ([_P, _P, _I, _P], _I),
-    "i2v_xcit_backward": ([_P, _P, _I, _P], _I),
-    "i2v_xcit_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
-    "i2v_xcit_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    **_net_protos("xcit", XcitConfig),
     "i2v_xcit_attention_f32": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
     "i2v_xcit_attention_bwd_f32": ([_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P], _I),
     "i2v_xcit_dw3_f32": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
@@ -296,13 +268,7 @@ class TwinsConfig(C.Structure):
 # planner runs there on scalar restatements, and so do the kernel entries on their own -- sub-sampled attention forward and backward,
 # the block gather / scatter pair, and window attention at shift 0 without a table (which the host simulation has in no other form).
 _TWINS_PROTOS = {
-    "i2v_twins_create": ([_I, C.POINTER(TwinsConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
-    "i2v_twins_destroy": ([_P], _I),
-    "i2v_twins_workspace_bytes": ([_P], _L),
-    "i2v_twins_forward": ([_P, _P, _I, _P], _I),
-    "i2v_twins_backward": ([_P, _P, _I, _P], _I),
-    "i2v_twins_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
-    "i2v_twins_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    **_net_protos("twins", TwinsConfig),
     "i2v_twins_attention_f32": ([_P, _P, _I, _I, _I, _I, _I, _F, _P, _P], _I),
     "i2v_twins_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P], _I),
     "i2v_twins_block_gather_f32": ([_P, _P, _I, _I, _I, _I, _I, _P], _I),
@@ -320,13 +286,7 @@ class BeitConfig(C.Structure):
 # The BEiT surrogates (`include/i2v_beit.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it: the
 # planner runs there on scalar restatements, and so do the two attention entries and the bias add on their own.
 _BEIT_PROTOS = {
-    "i2v_beit_create": ([_I, C.POINTER(BeitConfig), C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_P)], _I),
-    "i2v_beit_destroy": ([_P], _I),
-    "i2v_beit_workspace_bytes": ([_P], _L),
-    "i2v_beit_forward": ([_P, _P, _I, _P], _I),
-    "i2v_beit_backward": ([_P, _P, _I, _P], _I),
-    "i2v_beit_hook_info": ([_P, _I, C.POINTER(_P), C.POINTER(_L), C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)], _I),
-    "i2v_beit_read_hook": ([_P, _I, _I, _P, _I, _P], _I),
+    **_net_protos("beit", BeitConfig),
     "i2v_beit_attention_f32": ([_P, _P, _I, _I, _I, _I, _F, _P, _P], _I),
     "i2v_beit_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P], _I),
     "i2v_beit_bias_add_f32": ([_P, _P, _I, _L, _P], _I),
@@ -354,6 +314,11 @@ XF_EXPORTS = tuple(_XF_PROTOS)
 XF_HOST_PROTOS = {k: v for k, v in _XF_PROTOS.items() if "softmax" not in k}
 
 
+# The transformer families by the word in their entry names (`i2v_<word>_*`)
+FAMILY_PROTOS = {"vit": _VIT_PROTOS, "swin": _SWIN_PROTOS, "convnext": _CONVNEXT_PROTOS, "mixer": _MIXER_PROTOS, "cait": _CAIT_PROTOS,
+                 "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS}
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)
@@ -376,17 +341,8 @@ def load():
         lib = bind(C.CDLL(path))
         if lib.i2v_backend() != HIP_BACKEND:
             raise I2VError(f"{path} reports backend {lib.i2v_backend()!r}, expected {HIP_BACKEND!r}")
-        bind(lib, _LOADER_PROTOS)
-        bind(lib, _VIT_PROTOS)
-        bind(lib, _SWIN_PROTOS)
-        bind(lib, _CONVNEXT_PROTOS)
-        bind(lib, _MIXER_PROTOS)
-        bind(lib, _CAIT_PROTOS)
-        bind(lib, _CONVIT_PROTOS)
-        bind(lib, _XCIT_PROTOS)
-        bind(lib, _TWINS_PROTOS)
-        bind(lib, _BEIT_PROTOS)
-        bind(lib, _XF_PROTOS)
+        for protos in (_LOADER_PROTOS, *FAMILY_PROTOS.values(), _XF_PROTOS):
+            bind(lib, protos)
         _lib = lib
     return _lib
 

@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
-"""Developer tool: is a rebuilt engine (csrc/i2v_engine.cpp and its sibling units) the same engine?  Three subcommands.
+"""Developer tool: is a rebuilt engine (csrc/i2v_engine.cpp and its sibling units) the same engine?  Four subcommands.
 
     I2V_AUTOTUNE=0 I2V_LIB=<library> python tools/engine_split_compare.py plan OUT.json
         plans the headline ResNet-101 net (depth 3, 128 frames) and the SlowFast ILAF net (one 32-frame clip), runs one forward +
         backward in timing mode 1 and records workspace_bytes(), fusion_info() and every I2V_TIMING_DUMP line without its ms column
         (kind Cd K HWg frames pw, GFLOP, MB).  I2V_AUTOTUNE=0 makes the plan deterministic.  With a third argument, the path of a
         host-simulation library (tests/hostsim/libi2v_hostsim.so), the same on the CPU with the tiny graphs of the tests.
+    I2V_LIB=<library> python tools/engine_split_compare.py tokens OUT.json
+        the transformer families on their test-size twins (graphs.build_tiny at its smallest frame, synthetic weights of seed 0), ViT, DeiT distilled,
+        Swin, ConvNeXt, Mixer, ResMLP, CaiT, ConViT, XCiT, Twins-PCPVT, Twins-SVT and BEiT, and the I2V_BEIT_ATTN=0 / I2V_TWINS_ATTN=0
+        routes: two steps of the adaptive attack (AENS_I2V_MF) with hooks at the shallowest and the deepest depth on one clip of 3
+        frames, then on its first 2 frames with the same nets (planned for 3), and per run workspace_bytes() and a sha256 of every hook
+        activation, every hook gradient, the input gradient and the adversarial clip.  With a third argument, the path of a
+        host-simulation library, the families that library exports, on the CPU.
     python tools/engine_split_compare.py diff A.json B.json
         the two records must be identical; exit status 1 and the first differences otherwise.
     python tools/engine_split_compare.py npy DIR_A DIR_B
@@ -57,6 +64,66 @@ def plan(out_path, hostsim=None):
     print({k: (v["workspace_bytes"], v["fusion_info"], v["dump_lines"]) for k, v in record.items()})
 
 
+# (record name, model name the twin stands for, the twin's smallest frame side, environment of the run)
+TOKEN_CASES = [("vit", "vit_base_patch16_224", 64, {}), ("deit_distilled", "deit_tiny_distilled_patch16_224", 64, {}),
+               ("swin", "swin_tiny_patch4_window7_224", 64, {}), ("convnext", "convnext_tiny", 64, {}), ("mixer", "mixer_b16_224", 64, {}),
+               ("resmlp", "resmlp_12_224", 64, {}), ("cait", "cait_xxs24_224", 64, {}), ("convit", "convit_tiny", 64, {}),
+               ("xcit", "xcit_nano_12_p16_224", 64, {}), ("twins_pcpvt", "twins_pcpvt_small", 64, {}),
+               ("twins_svt", "twins_svt_small", 128, {}), ("beit", "beit_base_patch16_224", 64, {}),
+               ("twins_pcpvt_attn0", "twins_pcpvt_small", 64, {"I2V_TWINS_ATTN": "0"}),
+               ("twins_svt_attn0", "twins_svt_small", 128, {"I2V_TWINS_ATTN": "0"}),
+               ("beit_attn0", "beit_base_patch16_224", 64, {"I2V_BEIT_ATTN": "0"})]
+
+
+def tokens(out_path, hostsim=None):
+    import hashlib
+    import torch
+    from i2v_amd import attacks, graphs, lib
+    from i2v_amd.engine import Engine
+    families = ("vit", "swin", "convnext", "mixer", "cait", "convit", "xcit", "twins", "beit")      # the word in a family's entry names
+    if hostsim:
+        import ctypes
+        cd = ctypes.CDLL(hostsim)
+        capi = lib.bind(cd)
+        have = [f for f in families if hasattr(cd, f"i2v_{f}_create")]
+        for f in have:
+            lib.bind(capi, getattr(lib, f"_{f.upper()}_PROTOS"))
+        eng = Engine("cpu", capi=capi)
+    else:
+        eng, have = Engine("cuda:0"), families
+
+    def sha(t):
+        return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+    record = {}
+    for name, model, side, env in TOKEN_CASES:
+        vid = torch.randn(1, 3, 3, side, side, generator=torch.Generator().manual_seed(0))
+        spec = graphs.build_tiny(model, (side, side))
+        if type(spec).__name__[:-4].lower() not in have:      # (VitSpec -> "vit": the word in the family's entry names)
+            continue
+        common = sorted(set(spec.hooks) & set(graphs.build_tiny(model, (224, 224)).hooks))      # (the attack checks depths at 224 x 224)
+        os.environ.update(env)                                 # read when the net is planned
+        try:
+            atk = attacks.AENS_I2V_MF([model], depths={model: [common[0], common[-1]]}, step_size=0.005, momentum=0.5, steps=2, engine=eng,
+                                      graph_builder=graphs.build_tiny, weight_seed=0)
+            rec = {}
+            for frames in (3, 2):
+                adv, _, costs = atk(vid[:, :, :frames], torch.zeros(1, dtype=torch.long), ["clip"])
+                net = atk._nets[0]
+                rec[f"frames{frames}"] = {"workspace_bytes": net.workspace_bytes(), "max_frames": net.max_frames,
+                                          "act": [sha(net.read_hook(i, frames)) for i in range(len(net.hooks))],
+                                          "grad": [sha(net.read_hook(i, frames, grad=True)) for i in range(len(net.hooks))],
+                                          "gx": sha(atk._gx), "adv": sha(adv), "costs": [repr(float(c)) for c in costs]}
+            net.close()
+        finally:
+            for k in env:
+                del os.environ[k]
+        record[name] = rec
+        print(name, rec["frames3"]["workspace_bytes"], rec["frames3"]["adv"][:16], rec["frames2"]["adv"][:16], flush=True)
+    with open(out_path, "w") as fh:
+        json.dump(record, fh, indent=1)
+
+
 def diff(a_path, b_path):
     a, b = json.load(open(a_path)), json.load(open(b_path))
     bad = 0
@@ -71,8 +138,11 @@ def diff(a_path, b_path):
                         if la != lb:
                             print(f"  line {i}: {la} != {lb}")
                             break
-        print(f"{name}: workspace {ra.get('workspace_bytes')} fusion {ra.get('fusion_info')} dump lines {ra.get('dump_lines')}")
-    print("plans identical" if not bad else f"{bad} differences")
+        if "workspace_bytes" in ra:
+            print(f"{name}: workspace {ra.get('workspace_bytes')} fusion {ra.get('fusion_info')} dump lines {ra.get('dump_lines')}")
+        else:
+            print(f"{name}: " + " ".join(f"{k} workspace {v.get('workspace_bytes')} adv {v.get('adv', '')[:16]}" for k, v in sorted(ra.items())))
+    print("records identical" if not bad else f"{bad} differences")
     return 1 if bad else 0
 
 
@@ -92,4 +162,4 @@ def npy(dir_a, dir_b):
 
 if __name__ == "__main__":
     cmd, args = sys.argv[1], sys.argv[2:]
-    sys.exit({"plan": plan, "diff": diff, "npy": npy}[cmd](*args) or 0)
+    sys.exit({"plan": plan, "tokens": tokens, "diff": diff, "npy": npy}[cmd](*args) or 0)
