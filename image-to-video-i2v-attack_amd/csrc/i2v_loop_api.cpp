@@ -1,5 +1,6 @@
 // The loop kernels' C entries: argument checks in front of one backend call each.  None of them touches a net.
 #include "i2v_net.h"
+#include "../../include/i2v_nl_launch.h"
 #ifndef I2V_HAVE_CONVNEXT
 #include "i2v_convnext_host.h"   // (the host simulation's one-file build: the token-major depthwise launch as scalar code)
 #endif
@@ -352,4 +353,51 @@ extern "C" int i2v_mixer_tokens_bwd_f32(const float* z, const float* g, const fl
     p.in_scale = in_scale; p.in_shift = in_shift; p.out_scale = out_scale; p.F = frames; p.S = S; p.Sh = Sh; p.C = C; p.bwd = 1;
     p.ct = channel_tile;
     return mixer_tokens_launch(__func__, p, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The non-local block's launches and the gated add on their own (include/i2v_nl_launch.h): tests and tools
+// ---------------------------------------------------------------------------------------------
+static bool nl_view_ok(const i2v_nl_act& v, int count) { return v.p && v.T > 0 && v.HW > 0 && (int64_t)v.T * v.HW == count; }
+
+extern "C" int i2v_nl_gemm_f32(const i2v_nl_gemm_desc* d, void* stream) {
+    BAD_ARG_IF(!d, " (null descriptor)");
+    BAD_ARG_IF(d->form < 1 || d->form > 3, " (form 1..3)");
+    const int rows = d->form == 1 ? d->M : d->Cc, cols = d->form == 2 ? d->M : d->N;
+    if (rows <= 0 || cols <= 0 || d->clips <= 0) return 0;
+    if (d->form == 1) {
+        BAD_ARG_IF(!d->D || d->Cc <= 0 || !nl_view_ok(d->A, d->M) || !nl_view_ok(d->B, d->N), " (form 1: D, channels, A of M and B of N positions)");
+    } else {
+        BAD_ARG_IF(!d->Din || !d->C || d->c_T <= 0 || d->c_HW <= 0 || (int64_t)d->c_T * d->c_HW != cols ||
+                   !nl_view_ok(d->A, d->form == 2 ? d->N : d->M), " (forms 2 / 3: Din, A of the reduced count and C of the column count of positions)");
+        BAD_ARG_IF(d->ksplit > 1 && !d->part, " (a K-split launch needs part)");
+    }
+    I2VAttnGemm g; memset(&g, 0, sizeof g);
+    g.form = d->form; g.clips = d->clips; g.Cc = d->Cc; g.M = d->M; g.N = d->N;
+    g.A.p = d->A.p; g.A.nstride = d->A.nstride; g.A.T = d->A.T; g.A.HW = d->A.HW;
+    g.B.p = d->B.p; g.B.nstride = d->B.nstride; g.B.T = d->B.T; g.B.HW = d->B.HW;
+    g.Cact = d->C; g.C_nstride = d->c_nstride; g.C_T = d->c_T; g.C_HW = d->c_HW;
+    g.D = d->D; g.Din = d->Din; g.scale = d->scale; g.accumulate = d->accumulate; g.ksplit = d->ksplit; g.part = d->part;
+    RETURN_BE(k_attn_gemm(g, stream));
+}
+
+extern "C" int i2v_nl_softmax_rows_f32(float* X, const float* P, int64_t rows, int N, int mode, void* stream) {
+    BAD_ARG_IF(!X || N <= 0 || mode < 0 || mode > 1 || (mode == 1 && !P), " (mode 0, or 1 with P; N > 0)");
+    if (rows <= 0) return 0;
+    I2VSoftmaxRows p; memset(&p, 0, sizeof p);
+    p.X = X; p.P = P; p.rows = rows; p.N = N; p.mode = mode;
+    RETURN_BE(k_softmax_rows(p, stream));
+}
+
+extern "C" int i2v_nl_addmask_f32(const i2v_nl_addmask_desc* d, void* stream) {
+    BAD_ARG_IF(!d, " (null descriptor)");
+    BAD_ARG_IF(!d->out || d->C <= 0 || d->HW <= 0);
+    if (d->N <= 0) return 0;
+    BAD_ARG_IF(d->gate && (int64_t)d->gate_stride * 32 < (int64_t)d->N * d->HW, " (gate rows of at least N * HW bits)");
+    I2VAddMaskParams p; memset(&p, 0, sizeof p);
+    p.out = d->out; p.out_nstride = d->out_nstride;
+    for (int i = 0; i < 3; ++i) { p.a[i] = d->a[i]; p.a_nstride[i] = d->a_nstride[i]; }
+    p.mask = d->mask; p.mask_nstride = d->mask_nstride; p.gate = d->gate; p.gate_stride = d->gate_stride;
+    p.N = d->N; p.C = d->C; p.HW = d->HW; p.gain = d->gain;
+    RETURN_BE(k_addmask(p, stream));
 }

@@ -314,6 +314,31 @@ XF_EXPORTS = tuple(_XF_PROTOS)
 XF_HOST_PROTOS = {k: v for k, v in _XF_PROTOS.items() if "softmax" not in k}
 
 
+class NlAct(C.Structure):
+    _fields_ = [("p", _P), ("nstride", _L), ("T", C.c_int32), ("HW", C.c_int32)]
+
+
+class NlGemmDesc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("form", "clips", "Cc", "M", "N")] + [("A", NlAct), ("B", NlAct), ("C", _P), ("c_nstride", _L),
+                ("c_T", C.c_int32), ("c_HW", C.c_int32), ("D", _P), ("Din", _P), ("scale", _F), ("accumulate", C.c_int32),
+                ("ksplit", C.c_int32), ("part", _P)])
+
+
+class NlAddMaskDesc(C.Structure):
+    _fields_ = [("out", _P), ("out_nstride", _L), ("a", _P * 3), ("a_nstride", _L * 3), ("mask", _P), ("mask_nstride", _L), ("gate", _P),
+                ("gate_stride", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("HW", C.c_int32), ("gain", _F)]
+
+
+# The non-local block's launches and the gated add on their own (`include/i2v_nl_launch.h`): a header of its own, kept apart from
+# EXPORTS.  Every build exports them: the host simulation runs their scalar twins.
+_NL_PROTOS = {
+    "i2v_nl_gemm_f32": ([C.POINTER(NlGemmDesc), _P], _I),
+    "i2v_nl_softmax_rows_f32": ([_P, _P, _L, _I, _I, _P], _I),
+    "i2v_nl_addmask_f32": ([C.POINTER(NlAddMaskDesc), _P], _I),
+}
+NL_EXPORTS = tuple(_NL_PROTOS)
+
+
 # The transformer families by the word in their entry names (`i2v_<word>_*`)
 FAMILY_PROTOS = {"vit": _VIT_PROTOS, "swin": _SWIN_PROTOS, "convnext": _CONVNEXT_PROTOS, "mixer": _MIXER_PROTOS, "cait": _CAIT_PROTOS,
                  "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS}
@@ -341,7 +366,7 @@ def load():
         lib = bind(C.CDLL(path))
         if lib.i2v_backend() != HIP_BACKEND:
             raise I2VError(f"{path} reports backend {lib.i2v_backend()!r}, expected {HIP_BACKEND!r}")
-        for protos in (_LOADER_PROTOS, *FAMILY_PROTOS.values(), _XF_PROTOS):
+        for protos in (_LOADER_PROTOS, *FAMILY_PROTOS.values(), _XF_PROTOS, _NL_PROTOS):
             bind(lib, protos)
         _lib = lib
     return _lib

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "..", "image-to-video-i2v-attack_amd", "csrc")
 SRCS = [os.path.join(HERE, "hostsim", "hostsim_backend.cpp")] + [
         os.path.join(CSRC, f) for f in ("i2v_engine.cpp", "i2v_pack.cpp", "i2v_plan.cpp", "i2v_tune.cpp", "i2v_run.cpp", "i2v_loop_api.cpp",
                                         "i2v_net.h", "i2v_params.h", "i2v_kernels.h")] + [
-        os.path.join(HERE, "..", "include", "i2v_hip.h")]
+        os.path.join(HERE, "..", "include", h) for h in ("i2v_hip.h", "i2v_nl_launch.h")]
 _engine = None
 
 
@@ -27,6 +27,7 @@ def hostsim_engine():
         from i2v_amd import lib
         from i2v_amd.engine import Engine
         capi = lib.bind(ctypes.CDLL(SO))
+        lib.bind(capi, lib._NL_PROTOS)
         assert capi.i2v_backend() == b"hostsim"
         _engine = Engine("cpu", capi=capi)
     return _engine

@@ -1,7 +1,9 @@
 """Developer soak test (GPU box): random clip shapes through the tiny non-local I3D (two non-local blocks inside the hooked stage) --
 attention products over frame-major views whose planes are / are not multiples of 4 (vector vs per-element operand loads, frames
 crossed inside a group of four positions), with and without the K-split of the dg / dphi gradients (>= 512 positions) -- forward +
-input gradient through the C ABI against the torch module in float64.  python tools/soak_attn.py <seconds> [seed]"""
+input gradient through the C ABI against the torch module in float64.  python tools/soak_attn.py <seconds> [seed]
+The suite's own coverage of these edges is the case table tests/nl_cases.py (tests/test_nl_kernels_cpu.py, tests/test_gpu_nl_kernels.py),
+which reaches the launches one at a time with named shapes; this soak stays a developer tool for random whole-net shapes."""
 import os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "image-to-video-i2v-attack_amd")); sys.path.insert(0, ROOT)
