@@ -83,7 +83,7 @@ class _ImageGuided(Attack):
         # the scalar-depth lookup's tensor -- the two differ for SqueezeNet (Fire output vs its 3x3 branch)
         self._whole = list(whole_module) if whole_module is not None else [False] * len(self.model_names)
         self._engine = engine
-        self._builder = graph_builder or _graphs.build
+        self._builder = graph_builder or _graphs.build_surrogate
         self._wseed = weight_seed
         self._nets = None
         self._net_key = None

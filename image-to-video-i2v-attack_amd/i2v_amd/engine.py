@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import BeitSpec, CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
+from .graphs import BeitSpec, CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -343,6 +343,68 @@ class Engine:
         assert tuple(S.shape[1:]) == tuple(bias.shape)
         _lib.check(self.capi, self.capi.i2v_beit_bias_add_f32(_ptr(S, self), _ptr(bias, self), S.shape[0], bias.numel(), self.stream()))
         return S
+
+    def build_pit_net(self, spec: PitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "PitNet":
+        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
+
+    def pit_attention(self, qkv: torch.Tensor, heads: int, scale: float = None):
+        """Streaming attention on its own (`i2v_pit_attention_f32`): qkv (frames, T, 3 heads dh), any T -> out (frames, T, heads dh) and the
+        row log-sum-exp lse (frames, heads, T); `scale` defaults to dh^-0.5."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        assert 3 * heads * dh == C3
+        out = torch.empty(n, T, heads * dh, dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(n, heads, T, dtype=torch.float32, device=qkv.device)
+        _lib.check(self.capi, self.capi.i2v_pit_attention_f32(_ptr(qkv, self), n, T, heads, dh, dh ** -0.5 if scale is None else scale,
+                                                              _ptr(out, self), _ptr(lse, self), self.stream()))
+        return out, lse
+
+    def pit_attention_bwd(self, qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dout: torch.Tensor, heads: int,
+                          scale: float = None) -> torch.Tensor:
+        """The input gradient of that launch (`i2v_pit_attention_bwd_f32`) from the forward's out and lse and dout = d(out): dqkv as qkv."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        dqkv = torch.empty_like(qkv)
+        delta = torch.empty_like(lse)
+        _lib.check(self.capi, self.capi.i2v_pit_attention_bwd_f32(_ptr(qkv, self), _ptr(out, self), _ptr(lse, self), _ptr(dout, self), n, T, heads,
+                                                                  dh, dh ** -0.5 if scale is None else scale, _ptr(delta, self),
+                                                                  _ptr(dqkv, self), self.stream()))
+        return dqkv
+
+    def pit_pool(self, x: torch.Tensor, w: torch.Tensor, b, grid: int, prefix: int = 0, into: torch.Tensor = None) -> torch.Tensor:
+        """The pooling convolution on its own (`i2v_pit_pool_f32`): x (frames, prefix + grid^2, C), w (2 C, 9), b (2 C) or None -> y
+        (frames, prefix + go^2, 2 C) whose prefix rows are left as `into` has them (zeros without `into`)."""
+        n, T, Cn = x.shape
+        go = (grid - 1) // 2 + 1
+        assert T == prefix + grid * grid
+        y = torch.zeros(n, prefix + go * go, 2 * Cn, dtype=torch.float32, device=x.device) if into is None else into
+        _lib.check(self.capi, self.capi.i2v_pit_pool_f32(_ptr(x, self), _ptr(w, self), None if b is None else _ptr(b, self), n, grid, Cn, prefix,
+                                                         _ptr(y, self), self.stream()))
+        return y
+
+    def pit_pool_bwd(self, dy: torch.Tensor, w: torch.Tensor, grid: int, prefix: int = 0, into: torch.Tensor = None) -> torch.Tensor:
+        """Its input gradient (`i2v_pit_pool_bwd_f32`): dy (frames, prefix + go^2, 2 C) -> dx (frames, prefix + grid^2, C), written
+        (prefix rows zeros) or, with `into`, added to the grid rows of `into`."""
+        n, To, C2 = dy.shape
+        dx = torch.zeros(n, prefix + grid * grid, C2 // 2, dtype=torch.float32, device=dy.device) if into is None else into
+        _lib.check(self.capi, self.capi.i2v_pit_pool_bwd_f32(_ptr(dy, self), _ptr(w, self), n, grid, C2 // 2, prefix, int(into is not None),
+                                                             _ptr(dx, self), self.stream()))
+        return dx
+
+    def pit_patch_gather(self, img: torch.Tensor, p: int, s: int) -> torch.Tensor:
+        """Overlapping patch rows (`i2v_pit_patch_gather_f32`): img (frames, C, side, side) -> rows (frames g^2, C p^2)."""
+        n, Cn, side, _ = img.shape
+        g = (side - p) // s + 1
+        rows = torch.empty(n * g * g, Cn * p * p, dtype=torch.float32, device=img.device)
+        _lib.check(self.capi, self.capi.i2v_pit_patch_gather_f32(_ptr(img, self), n, Cn, side, p, s, _ptr(rows, self), self.stream()))
+        return rows
+
+    def pit_patch_scatter(self, rows: torch.Tensor, frames: int, chans: int, side: int, p: int, s: int, into: torch.Tensor = None) -> torch.Tensor:
+        """The gather's transpose (`i2v_pit_patch_scatter_f32`): rows -> gimg (frames, C, side, side), written or added to `into`."""
+        g = torch.empty(frames, chans, side, side, dtype=torch.float32, device=rows.device) if into is None else into
+        _lib.check(self.capi, self.capi.i2v_pit_patch_scatter_f32(_ptr(rows, self), frames, chans, side, p, s, int(into is not None), _ptr(g, self),
+                                                                  self.stream()))
+        return g
 
     # ---- measurement ----
     KINDS = ("conv_igemm_fwd", "conv_igemm_imggrad", "pool_fwd", "pool_bwd", "addmask", "conv_igemm_dgrad")
@@ -988,6 +1050,19 @@ class BeitNet(TokenNet):
     _api = "beit"
 
 
+class PitNet(TokenNet):
+    """A PiT surrogate: a hook is the residual stream after one block (flat index across the three stages), all tokens with the prefix
+    tokens, before any pooling: (tokens * width) floats per frame of the block's stage.  Packed with the position table token-major."""
+    _api = "pit"
+
+    def hook_shape(self, i):
+        return (*self.graph.hook_shape(self.hook_tensors[i]), 1)
+
+
+def _three(v):
+    return (C.c_int32 * 3)(*v)
+
+
 def _four(v):
     v = list(v)
     return (C.c_int32 * 4)(*(v + [0] * (4 - len(v))))
@@ -1021,4 +1096,6 @@ TOKEN_FAMILIES = {
     XcitSpec: (XcitNet, lambda s: _lib.XcitConfig(s.img, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
     TwinsSpec: (TwinsNet, _twins_config, _stages),
     BeitSpec: (BeitNet, lambda s: _lib.BeitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
+    PitSpec: (PitNet, lambda s: _lib.PitConfig(s.img, s.patch, s.stride, s.in_chans, s.prefix, _three(s.widths), _three(s.heads), _three(s.depths),
+                                               s.ln_eps), _blocks),
 }

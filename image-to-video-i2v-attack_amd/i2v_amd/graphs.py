@@ -2620,6 +2620,209 @@ def beit_tiny_twin(model_name: str = "beit_base_patch16_224", in_hw=(64, 64)) ->
 
 
 # ---------------------------------------------------------------------------
+# the PiT surrogates: a ViT whose token grid is pooled between three stages like a CNN's, with an overlapping patch embedding and a
+# spatial position table, planned on the transformer stack (include/i2v_pit.h)
+# ---------------------------------------------------------------------------
+#: timm 0.5.0's `PoolingVisionTransformer` models at 224 x 224: name -> (patch, stride, base dim, heads per stage, depth per stage);
+#: every name has a `_distilled_224` twin with two prefix tokens (`pit_named`)
+PIT_MODELS: Dict[str, Tuple[int, int, int, Tuple[int, int, int], Tuple[int, int, int]]] = {
+    "pit_ti_224": (16, 8, 32, (2, 4, 8), (2, 6, 4)),
+    "pit_xs_224": (16, 8, 48, (2, 4, 8), (2, 6, 4)),
+    "pit_s_224": (16, 8, 48, (3, 6, 12), (2, 6, 4)),
+    "pit_b_224": (14, 7, 64, (4, 8, 16), (3, 6, 4)),
+}
+PIT_MODELS.update({k.replace("_224", "_distilled_224"): v for k, v in list(PIT_MODELS.items())})
+
+
+@dataclass
+class PitSpec:
+    """timm 0.5.0 `PoolingVisionTransformer` up to its last block (restated, UNCHECKED against timm):
+    `patch_embed.conv`, a patch x patch convolution at stride `stride` < patch, padding 0, with bias, onto a grid of
+    (img - patch) / stride + 1 a side; `pos_embed` (1, C, g, g) added to the grid tokens only; `cls_token` (1, prefix, C) prepended
+    (prefix = 2 for a distilled net); three stages `transformers.{s}` of pre-norm ViT blocks (LayerNorm eps `ln_eps`, exact GELU, MLP
+    ratio 4, qkv bias, head width = base dim); behind stages 0 and 1 `transformers.{s}.pool`: `pool.conv`, a Conv2d(C, 2 C, 3, stride 2,
+    padding 1, groups = C) on the grid tokens (grid -> (g - 1) / 2 + 1), and `pool.fc`, a Linear(C, 2 C) on the prefix tokens.
+    `hooks`: depth d (1..4) -> zero-based FLAT block index whose OUTPUT (the residual stream after it, all tokens, the prefix tokens
+    included, before any pooling) is the hooked feature: the last block of stage 0, block depth[1] / 2 - 1 of stage 1, the last block of
+    stage 1, the last block of stage 2.  `norm`, `head` and `head_dist` lie behind every hook."""
+    arch: str
+    img: int
+    patch: int = 16
+    stride: int = 8
+    base_dim: int = 48
+    heads: Tuple[int, int, int] = (3, 6, 12)
+    depths: Tuple[int, int, int] = (2, 6, 4)
+    prefix: int = 1
+    in_chans: int = 3
+    ln_eps: float = 1e-6
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        if self.patch > self.img or (self.img - self.patch) % self.stride or self.stride > self.patch:
+            raise ValueError(f"{self.arch}: patches of {self.patch} at stride {self.stride} do not tile a {self.img} x {self.img} frame")
+        if self.base_dim % 4 or self.base_dim > 64 or self.prefix not in (1, 2) or len(self.heads) != 3 or len(self.depths) != 3:
+            raise ValueError(f"{self.arch}: head width {self.base_dim} (a multiple of 4 up to 64), {self.prefix} prefix tokens (1 or 2), three stages")
+        if not self.hooks:
+            d = self.depths
+            self.hooks = {1: d[0] - 1, 2: d[0] + d[1] // 2 - 1, 3: d[0] + d[1] - 1, 4: d[0] + d[1] + d[2] - 1}
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def grids(self) -> Tuple[int, int, int]:
+        g0 = (self.img - self.patch) // self.stride + 1
+        g1 = (g0 - 1) // 2 + 1
+        return (g0, g1, (g1 - 1) // 2 + 1)
+
+    @property
+    def widths(self) -> Tuple[int, int, int]:
+        return tuple(self.base_dim * h for h in self.heads)
+
+    @property
+    def blocks(self) -> int:
+        return sum(self.depths)
+
+    def stage_of(self, block: int) -> int:
+        """The stage of a flat block index."""
+        d = self.depths
+        return 0 if block < d[0] else 1 if block < d[0] + d[1] else 2
+
+    def tokens(self, stage: int) -> int:
+        return self.prefix + self.grids[stage] ** 2
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based flat block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def hook_shape(self, block: int) -> Tuple[int, int]:
+        st = self.stage_of(block)
+        return (self.tokens(st), self.widths[st])
+
+    def block_key(self, block: int) -> str:
+        """timm's prefix of a flat block index: `transformers.{s}.blocks.{j}.`"""
+        st = self.stage_of(block)
+        return f"transformers.{st}.blocks.{block - sum(self.depths[:st])}."
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block, in timm's order."""
+        g0, W = self.grids[0], self.widths
+        out = {"pos_embed": (1, W[0], g0, g0), "cls_token": (1, self.prefix, W[0]),
+               "patch_embed.conv.weight": (W[0], self.in_chans, self.patch, self.patch), "patch_embed.conv.bias": (W[0],)}
+        b = 0
+        for st in range(3):
+            D = W[st]
+            for _ in range(self.depths[st]):
+                p = self.block_key(b)
+                out.update({p + "norm1.weight": (D,), p + "norm1.bias": (D,), p + "attn.qkv.weight": (3 * D, D), p + "attn.qkv.bias": (3 * D,),
+                            p + "attn.proj.weight": (D, D), p + "attn.proj.bias": (D,), p + "norm2.weight": (D,), p + "norm2.bias": (D,),
+                            p + "mlp.fc1.weight": (4 * D, D), p + "mlp.fc1.bias": (4 * D,), p + "mlp.fc2.weight": (D, 4 * D),
+                            p + "mlp.fc2.bias": (D,)})
+                b += 1
+            if st < 2:
+                p = f"transformers.{st}.pool."
+                out.update({p + "conv.weight": (2 * D, 1, 3, 3), p + "conv.bias": (2 * D,), p + "fc.weight": (2 * D, D), p + "fc.bias": (2 * D,)})
+        return out
+
+    def native_arrays(self, sd, n_blocks: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_pit_create` takes for the first `n_blocks` flat blocks, from a timm-layout state dict, as float32 host
+        tensors: the patch weight flattened as it stands, its bias, `pos_embed` transposed to token-major with `prefix` rows of zeros in
+        front, `cls_token` as (prefix, C); per block its 12 arrays; behind a stage whose successor runs a block, its pool's 4 arrays
+        (the filter as (2 C, 9))."""
+        import torch
+        f32 = lambda k: sd[k].detach().float().cpu().contiguous()      # noqa: E731
+        W, g0 = self.widths, self.grids[0]
+        pos = f32("pos_embed").reshape(W[0], g0 * g0).t()
+        out = [f32("patch_embed.conv.weight").reshape(W[0], -1), f32("patch_embed.conv.bias"),
+               torch.cat([torch.zeros(self.prefix, W[0]), pos]).contiguous(), f32("cls_token").reshape(self.prefix, W[0])]
+        for b in range(n_blocks):
+            st, p = self.stage_of(b), self.block_key(b)
+            if b and st != self.stage_of(b - 1):
+                q = f"transformers.{st - 1}.pool."
+                out += [f32(q + "conv.weight").reshape(W[st], 9), f32(q + "conv.bias"), f32(q + "fc.weight"), f32(q + "fc.bias")]
+            out += [f32(p + k) for k in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
+                                         "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
+        return out
+
+    def macs_per_frame(self) -> int:
+        total = self.grids[0] ** 2 * self.widths[0] * self.in_chans * self.patch ** 2
+        for st in range(3):
+            T, D = self.tokens(st), self.widths[st]
+            total += self.depths[st] * (T * D * 12 * D + 2 * T * T * D)
+        return total
+
+    def workspace_bytes(self, hook_blocks: Sequence[int], frames: int, composed: Optional[bool] = None) -> int:
+        """Device bytes `i2v_pit_create` plans for these hooks and `frames` frames (the formula of csrc/i2v_pit.cpp): the weights of the
+        blocks run and of the pools between the stages run; per block its input, qkv, the mid stream, the fc1 pre-activation, four
+        statistics per token, and the attention output with its log-sum-exp; per stage the stream behind it; the shared scratch -- three
+        streams, one MLP-wide, the qkv gradient (all at the widest stage's size), the patch rows and their embedding, delta --; one
+        gradient view per hook.  `composed`: the plan of the shared-launch route (`I2V_PIT_ATTN=0`; None reads the environment as the
+        planner does), which keeps per block the probabilities -- tokens x tokens rounded up to 4, per head and frame -- instead of the
+        output and the log-sum-exp, and one array of scratch the size of the largest block's probabilities instead of delta."""
+        import os
+        if composed is None:
+            composed = os.environ.get("I2V_PIT_ATTN") == "0"
+        F, nb, W = frames, max(hook_blocks) + 1, self.widths
+        KP, NP = self.in_chans * self.patch ** 2, self.grids[0] ** 2
+        total = W[0] * KP + W[0] + (self.prefix + NP) * W[0] + self.prefix * W[0]
+        mFTD = mStat = mP = first = 0
+        for st in range(3):
+            if first >= nb:
+                break
+            D, T, H = W[st], self.tokens(st), self.heads[st]
+            count, FT = min(self.depths[st], nb - first), F * T
+            probs = F * H * T * ((T + 3) // 4 * 4) if composed else 0
+            core = probs if composed else FT * D + F * H * T
+            total += count * (12 * D * D + 13 * D + 9 * FT * D + 4 * FT + core) + FT * D
+            first += self.depths[st]
+            if first < nb:
+                total += 2 * D * 9 + 2 * D + 2 * D * D + 2 * D
+            mFTD, mStat, mP = max(mFTD, FT * D), max(mStat, F * H * T), max(mP, probs)
+        total += 10 * mFTD + F * NP * (KP + W[0]) + (mP if composed else mStat)
+        total += sum(F * self.hook_shape(b)[0] * self.hook_shape(b)[1] for b in hook_blocks)
+        return 4 * total
+
+
+def is_pit_name(model_name: str) -> bool:
+    """A name of timm's PiT vocabulary (`pit.py`), served (`PIT_MODELS`) or not: `graphs.build_surrogate` routes these to `pit_named`, which
+    refuses the ones that are not offered with a message that lists the served names."""
+    return model_name.startswith("pit_")
+
+
+def pit_named(model_name: str, in_hw=(224, 224)) -> PitSpec:
+    """Any row of `PIT_MODELS`, at 224 x 224 only.  Refused, each with the reason: names outside the table and every other input size."""
+    served = "; served: " + ", ".join(PIT_MODELS)
+    if model_name not in PIT_MODELS:
+        raise ValueError(f"PiT surrogate {model_name!r}: not a model of this table (224 x 224 checkpoints only)" + served)
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}): its position table is "
+                         "that of its own grid" + served)
+    patch, stride, base, heads, depths = PIT_MODELS[model_name]
+    return PitSpec(model_name, 224, patch, stride, base, heads, depths, 2 if "_distilled_" in model_name else 1)
+
+
+def pit_tiny_twin(model_name: str = "pit_s_224", in_hw=(64, 64)) -> PitSpec:
+    """The same topology at test size, by frame size (every served name maps to the same twins).  Not rows of `PIT_MODELS`.
+      64 x 64: "pit_test" -- patch 16 / stride 8, grids 7 -> 4 -> 2, one prefix token, base dim 16, heads 2 / 4 / 8, depths 2 / 2 / 2
+      70 x 70: "pit_test_70" -- patch 14 / stride 7, grids 9 -> 5 -> 3, TWO prefix tokens, base dim 12 (ragged against the MFMA's chunk
+        of 16), heads 2 / 4 / 8, depths 3 / 2 / 2
+      224 x 224 (the size the attack classes probe a builder with): "pit_test_224" -- 730 tokens in stage 0, base dim 32, heads
+        1 / 2 / 4, depths 1 / 2 / 1"""
+    if in_hw[0] != in_hw[1] or int(in_hw[0]) not in (64, 70, 224):
+        raise ValueError(f"the test-size PiTs take 64 x 64, 70 x 70 or 224 x 224 frames (got {tuple(in_hw)})")
+    side = int(in_hw[0])
+    if side == 64:
+        return PitSpec("pit_test", 64, 16, 8, 16, (2, 4, 8), (2, 2, 2), 1)
+    if side == 70:
+        return PitSpec("pit_test_70", 70, 14, 7, 12, (2, 4, 8), (3, 2, 2), 2)
+    return PitSpec("pit_test_224", 224, 16, 8, 32, (1, 2, 4), (1, 2, 1), 1)
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -2677,6 +2880,15 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
     raise UnboundLocalError("local variable 'model' referenced before assignment")
 
 
+def build_surrogate(model_name: str, in_hw=(224, 224)):
+    """The name resolver of the image-guided attack classes and the command line: `build`, with timm's PiT family in front (three
+    stages pooled by a depthwise convolution, overlapping patches: `pit_named`).  `build` itself keeps its vocabulary as it stands --
+    there a `pit_*` name is an unknown name, as in the reference -- so a family is added here without changing what `build` answers."""
+    if is_pit_name(model_name):
+        return pit_named(model_name, in_hw)
+    return build(model_name, in_hw)
+
+
 #: tiny variants used by parity tests / golden fixtures (same topology, fewer channels/blocks)
 def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
     if model_name in ("resnet", "resnet50"):
@@ -2721,4 +2933,7 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return twins_tiny_twin(model_name, in_hw)
     if model_name in BEIT_MODELS:
         return beit_tiny_twin(model_name, in_hw)
+    if is_pit_name(model_name):
+        pit_named(model_name)               # (a name outside the table is refused with the served names)
+        return pit_tiny_twin(model_name, in_hw)
     return build(model_name, in_hw)

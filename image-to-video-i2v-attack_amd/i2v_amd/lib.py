@@ -294,6 +294,26 @@ _BEIT_PROTOS = {
 BEIT_EXPORTS = tuple(_BEIT_PROTOS)
 
 
+class PitConfig(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("img", "patch", "stride", "in_chans", "prefix")]
+                + [(n, C.c_int32 * 3) for n in ("dims", "heads", "depths")] + [("ln_eps", C.c_float)])
+
+
+# The PiT surrogates (`include/i2v_pit.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it: the
+# planner runs there on scalar restatements, and so do the kernel entries on their own -- streaming attention forward and backward, the
+# pooling convolution pair and the overlapping patch gather / scatter pair.
+_PIT_PROTOS = {
+    **_net_protos("pit", PitConfig),
+    "i2v_pit_attention_f32": ([_P, _I, _I, _I, _I, _F, _P, _P, _P], _I),
+    "i2v_pit_attention_bwd_f32": ([_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P], _I),
+    "i2v_pit_pool_f32": ([_P, _P, _P, _I, _I, _I, _I, _P, _P], _I),
+    "i2v_pit_pool_bwd_f32": ([_P, _P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "i2v_pit_patch_gather_f32": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "i2v_pit_patch_scatter_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+}
+PIT_EXPORTS = tuple(_PIT_PROTOS)
+
+
 class XfGemmDesc(C.Structure):
     _fields_ = ([("A", _P)] + [(n, _L) for n in ("a_bo", "a_bi", "a_sm", "a_sk")] + [("B", _P)] + [(n, _L) for n in ("b_bo", "b_bi", "b_sk", "b_sn")]
                 + [("C", _P)] + [(n, _L) for n in ("c_bo", "c_bi", "c_sm")] + [(n, _P) for n in ("bias", "R", "C2", "H")]
@@ -341,7 +361,7 @@ NL_EXPORTS = tuple(_NL_PROTOS)
 
 # The transformer families by the word in their entry names (`i2v_<word>_*`)
 FAMILY_PROTOS = {"vit": _VIT_PROTOS, "swin": _SWIN_PROTOS, "convnext": _CONVNEXT_PROTOS, "mixer": _MIXER_PROTOS, "cait": _CAIT_PROTOS,
-                 "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS}
+                 "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS, "pit": _PIT_PROTOS}
 
 
 def bind(cdll, protos=_PROTOS):

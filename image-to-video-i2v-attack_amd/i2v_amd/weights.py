@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import BeitSpec, CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
+from .graphs import BeitSpec, CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -268,6 +268,30 @@ def _beit_synthetic(spec: BeitSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _pit_synthetic(spec: PitSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained PiT, drawn per key as `_beit_synthetic` draws: Linears and the patch convolution ~ fan_in^-0.5
+    N(0, 1) (`attn.proj` and `mlp.fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1).  What is new must show in the
+    tests: `pos_embed` and `cls_token` are N(0, 1) (timm's 0.02 would leave the position table and the prefix tokens below the tests'
+    bounds), and the pool filter `pool.conv.weight` is N(0, 1) / 3 over its 9 taps, so that a pooled token is of the size of its inputs."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k in ("pos_embed", "cls_token"):
+            sd[k] = torch.randn(*shp, generator=g)
+        elif k.endswith("pool.conv.weight"):
+            sd[k] = torch.randn(*shp, generator=g) / 3.0
+        elif k.endswith(("norm1.weight", "norm2.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if k.endswith(("fc2.weight", "attn.proj.weight")) else 1.0) * fan_in ** -0.5)
+    return sd
+
+
 def check_beit_buffers(spec: BeitSpec, sd, where: str) -> None:
     """timm's BEiT checkpoints carry the buffer `attn.relative_position_index` per block; it is computed from the geometry here and
     never loaded, so one that differs describes another model: refused by key name.  An absent one is fine."""
@@ -327,6 +351,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _twins_synthetic(graph, seed)
     if isinstance(graph, BeitSpec):
         return _beit_synthetic(graph, seed)
+    if isinstance(graph, PitSpec):
+        return _pit_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":
