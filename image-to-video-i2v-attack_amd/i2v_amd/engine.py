@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import BeitSpec, CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
+from .graphs import BeitSpec, CaitSpec, CoatSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -405,6 +405,75 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_pit_patch_scatter_f32(_ptr(rows, self), frames, chans, side, p, s, int(into is not None), _ptr(g, self),
                                                                   self.stream()))
         return g
+
+    def build_coat_net(self, spec: CoatSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "CoatNet":
+        return self.build_token_net(spec, state_dict, hook_stages, max_frames)
+
+    def coat_attention(self, qkv: torch.Tensor, E: torch.Tensor, heads: int, scale: float = None):
+        """Factorized attention on its own (`i2v_coat_factor_attention_f32`): qkv (frames, T, 3 heads dh), E (frames, T, heads dh), any T
+        -> out (frames, T, heads dh), gram (frames, heads, dh, dh) and kstat (frames, heads, 2, dh); `scale` defaults to dh^-0.5."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        assert 3 * heads * dh == C3
+        out = torch.empty(n, T, heads * dh, dtype=torch.float32, device=qkv.device)
+        gram = torch.empty(n, heads, dh, dh, dtype=torch.float32, device=qkv.device)
+        kstat = torch.empty(n, heads, 2, dh, dtype=torch.float32, device=qkv.device)
+        _lib.check(self.capi, self.capi.i2v_coat_factor_attention_f32(_ptr(qkv, self), _ptr(E, self), n, T, heads, dh,
+                                                                      dh ** -0.5 if scale is None else scale, _ptr(gram, self),
+                                                                      _ptr(kstat, self), _ptr(out, self), self.stream()))
+        return out, gram, kstat
+
+    def coat_attention_bwd(self, qkv: torch.Tensor, E: torch.Tensor, gram: torch.Tensor, kstat: torch.Tensor, dout: torch.Tensor, heads: int,
+                           scale: float = None):
+        """The input gradient of that launch (`i2v_coat_factor_attention_bwd_f32`) from the forward's gram and kstat: dqkv as qkv, and
+        dE = dout o q (the crpe backward carries it onto dv)."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        dqkv, dE, dgram = torch.empty_like(qkv), torch.empty_like(E), torch.empty_like(gram)
+        _lib.check(self.capi, self.capi.i2v_coat_factor_attention_bwd_f32(_ptr(qkv, self), _ptr(E, self), _ptr(gram, self), _ptr(kstat, self),
+                                                                          _ptr(dout, self), n, T, heads, dh,
+                                                                          dh ** -0.5 if scale is None else scale, _ptr(dgram, self),
+                                                                          _ptr(dqkv, self), _ptr(dE, self), self.stream()))
+        return dqkv, dE
+
+    def coat_dwmix(self, x: torch.Tensor, filters, bias, grid: int, prefix: int = 1, residual: bool = False, col: int = 0, channels: int = None,
+                   bwd: bool = False, into: torch.Tensor = None, into_col: int = 0) -> torch.Tensor:
+        """The per-channel-window depthwise convolution on its own (`i2v_coat_dwmix_f32`, with `bwd` its transpose
+        `i2v_coat_dwmix_bwd_f32`): x (frames, prefix + grid^2, row stride) read from column `col` on, `channels` wide (default: the whole
+        row); `filters` = (w3, w5, w7) as (9, n3), (25, n5), (49, n7), None for a window without channels -> y (frames, prefix + grid^2, C);
+        `into` (backward only): added to instead of written, from its column `into_col` on at its own row stride (dv inside a qkv gradient)."""
+        n, T, rs = x.shape
+        Cn = rs - col if channels is None else channels
+        assert T == prefix + grid * grid
+        w3, w5, w7 = filters
+        n3, n5 = (0 if w3 is None else w3.shape[1]), (0 if w5 is None else w5.shape[1])
+        ptr = lambda t: None if t is None else _ptr(t, self)      # noqa: E731
+        y = torch.empty(n, T, Cn, dtype=torch.float32, device=x.device) if into is None else into
+        xp, yp = C.c_void_p(_ptr(x, self).value + 4 * col), C.c_void_p(_ptr(y, self).value + 4 * into_col)
+        if bwd:
+            _lib.check(self.capi, self.capi.i2v_coat_dwmix_bwd_f32(xp, rs, ptr(w3), ptr(w5), ptr(w7), n, grid, Cn, n3, n5, prefix, int(residual),
+                                                                   int(into is not None), yp, y.shape[2], self.stream()))
+        else:
+            _lib.check(self.capi, self.capi.i2v_coat_dwmix_f32(xp, rs, ptr(w3), ptr(w5), ptr(w7), ptr(bias), n, grid, Cn, n3, n5, prefix,
+                                                               int(residual), yp, y.shape[2], self.stream()))
+        return y
+
+    def coat_cell_gather(self, x: torch.Tensor, grid: int, s: int, prefix: int = 1) -> torch.Tensor:
+        """The s x s cells of a token-major plane behind `prefix` rows (`i2v_coat_cell_gather_f32`): x (frames, prefix + grid^2, C) ->
+        rows (frames (grid / s)^2, s^2 C)."""
+        n, T, Cn = x.shape
+        rows = torch.empty(n * (grid // s) ** 2, s * s * Cn, dtype=torch.float32, device=x.device)
+        _lib.check(self.capi, self.capi.i2v_coat_cell_gather_f32(_ptr(x, self), n, grid, Cn, s, prefix, _ptr(rows, self), self.stream()))
+        return rows
+
+    def coat_cell_scatter(self, rows: torch.Tensor, frames: int, grid: int, s: int, prefix: int = 1, into: torch.Tensor = None) -> torch.Tensor:
+        """Its inverse (`i2v_coat_cell_scatter_f32`): rows -> dx (frames, prefix + grid^2, C), written with the prefix rows 0, or added to
+        `into`."""
+        Cn = rows.shape[1] // (s * s)
+        dx = torch.empty(frames, prefix + grid * grid, Cn, dtype=torch.float32, device=rows.device) if into is None else into
+        _lib.check(self.capi, self.capi.i2v_coat_cell_scatter_f32(_ptr(rows, self), frames, grid, Cn, s, prefix, int(into is not None),
+                                                                  _ptr(dx, self), self.stream()))
+        return dx
 
     # ---- measurement ----
     KINDS = ("conv_igemm_fwd", "conv_igemm_imggrad", "pool_fwd", "pool_bwd", "addmask", "conv_igemm_dgrad")
@@ -1059,6 +1128,13 @@ class PitNet(TokenNet):
         return (*self.graph.hook_shape(self.hook_tensors[i]), 1)
 
 
+class CoatNet(TokenNet):
+    """A CoaT-Lite surrogate: a hook is the residual stream after the last block of a stage, all tokens with the class token, before the
+    next patch embedding: ((1 + grid^2) * width) floats per frame.  Packed with the filters tap-major and the later patch embeddings in
+    the cell gather's column order."""
+    _api = "coat"
+
+
 def _three(v):
     return (C.c_int32 * 3)(*v)
 
@@ -1098,4 +1174,6 @@ TOKEN_FAMILIES = {
     BeitSpec: (BeitNet, lambda s: _lib.BeitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
     PitSpec: (PitNet, lambda s: _lib.PitConfig(s.img, s.patch, s.stride, s.in_chans, s.prefix, _three(s.widths), _three(s.heads), _three(s.depths),
                                                s.ln_eps), _blocks),
+    CoatSpec: (CoatNet, lambda s: _lib.CoatConfig(s.img, s.in_chans, _four(s.widths), s.heads, _four(s.depths), _four(s.mlp_ratios), *s.windows,
+                                                  s.ln_eps), _stages),
 }

@@ -2823,6 +2823,210 @@ def pit_tiny_twin(model_name: str = "pit_s_224", in_hw=(64, 64)) -> PitSpec:
 
 
 # ---------------------------------------------------------------------------
+# the CoaT-Lite surrogates: four stages of serial blocks whose attention is FACTORIZED -- a softmax down the token axis of K, a dh x dh
+# product per head -- with a convolutional position encoding, planned on the transformer stack (include/i2v_coat.h)
+# ---------------------------------------------------------------------------
+#: timm 0.5.0's serial `CoaT` models at 224 x 224: name -> (width per stage, depth per stage, MLP ratio per stage); 8 heads, crpe
+#: windows 3 / 5 / 7 on 2 / 3 / 3 heads
+COAT_MODELS: Dict[str, Tuple[Tuple[int, int, int, int], Tuple[int, int, int, int], Tuple[int, int, int, int]]] = {
+    "coat_lite_tiny": ((64, 128, 256, 320), (2, 2, 2, 2), (8, 8, 4, 4)),
+    "coat_lite_mini": ((64, 128, 320, 512), (2, 2, 2, 2), (8, 8, 4, 4)),
+    "coat_lite_small": ((64, 128, 320, 512), (3, 4, 6, 3), (8, 8, 4, 4)),
+}
+#: timm's CoaT names with parallel blocks: refused with that reason
+COAT_PARALLEL = ("coat_tiny", "coat_mini")
+
+
+@dataclass
+class CoatSpec:
+    """timm 0.5.0 `CoaT` with serial blocks only, up to its last block (restated from memory of coat.py, UNCHECKED
+    against timm): `patch_embed1`, a Conv2d(3, C, 4, stride 4) and a LayerNorm; `patch_embed{2,3,4}`, a Conv2d(C', C, 2, stride 2) and
+    a LayerNorm on the previous stage's grid tokens, the class token dropped; `cls_token{k}` (1, 1, C) in front of every stage, no
+    position table; `serial_blocks{k}.{j}`: x = cpe(x); x = x + proj(FA(LN1 x)); x = x + fc2(gelu(fc1(LN2 x))) with LayerNorm eps
+    `ln_eps`, a qkv bias and the exact GELU.  `cpe{k}.proj` is a depthwise 3 x 3 with a residual on the grid tokens.  FA takes the
+    softmax of k over the TOKENS per channel, G = softmax(k)^T v per head, out = dh^-0.5 q G + q o E, E = `crpe{k}` of v as an image (0 on
+    the class row): `conv_list.0 / 1 / 2`, depthwise 3 x 3 / 5 x 5 / 7 x 7 on the first `windows[0]`, the next `windows[1]` and the last
+    `windows[2]` heads.  `hooks`: depth d (1..4) -> zero-based stage whose output (the residual stream after its last block, all tokens
+    with the class token, before the next patch embedding) is the hooked feature.  `norm*`, `head` and `aggregate` lie behind every hook."""
+    arch: str
+    img: int
+    widths: Tuple[int, int, int, int] = (64, 128, 256, 320)
+    depths: Tuple[int, int, int, int] = (2, 2, 2, 2)
+    mlp_ratios: Tuple[int, int, int, int] = (8, 8, 4, 4)
+    heads: int = 8
+    windows: Tuple[int, int, int] = (2, 3, 3)
+    in_chans: int = 3
+    ln_eps: float = 1e-6
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        if self.img % 32:
+            raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame is not tiled by the 4 x 4 patches and three 2 x 2 embeddings")
+        if sum(self.windows) != self.heads or min(self.windows) < 1 or any(w % self.heads or (w // self.heads) % 4 or w // self.heads > 64
+                                                                            for w in self.widths):
+            raise ValueError(f"{self.arch}: widths {self.widths} over {self.heads} heads (head widths: multiples of 4 up to 64), "
+                             f"windows {self.windows} (positive, summing to the heads)")
+        if not self.hooks:
+            self.hooks = {1: 0, 2: 1, 3: 2, 4: 3}
+
+    stages = 4
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def grids(self) -> Tuple[int, int, int, int]:
+        return tuple(self.img // 4 // 2 ** k for k in range(4))
+
+    @property
+    def head_widths(self) -> Tuple[int, int, int, int]:
+        return tuple(w // self.heads for w in self.widths)
+
+    def tokens(self, stage: int) -> int:
+        return 1 + self.grids[stage] ** 2
+
+    def width(self, stage: int) -> int:
+        return self.widths[stage]
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based stage whose output depth `depth` hooks (`whole_module` changes nothing: a stage is one module list)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def hook_shape(self, stage: int) -> Tuple[int, int]:
+        return (self.tokens(stage), self.widths[stage])
+
+    def window_channels(self, stage: int) -> Tuple[int, int, int]:
+        """Channels of stage `stage` that pass crpe's 3 x 3, 5 x 5 and 7 x 7."""
+        return tuple(w * self.head_widths[stage] for w in self.windows)
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block, the shared cpe / crpe under their stage-level keys."""
+        out = {}
+        for k in range(4):
+            D, Cin, p, s = self.widths[k], self.widths[k - 1] if k else self.in_chans, 2 if k else 4, k + 1
+            out.update({f"patch_embed{s}.proj.weight": (D, Cin, p, p), f"patch_embed{s}.proj.bias": (D,), f"patch_embed{s}.norm.weight": (D,),
+                        f"patch_embed{s}.norm.bias": (D,), f"cls_token{s}": (1, 1, D), f"cpe{s}.proj.weight": (D, 1, 3, 3),
+                        f"cpe{s}.proj.bias": (D,)})
+            for i, (K, n) in enumerate(zip((3, 5, 7), self.window_channels(k))):
+                out.update({f"crpe{s}.conv_list.{i}.weight": (n, 1, K, K), f"crpe{s}.conv_list.{i}.bias": (n,)})
+            M = self.mlp_ratios[k] * D
+            for j in range(self.depths[k]):
+                q = f"serial_blocks{s}.{j}."
+                out.update({q + "norm1.weight": (D,), q + "norm1.bias": (D,), q + "factoratt_crpe.qkv.weight": (3 * D, D),
+                            q + "factoratt_crpe.qkv.bias": (3 * D,), q + "factoratt_crpe.proj.weight": (D, D), q + "factoratt_crpe.proj.bias": (D,),
+                            q + "norm2.weight": (D,), q + "norm2.bias": (D,), q + "mlp.fc1.weight": (M, D), q + "mlp.fc1.bias": (M,),
+                            q + "mlp.fc2.weight": (D, M), q + "mlp.fc2.bias": (D,)})
+        return out
+
+    def shared_duplicates(self) -> Dict[str, str]:
+        """The keys under which a timm checkpoint carries the shared modules AGAIN inside every block -> their stage-level key."""
+        out = {}
+        for k in range(4):
+            s = k + 1
+            for j in range(self.depths[k]):
+                q = f"serial_blocks{s}.{j}."
+                for t in ("weight", "bias"):
+                    out[q + f"cpe.proj.{t}"] = f"cpe{s}.proj.{t}"
+                    for i in range(3):
+                        out[q + f"factoratt_crpe.crpe.conv_list.{i}.{t}"] = f"crpe{s}.conv_list.{i}.{t}"
+        return out
+
+    def native_arrays(self, sd, n_stages: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_coat_create` takes for the first `n_stages` stages, from a timm-layout state dict, as float32 host tensors.
+        Per stage 12: the patch weight as a Linear (stage 0 flattened as it stands, later stages with column (dy 2 + dx) C' + c, the cell
+        gather's order), its bias, the LayerNorm pair, `cls_token` as (C), a table of zeros (1 + g^2, C), `cpe.proj.weight` tap-major as
+        (9, C), its bias, crpe's filters tap-major as (9, n3), (25, n5), (49, n7) and its biases concatenated; then 12 per block."""
+        import torch
+        f32 = lambda k: sd[k].detach().float().cpu().contiguous()      # noqa: E731
+        out = []
+        for k in range(n_stages):
+            D, s = self.widths[k], k + 1
+            w = f32(f"patch_embed{s}.proj.weight")
+            out += [(w.permute(0, 2, 3, 1) if k else w).reshape(D, -1).contiguous(), f32(f"patch_embed{s}.proj.bias"),
+                    f32(f"patch_embed{s}.norm.weight"), f32(f"patch_embed{s}.norm.bias"), f32(f"cls_token{s}").reshape(D),
+                    torch.zeros(self.tokens(k), D), f32(f"cpe{s}.proj.weight").reshape(D, 9).t().contiguous(), f32(f"cpe{s}.proj.bias")]
+            out += [f32(f"crpe{s}.conv_list.{i}.weight").reshape(-1, K * K).t().contiguous() for i, K in enumerate((3, 5, 7))]
+            out += [torch.cat([f32(f"crpe{s}.conv_list.{i}.bias") for i in range(3)]).contiguous()]
+            for j in range(self.depths[k]):
+                q = f"serial_blocks{s}.{j}."
+                out += [f32(q + t) for t in ("norm1.weight", "norm1.bias", "factoratt_crpe.qkv.weight", "factoratt_crpe.qkv.bias",
+                                             "factoratt_crpe.proj.weight", "factoratt_crpe.proj.bias", "norm2.weight", "norm2.bias",
+                                             "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
+        return out
+
+    def macs_per_frame(self) -> int:
+        total = 0
+        for k in range(4):
+            T, D, np_, dh = self.tokens(k), self.widths[k], self.grids[k] ** 2, self.head_widths[k]
+            total += np_ * D * (4 * self.widths[k - 1] if k else 16 * self.in_chans)
+            total += self.depths[k] * (T * D * (4 * D + 2 * self.mlp_ratios[k] * D) + 2 * T * D * dh + np_ * D * (9 + 30))
+        return total
+
+    def workspace_bytes(self, hook_stages: Sequence[int], frames: int) -> int:
+        """Device bytes `i2v_coat_create` plans for these hooks and `frames` frames (the formula of csrc/i2v_coat.cpp): per stage run its
+        12 arrays, the embedding before its LayerNorm with two statistics per grid token and the stream behind it; per block its 12 arrays,
+        its input, qkv, the mid stream, the fc1 pre-activation, four statistics per token, E, G (frames, heads, dh, dh) and the column
+        statistics (frames, heads, 2, dh); the shared scratch -- five streams and the qkv gradient at the widest stage's size, one
+        MLP-wide, the patch rows, dG --; one gradient view per hook."""
+        F, ns = frames, max(hook_stages) + 1
+        total = mFTD = mMlp = mRows = mGram = 0
+        for k in range(ns):
+            D, T, np_, dh, M = self.widths[k], self.tokens(k), self.grids[k] ** 2, self.head_widths[k], self.mlp_ratios[k] * self.widths[k]
+            kp, FT = (4 * self.widths[k - 1] if k else 16 * self.in_chans), F * T
+            n3, n5, n7 = self.window_channels(k)
+            total += D * kp + 4 * D + T * D + 9 * D + D + 9 * n3 + 25 * n5 + 49 * n7 + D
+            total += self.depths[k] * (4 * D * D + 2 * M * D + 9 * D + M + 6 * FT * D + FT * M + 4 * FT + F * D * dh + 2 * F * D)
+            total += F * np_ * D + 2 * F * np_ + FT * D
+            mFTD, mMlp, mRows, mGram = max(mFTD, FT * D), max(mMlp, FT * M), max(mRows, F * np_ * kp), max(mGram, F * D * dh)
+        total += 8 * mFTD + mMlp + mRows + mGram
+        total += sum(F * self.tokens(k) * self.widths[k] for k in hook_stages)
+        return 4 * total
+
+
+def is_coat_name(model_name: str) -> bool:
+    """A name of timm's CoaT vocabulary (`coat.py`), served (`COAT_MODELS`) or not: `graphs.build_surrogate` routes these to `coat_named`,
+    which refuses the ones that are not offered with a message that lists the served names."""
+    return model_name.startswith("coat")
+
+
+def coat_named(model_name: str, in_hw=(224, 224)) -> CoatSpec:
+    """Any row of `COAT_MODELS`, at 224 x 224 only.  Refused, each with the reason: `coat_tiny` and `coat_mini` (parallel blocks with
+    bilinear cross-scale resampling), names outside the table and every other input size."""
+    served = "; served: " + ", ".join(COAT_MODELS)
+    if model_name in COAT_PARALLEL:
+        raise ValueError(f"CoaT surrogate {model_name!r}: its parallel blocks need bilinear cross-scale resampling, which is not built "
+                         "(the serial CoaT-Lite models are)" + served)
+    if model_name not in COAT_MODELS:
+        raise ValueError(f"CoaT surrogate {model_name!r}: not a model of this table (serial 224 x 224 models only)" + served)
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]})" + served)
+    widths, depths, ratios = COAT_MODELS[model_name]
+    return CoatSpec(model_name, 224, widths, depths, ratios)
+
+
+def coat_tiny_twin(model_name: str = "coat_lite_tiny", in_hw=(64, 64)) -> CoatSpec:
+    """The same topology at test size, by frame size (every served name maps to the same twins).  Not rows of `COAT_MODELS`.
+      64 x 64: "coat_test" -- grids 16 -> 8 -> 4 -> 2 (the 7 x 7 window on a 2 x 2 plane), 8 heads, windows 2 / 3 / 3, widths
+        32 / 32 / 64 / 96 (head widths 4 / 4 / 8 / 12), depths 2 / 1 / 2 / 1
+      96 x 96: "coat_test_96" -- grids 24 -> 12 -> 6 -> 3 (an odd last grid), 4 heads, windows 1 / 2 / 1, widths 48 / 48 / 80 / 160 (no
+        doublings; head widths 12 / 12 / 20 / 40, ragged against the MFMA's chunk of 16), depths 1 / 2 / 1 / 2
+      224 x 224 (the size the attack classes probe a builder with): "coat_test_224" -- 3137 tokens in stage 0, widths 32 / 64 / 64 / 96,
+        depths 1 / 1 / 1 / 1"""
+    if in_hw[0] != in_hw[1] or int(in_hw[0]) not in (64, 96, 224):
+        raise ValueError(f"the test-size CoaTs take 64 x 64, 96 x 96 or 224 x 224 frames (got {tuple(in_hw)})")
+    side = int(in_hw[0])
+    if side == 64:
+        return CoatSpec("coat_test", 64, (32, 32, 64, 96), (2, 1, 2, 1), (8, 8, 4, 4), 8, (2, 3, 3))
+    if side == 96:
+        return CoatSpec("coat_test_96", 96, (48, 48, 80, 160), (1, 2, 1, 2), (8, 8, 4, 4), 4, (1, 2, 1))
+    return CoatSpec("coat_test_224", 224, (32, 64, 64, 96), (1, 1, 1, 1), (8, 8, 4, 4), 8, (2, 3, 3))
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -2886,6 +3090,8 @@ def build_surrogate(model_name: str, in_hw=(224, 224)):
     there a `pit_*` name is an unknown name, as in the reference -- so a family is added here without changing what `build` answers."""
     if is_pit_name(model_name):
         return pit_named(model_name, in_hw)
+    if is_coat_name(model_name):            # (timm's CoaT-Lite: factorized attention, `coat_named`)
+        return coat_named(model_name, in_hw)
     return build(model_name, in_hw)
 
 
@@ -2936,4 +3142,7 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
     if is_pit_name(model_name):
         pit_named(model_name)               # (a name outside the table is refused with the served names)
         return pit_tiny_twin(model_name, in_hw)
+    if is_coat_name(model_name):
+        coat_named(model_name)              # (a name outside the table is refused with the served names)
+        return coat_tiny_twin(model_name, in_hw)
     return build(model_name, in_hw)

@@ -314,6 +314,26 @@ _PIT_PROTOS = {
 PIT_EXPORTS = tuple(_PIT_PROTOS)
 
 
+class CoatConfig(C.Structure):
+    _fields_ = ([("img", C.c_int32), ("in_chans", C.c_int32), ("dims", C.c_int32 * 4), ("heads", C.c_int32), ("depths", C.c_int32 * 4),
+                 ("mlp_ratios", C.c_int32 * 4)] + [(n, C.c_int32) for n in ("win3", "win5", "win7")] + [("ln_eps", C.c_float)])
+
+
+# The CoaT-Lite surrogates (`include/i2v_coat.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it:
+# the planner runs there on scalar restatements, and so do the kernel entries on their own -- factorized attention forward and backward,
+# the per-channel-window depthwise convolution pair and the cell gather / scatter pair behind a class row.
+_COAT_PROTOS = {
+    **_net_protos("coat", CoatConfig),
+    "i2v_coat_factor_attention_f32": ([_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P], _I),
+    "i2v_coat_factor_attention_bwd_f32": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P], _I),
+    "i2v_coat_dwmix_f32": ([_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P], _I),
+    "i2v_coat_dwmix_bwd_f32": ([_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P], _I),
+    "i2v_coat_cell_gather_f32": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "i2v_coat_cell_scatter_f32": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+}
+COAT_EXPORTS = tuple(_COAT_PROTOS)
+
+
 class XfGemmDesc(C.Structure):
     _fields_ = ([("A", _P)] + [(n, _L) for n in ("a_bo", "a_bi", "a_sm", "a_sk")] + [("B", _P)] + [(n, _L) for n in ("b_bo", "b_bi", "b_sk", "b_sn")]
                 + [("C", _P)] + [(n, _L) for n in ("c_bo", "c_bi", "c_sm")] + [(n, _P) for n in ("bias", "R", "C2", "H")]
@@ -361,7 +381,7 @@ NL_EXPORTS = tuple(_NL_PROTOS)
 
 # The transformer families by the word in their entry names (`i2v_<word>_*`)
 FAMILY_PROTOS = {"vit": _VIT_PROTOS, "swin": _SWIN_PROTOS, "convnext": _CONVNEXT_PROTOS, "mixer": _MIXER_PROTOS, "cait": _CAIT_PROTOS,
-                 "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS, "pit": _PIT_PROTOS}
+                 "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS, "pit": _PIT_PROTOS, "coat": _COAT_PROTOS}
 
 
 def bind(cdll, protos=_PROTOS):

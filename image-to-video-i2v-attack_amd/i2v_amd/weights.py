@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import BeitSpec, CaitSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
+from .graphs import BeitSpec, CaitSpec, CoatSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -292,6 +292,39 @@ def _pit_synthetic(spec: PitSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _coat_synthetic(spec: CoatSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained CoaT-Lite, drawn per key as `_pit_synthetic` draws: Linears and the patch convolutions ~ fan_in^-0.5
+    N(0, 1) (`factoratt_crpe.proj` and `mlp.fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1).  What is new must
+    show in the tests: the class tokens are N(0, 1) and the filters of `cpe` and `crpe` N(0, 1) / window over their window^2 taps, so
+    that each window moves the features."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k.startswith("cls_token"):
+            sd[k] = torch.randn(*shp, generator=g)
+        elif k.startswith(("cpe", "crpe")) and k.endswith("weight"):
+            sd[k] = torch.randn(*shp, generator=g) / shp[-1]
+        elif k.endswith(("norm1.weight", "norm2.weight", "norm.weight")):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if k.endswith(("fc2.weight", "factoratt_crpe.proj.weight")) else 1.0) * fan_in ** -0.5)
+    return sd
+
+
+def check_coat_duplicates(spec: CoatSpec, sd, where: str) -> None:
+    """timm registers a stage's shared `cpe` and `crpe` again inside every serial block, so its checkpoints carry them under block-level
+    keys too.  The stage-level keys are the ones loaded; a block-level duplicate that differs describes another model: refused by key
+    name.  An absent one is fine."""
+    for dup, key in spec.shared_duplicates().items():
+        if dup in sd and not (tuple(sd[dup].shape) == tuple(sd[key].shape) and torch.equal(sd[dup].float(), sd[key].float())):
+            raise ValueError(f"{where}: {dup} differs from the stage's shared {key}")
+
+
 def check_beit_buffers(spec: BeitSpec, sd, where: str) -> None:
     """timm's BEiT checkpoints carry the buffer `attn.relative_position_index` per block; it is computed from the geometry here and
     never loaded, so one that differs describes another model: refused by key name.  An absent one is fine."""
@@ -353,6 +386,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _beit_synthetic(graph, seed)
     if isinstance(graph, PitSpec):
         return _pit_synthetic(graph, seed)
+    if isinstance(graph, CoatSpec):
+        return _coat_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":
@@ -430,6 +465,8 @@ def load_state_dict(graph: Graph, seed=None, keep_head: bool = False) -> Dict[st
             check_swin_buffers(graph, sd, path)
         if isinstance(graph, BeitSpec):
             check_beit_buffers(graph, sd, path)
+        if isinstance(graph, CoatSpec):
+            check_coat_duplicates(graph, sd, path)
         for k, shp in shapes.items():
             if tuple(sd[k].shape) != tuple(shp):
                 raise ValueError(f"{path}: {k} has shape {tuple(sd[k].shape)}, expected {shp}")

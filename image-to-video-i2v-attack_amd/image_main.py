@@ -52,7 +52,8 @@ def arg_parse(argv=None, ucf101=False):
                              + ", ".join(graphs.XCIT_MODELS) + "; and timm's Twins (PCPVT and SVT) at 224 x 224: "
                              + ", ".join(graphs.TWINS_MODELS) + "; and timm's BEiTs at 224 x 224 with patch 16: "
                              + ", ".join(graphs.BEIT_MODELS) + "; and timm's PiTs at 224 x 224: "
-                             + ", ".join(graphs.PIT_MODELS) + ")")
+                             + ", ".join(graphs.PIT_MODELS) + "; and timm's serial CoaT-Lites at 224 x 224: "
+                             + ", ".join(graphs.COAT_MODELS) + ")")
     # additions (not in the reference)
     parser.add_argument("--anno", type=str, default=os.environ.get("I2V_ANNO", ""),
                         help="sample list csv `path,gt_label,clip_index` (the reference's kinetics400_attack_samples.csv, utils.py:29); without it 400 synthetic names with labels 0..399 are used")
@@ -94,7 +95,8 @@ def arg_parse(argv=None, ucf101=False):
                                        (graphs.is_xcit_name, graphs.xcit_named, "blocks {}"),
                                        (graphs.is_twins_name, graphs.twins_named, "the last block of stages {}"),
                                        (graphs.is_beit_name, graphs.beit_named, "blocks {}"),
-                                       (graphs.is_pit_name, graphs.pit_named, "blocks {}, numbered across the stages")):
+                                       (graphs.is_pit_name, graphs.pit_named, "blocks {}, numbered across the stages"),
+                                       (graphs.is_coat_name, graphs.coat_named, "the last block of stages {}")):
             if not is_name(args.direction_image_model):
                 continue
             try:
