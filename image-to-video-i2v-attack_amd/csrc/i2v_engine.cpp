@@ -516,6 +516,7 @@ extern "C" size_t i2v_net_workspace_bytes(i2v_handle h, int net) {
 #include "i2v_beit.cpp"         // (... and the BEiT planner, on the same restatements and i2v_beit_host.h)
 #include "i2v_pit.cpp"          // (... and the PiT planner, on the same restatements and i2v_pit_host.h)
 #include "i2v_coat.cpp"         // (... and the CoaT planner, on the same restatements and i2v_coat_host.h)
+#include "i2v_tnt.cpp"          // (... and the TNT planner, on the same restatements, i2v_beit_host.h and i2v_tnt_host.h)
 #include "i2v_xf_api.cpp"       // (... and the restatements on their own, include/i2v_xf_launch.h)
 #undef fail
 #endif

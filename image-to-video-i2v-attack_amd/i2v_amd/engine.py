@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import BeitSpec, CaitSpec, CoatSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
+from .graphs import BeitSpec, CaitSpec, CoatSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TntSpec, TwinsSpec, VitSpec, XcitSpec
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -472,6 +472,48 @@ class Engine:
         Cn = rows.shape[1] // (s * s)
         dx = torch.empty(frames, prefix + grid * grid, Cn, dtype=torch.float32, device=rows.device) if into is None else into
         _lib.check(self.capi, self.capi.i2v_coat_cell_scatter_f32(_ptr(rows, self), frames, grid, Cn, s, prefix, int(into is not None),
+                                                                  _ptr(dx, self), self.stream()))
+        return dx
+
+    def build_tnt_net(self, spec: TntSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "TntNet":
+        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
+
+    def tnt_attention(self, qkv: torch.Tensor, heads: int, scale: float = None) -> torch.Tensor:
+        """Attention over many short sequences on its own (`i2v_tnt_attention_f32`): qkv (seqs, T, 3 heads dh), T up to 16, dh up to 16
+        (any width), up to 8 heads -> out (seqs, T, heads dh); `scale` defaults to dh^-0.5.  One launch, nothing kept."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        assert 3 * heads * dh == C3
+        out = torch.empty(n, T, heads * dh, dtype=torch.float32, device=qkv.device)
+        _lib.check(self.capi, self.capi.i2v_tnt_attention_f32(_ptr(qkv, self), n, T, heads, dh, dh ** -0.5 if scale is None else scale,
+                                                              _ptr(out, self), self.stream()))
+        return out
+
+    def tnt_attention_bwd(self, qkv: torch.Tensor, dout: torch.Tensor, heads: int, scale: float = None) -> torch.Tensor:
+        """The input gradient of that launch (`i2v_tnt_attention_bwd_f32`) from qkv and dout alone: dqkv as qkv.  One launch."""
+        n, T, C3 = qkv.shape
+        dh = C3 // (3 * heads)
+        dqkv = torch.empty_like(qkv)
+        _lib.check(self.capi, self.capi.i2v_tnt_attention_bwd_f32(_ptr(qkv, self), _ptr(dout, self), n, T, heads, dh,
+                                                                  dh ** -0.5 if scale is None else scale, _ptr(dqkv, self), self.stream()))
+        return dqkv
+
+    def tnt_attention_group(self, T: int, heads: int, dh: int) -> int:
+        """Sequences one workgroup of the two launches owns for this shape (`i2v_tnt_attention_group`)."""
+        return int(self.capi.i2v_tnt_attention_group(T, heads, dh))
+
+    def tnt_pixel_gather(self, x: torch.Tensor) -> torch.Tensor:
+        """The rows of TNT's 7 x 7, stride 4, padding 3 pixel convolution (`i2v_tnt_pixel_gather_f32`): x (frames, C, side, side), side a
+        multiple of 16 -> rows (frames (side / 16)^2 16, C 49 rounded up to 4) in (patch, pixel) order."""
+        n, Cn, side, _ = x.shape
+        rows = torch.empty(n * (side // 4) ** 2, (Cn * 49 + 3) // 4 * 4, dtype=torch.float32, device=x.device)
+        _lib.check(self.capi, self.capi.i2v_tnt_pixel_gather_f32(_ptr(x, self), n, Cn, side, _ptr(rows, self), self.stream()))
+        return rows
+
+    def tnt_pixel_scatter(self, rows: torch.Tensor, frames: int, in_chans: int, side: int, into: torch.Tensor = None) -> torch.Tensor:
+        """Its transpose (`i2v_tnt_pixel_scatter_f32`): rows -> dx (frames, C, side, side), written, or added to `into`."""
+        dx = torch.empty(frames, in_chans, side, side, dtype=torch.float32, device=rows.device) if into is None else into
+        _lib.check(self.capi, self.capi.i2v_tnt_pixel_scatter_f32(_ptr(rows, self), frames, in_chans, side, int(into is not None),
                                                                   _ptr(dx, self), self.stream()))
         return dx
 
@@ -1135,6 +1177,12 @@ class CoatNet(TokenNet):
     _api = "coat"
 
 
+class TntNet(TokenNet):
+    """A TNT surrogate: a hook is the OUTER residual stream after a block, all tokens with the class token: ((1 + grid^2) * dim) floats
+    per frame.  Packed with qk and v stacked, the pixel filter padded to a multiple of 4 columns and `pixel_pos` pixel-major."""
+    _api = "tnt"
+
+
 def _three(v):
     return (C.c_int32 * 3)(*v)
 
@@ -1176,4 +1224,5 @@ TOKEN_FAMILIES = {
                                                s.ln_eps), _blocks),
     CoatSpec: (CoatNet, lambda s: _lib.CoatConfig(s.img, s.in_chans, _four(s.widths), s.heads, _four(s.depths), _four(s.mlp_ratios), *s.windows,
                                                   s.ln_eps), _stages),
+    TntSpec: (TntNet, lambda s: _lib.TntConfig(s.img, s.in_chans, s.dim, s.in_dim, s.heads, s.in_heads, s.mlp_ratio, s.blocks, s.ln_eps), _blocks),
 }

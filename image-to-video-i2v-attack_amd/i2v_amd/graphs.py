@@ -3027,6 +3027,184 @@ def coat_tiny_twin(model_name: str = "coat_lite_tiny", in_hw=(64, 64)) -> CoatSp
 
 
 # ---------------------------------------------------------------------------
+# the TNT surrogates (Transformer in Transformer): an inner transformer over the 16 pixel tokens of every patch feeding an outer ViT
+# over the patches, planned on the transformer stack (include/i2v_tnt.h)
+# ---------------------------------------------------------------------------
+#: timm 0.5.0's `TNT` models at 224 x 224 with patch 16: name -> (dim, in_dim, blocks, heads, in_heads); MLP ratio 4 on both levels
+TNT_MODELS: Dict[str, Tuple[int, int, int, int, int]] = {
+    "tnt_s_patch16_224": (384, 24, 12, 6, 4),
+    "tnt_b_patch16_224": (640, 40, 12, 10, 4),
+}
+
+
+@dataclass
+class TntSpec:
+    """timm 0.5.0 `TNT` up to its last block (restated from memory of tnt.py, UNCHECKED against timm).
+    `pixel_embed.proj`, a Conv2d(3, in_dim, 7, stride 4, padding 3), gives img / 4 positions a side; the 4 x 4 cell of patch
+    n = g py + px is its 16 pixel tokens, p = 4 i + j at conv output (4 py + i, 4 px + j); `pixel_pos` (1, in_dim, 4, 4) is added per
+    (c, i, j): the inner stream (frames g^2, 16, in_dim).  patch = norm2_proj(proj(norm1_proj(inner as (frames, g^2, 16 in_dim)))), the
+    columns ordered p in_dim + c; `cls_token` in front, `patch_pos` (1, 1 + g^2, dim) added.  Block: inner += attn_in(norm_in inner);
+    inner += mlp_in(norm_mlp_in inner); outer[:, 1:] += proj(norm1_proj(inner) as (frames, g^2, 16 in_dim)), norm1_proj over in_dim;
+    outer += attn_out(norm_out outer); outer += mlp(norm_mlp outer).  An attention is `qk` = Linear(dim, 2 dim) without bias, columns
+    [q of head 0.. | k of head 0..], `v` = Linear(dim, dim) without bias, scale head_dim ** -0.5, `proj` with bias; LayerNorm eps
+    `ln_eps`, exact GELU.  `hooks`: depth d (1..4) -> zero-based block d * blocks / 4 - 1 (2, 5, 8, 11 of 12), whose OUTER stream behind
+    it, all tokens with the class token, is the hooked feature: tokens * dim floats per frame.  `norm` and `head` lie behind every hook."""
+    arch: str
+    img: int
+    dim: int = 384
+    in_dim: int = 24
+    blocks: int = 12
+    heads: int = 6
+    in_heads: int = 4
+    mlp_ratio: int = 4
+    in_chans: int = 3
+    ln_eps: float = 1e-5
+    hooks: Dict[int, int] = field(default_factory=dict)
+    video: bool = False
+
+    def __post_init__(self):
+        if self.img % 16 or self.tokens > 208:
+            raise ValueError(f"{self.arch}: a {self.img} x {self.img} frame must be whole 16 x 16 patches and at most 208 tokens with the class token")
+        if self.in_dim % self.in_heads or self.in_dim % 4 or self.in_dim // self.in_heads > 16 or self.in_heads > 8:
+            raise ValueError(f"{self.arch}: inner width {self.in_dim} under {self.in_heads} heads: a multiple of 4, up to 8 heads up to 16 wide")
+        if self.dim % self.heads or (self.dim // self.heads) % 4 or self.dim // self.heads > 64:
+            raise ValueError(f"{self.arch}: width {self.dim} under {self.heads} heads: the head width must be a multiple of 4 up to 64")
+        if self.blocks % 4:
+            raise ValueError(f"{self.arch}: {self.blocks} blocks: the hooks sit at every quarter of the stack")
+        if not self.hooks:
+            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
+
+    @property
+    def in_hw(self):
+        return (self.img, self.img)
+
+    @property
+    def grid(self) -> int:
+        return self.img // 16
+
+    @property
+    def tokens(self) -> int:
+        return 1 + self.grid ** 2
+
+    @property
+    def pixel_cols(self) -> int:
+        """Columns of a row of the pixel gather: in_chans * 49 rounded up to a multiple of 4."""
+        return (self.in_chans * 49 + 3) // 4 * 4
+
+    @property
+    def hook_dim(self) -> int:
+        """Floats per frame of a hooked feature."""
+        return self.tokens * self.dim
+
+    def hook_for(self, depth: int, whole_module: bool = False) -> int:
+        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
+        if depth not in self.hooks:
+            raise KeyError(depth)
+        return self.hooks[depth]
+
+    def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """timm `state_dict` key -> shape for every parameter up to the last block."""
+        D, d, T, r = self.dim, self.in_dim, self.tokens, self.mlp_ratio
+        out = {"cls_token": (1, 1, D), "patch_pos": (1, T, D), "pixel_pos": (1, d, 4, 4), "pixel_embed.proj.weight": (d, self.in_chans, 7, 7),
+               "pixel_embed.proj.bias": (d,), "norm1_proj.weight": (16 * d,), "norm1_proj.bias": (16 * d,), "proj.weight": (D, 16 * d),
+               "proj.bias": (D,), "norm2_proj.weight": (D,), "norm2_proj.bias": (D,)}
+        for i in range(self.blocks):
+            p = f"blocks.{i}."
+            for outer, (w, nrm, att, nm, mlp) in enumerate(((d, "norm_in", "attn_in", "norm_mlp_in", "mlp_in"), (D, "norm_out", "attn_out", "norm_mlp", "mlp"))):
+                if outer:
+                    out.update({p + "norm1_proj.weight": (d,), p + "norm1_proj.bias": (d,), p + "proj.weight": (D, 16 * d), p + "proj.bias": (D,)})
+                out.update({p + nrm + ".weight": (w,), p + nrm + ".bias": (w,), p + att + ".qk.weight": (2 * w, w), p + att + ".v.weight": (w, w),
+                            p + att + ".proj.weight": (w, w), p + att + ".proj.bias": (w,), p + nm + ".weight": (w,), p + nm + ".bias": (w,),
+                            p + mlp + ".fc1.weight": (r * w, w), p + mlp + ".fc1.bias": (r * w,), p + mlp + ".fc2.weight": (w, r * w),
+                            p + mlp + ".fc2.bias": (w,)})
+        return out
+
+    def native_arrays(self, sd, n_blocks: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_tnt_create` takes for the first `n_blocks` blocks, from a timm-layout state dict, as float32 host tensors:
+        11 in front -- the pixel filter as (in_dim, in_chans 49) rows padded with zeros to `pixel_cols`, its bias, `pixel_pos` as
+        (16, in_dim) with row 4 i + j, the patch embedding's norm1_proj, proj and norm2_proj, `cls_token` as (dim), `patch_pos` as
+        (tokens, dim) -- then 28 per block: the inner half as the shared block's 12 (qk.weight stacked on v.weight as the qkv weight,
+        a qkv bias of zeros), the step's norm1_proj and proj, the outer half's 12."""
+        import torch
+        f32 = lambda k: sd[k].detach().float().cpu().contiguous()      # noqa: E731
+        d, D = self.in_dim, self.dim
+        pw = torch.zeros(d, self.pixel_cols)
+        pw[:, :self.in_chans * 49] = f32("pixel_embed.proj.weight").reshape(d, -1)
+        out = [pw, f32("pixel_embed.proj.bias"), f32("pixel_pos").reshape(d, 16).t().contiguous(), f32("norm1_proj.weight"),
+               f32("norm1_proj.bias"), f32("proj.weight"), f32("proj.bias"), f32("norm2_proj.weight"), f32("norm2_proj.bias"),
+               f32("cls_token").reshape(D), f32("patch_pos").reshape(self.tokens, D)]
+        for i in range(n_blocks):
+            p = f"blocks.{i}."
+            for outer, (w, nrm, att, nm, mlp) in enumerate(((d, "norm_in", "attn_in", "norm_mlp_in", "mlp_in"), (D, "norm_out", "attn_out", "norm_mlp", "mlp"))):
+                if outer:
+                    out += [f32(p + "norm1_proj.weight"), f32(p + "norm1_proj.bias"), f32(p + "proj.weight"), f32(p + "proj.bias")]
+                out += [f32(p + nrm + ".weight"), f32(p + nrm + ".bias"), torch.cat([f32(p + att + ".qk.weight"), f32(p + att + ".v.weight")]).contiguous(),
+                        torch.zeros(3 * w), f32(p + att + ".proj.weight"), f32(p + att + ".proj.bias"), f32(p + nm + ".weight"), f32(p + nm + ".bias"),
+                        f32(p + mlp + ".fc1.weight"), f32(p + mlp + ".fc1.bias"), f32(p + mlp + ".fc2.weight"), f32(p + mlp + ".fc2.bias")]
+        return out
+
+    def macs_per_frame(self) -> int:
+        d, D, np_, T, r = self.in_dim, self.dim, self.grid ** 2, self.tokens, self.mlp_ratio
+        inner = np_ * 16 * (d * (4 * d + 2 * r * d) + 2 * 16 * d)
+        outer = T * D * (4 * D + 2 * r * D) + 2 * T * T * D
+        return np_ * 16 * d * self.in_chans * 49 + np_ * 16 * d * D + self.blocks * (inner + np_ * 16 * d * D + outer)
+
+    def workspace_bytes(self, hook_blocks: Sequence[int], frames: int) -> int:
+        """Device bytes `i2v_tnt_create` plans for these hooks and `frames` frames (the formula of csrc/i2v_tnt.cpp), with R the pixel
+        tokens: the 11 arrays in front and 28 per block run; per block both halves' input, qkv, mid stream, fc1 pre-activation and four
+        statistics per token, and two statistics per pixel token for the step; the two top streams, the patch embedding before its
+        LayerNorm with four statistics per patch; the shared scratch -- one stream, one MLP-wide and the qkv gradient at the larger of
+        the two levels, the two running gradients, the pixel rows --; per hook one gradient view, and for a hook that is not the deepest
+        a copy of its stream.  Nothing of either attention's score matrix."""
+        F, nb, d, D, r = frames, max(hook_blocks) + 1, self.in_dim, self.dim, self.mlp_ratio
+        np_, T, Kp = self.grid ** 2, self.tokens, self.pixel_cols
+        R, FT, FP, Mi, M = F * np_ * 16, F * T, F * np_, r * d, r * D
+        weights = d * Kp + d + 16 * d + 32 * d + D * 16 * d + 4 * D + T * D
+        weights += nb * (4 * d * d + 2 * Mi * d + 9 * d + Mi + 2 * d + D * 16 * d + D + 4 * D * D + 2 * M * D + 9 * D + M)
+        per_block = 5 * R * d + R * Mi + 4 * R + 2 * R + 5 * FT * D + FT * M + 4 * FT
+        mS, mM = max(R * d, FT * D), max(R * Mi, FT * M)
+        shared = R * d + FT * D + FP * D + 4 * FP + 4 * mS + mM + FT * D + R * d + R * Kp
+        hooks = sum(FT * D * (2 if b != nb - 1 else 1) for b in hook_blocks)
+        return 4 * (weights + nb * per_block + shared + hooks)
+
+
+def is_tnt_name(model_name: str) -> bool:
+    """A name of timm's TNT vocabulary (`tnt.py`), served (`TNT_MODELS`) or not: `graphs.build_surrogate` routes these to `tnt_named`,
+    which refuses the ones that are not offered with a message that lists the served names."""
+    return model_name.startswith("tnt")
+
+
+def tnt_named(model_name: str, in_hw=(224, 224)) -> TntSpec:
+    """Any row of `TNT_MODELS`, at 224 x 224 only.  Refused, each with the reason: names outside the table and every other input size."""
+    served = "; served: " + ", ".join(TNT_MODELS)
+    if model_name not in TNT_MODELS:
+        raise ValueError(f"TNT surrogate {model_name!r}: not a model of this table (timm 0.5.0's 224 x 224 models with patch 16 only)" + served)
+    if tuple(in_hw) != (224, 224):
+        raise ValueError(f"{model_name} takes 224 x 224 frames only (got {tuple(in_hw)[0]} x {tuple(in_hw)[1]}): its position tables are "
+                         "those of the 14 x 14 grid" + served)
+    dim, in_dim, blocks, heads, in_heads = TNT_MODELS[model_name]
+    return TntSpec(model_name, 224, dim, in_dim, blocks, heads, in_heads)
+
+
+def tnt_tiny_twin(model_name: str = "tnt_s_patch16_224", in_hw=(64, 64)) -> TntSpec:
+    """The same topology at test size, by frame size (every served name maps to the same twins).  Not rows of `TNT_MODELS`.  All have 4
+    blocks, so that depths 1..4 hook every block.
+      64 x 64: "tnt_test" -- grid 4, 17 outer tokens, 256 inner sequences a frame; in_dim 24 under 4 heads of width 6 (tnt_s's inner
+        shape), dim 32 under 2 heads of width 16
+      48 x 48: "tnt_test_48" -- grid 3 (odd), 10 outer tokens; in_dim 40 under 4 heads of width 10 (tnt_b's inner shape), dim 48 under
+        4 heads of width 12
+      224 x 224 (the size the attack classes probe a builder with): "tnt_test_224" -- 197 outer tokens, in_dim 24, dim 32 under 1 head"""
+    if in_hw[0] != in_hw[1] or int(in_hw[0]) not in (64, 48, 224):
+        raise ValueError(f"the test-size TNTs take 64 x 64, 48 x 48 or 224 x 224 frames (got {tuple(in_hw)})")
+    side = int(in_hw[0])
+    if side == 64:
+        return TntSpec("tnt_test", 64, 32, 24, 4, 2, 4)
+    if side == 48:
+        return TntSpec("tnt_test_48", 48, 48, 40, 4, 4, 4)
+    return TntSpec("tnt_test_224", 224, 32, 24, 4, 1, 4)
+
+
+# ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
 def build(model_name: str, in_hw=(224, 224)) -> Graph:
@@ -3086,12 +3264,14 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
 
 def build_surrogate(model_name: str, in_hw=(224, 224)):
     """The name resolver of the image-guided attack classes and the command line: `build`, with timm's PiT family in front (three
-    stages pooled by a depthwise convolution, overlapping patches: `pit_named`).  `build` itself keeps its vocabulary as it stands --
+    stages pooled by a depthwise convolution, overlapping patches: `pit_named`), CoaT-Lite and TNT next to it.  `build` itself keeps its vocabulary as it stands --
     there a `pit_*` name is an unknown name, as in the reference -- so a family is added here without changing what `build` answers."""
     if is_pit_name(model_name):
         return pit_named(model_name, in_hw)
     if is_coat_name(model_name):            # (timm's CoaT-Lite: factorized attention, `coat_named`)
         return coat_named(model_name, in_hw)
+    if is_tnt_name(model_name):             # (timm's TNT: an inner transformer over every patch's pixels, `tnt_named`)
+        return tnt_named(model_name, in_hw)
     return build(model_name, in_hw)
 
 
@@ -3145,4 +3325,7 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
     if is_coat_name(model_name):
         coat_named(model_name)              # (a name outside the table is refused with the served names)
         return coat_tiny_twin(model_name, in_hw)
+    if is_tnt_name(model_name):
+        tnt_named(model_name)               # (a name outside the table is refused with the served names)
+        return tnt_tiny_twin(model_name, in_hw)
     return build(model_name, in_hw)

@@ -334,6 +334,24 @@ _COAT_PROTOS = {
 COAT_EXPORTS = tuple(_COAT_PROTOS)
 
 
+class TntConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("img", "in_chans", "dim", "in_dim", "heads", "in_heads", "mlp_ratio", "blocks")] + [("ln_eps", C.c_float)]
+
+
+# The TNT surrogates (`include/i2v_tnt.h`): a header of its own, kept apart from EXPORTS.  The host simulation exports all of it: the
+# planner runs there on scalar restatements, and so do the kernel entries on their own -- the batched short-sequence attention forward
+# and backward, the workgroup's share of sequences, and the pixel gather / scatter pair.
+_TNT_PROTOS = {
+    **_net_protos("tnt", TntConfig),
+    "i2v_tnt_attention_f32": ([_P, _L, _I, _I, _I, _F, _P, _P], _I),
+    "i2v_tnt_attention_bwd_f32": ([_P, _P, _L, _I, _I, _I, _F, _P, _P], _I),
+    "i2v_tnt_attention_group": ([_I, _I, _I], _I),
+    "i2v_tnt_pixel_gather_f32": ([_P, _I, _I, _I, _P, _P], _I),
+    "i2v_tnt_pixel_scatter_f32": ([_P, _I, _I, _I, _I, _P, _P], _I),
+}
+TNT_EXPORTS = tuple(_TNT_PROTOS)
+
+
 class XfGemmDesc(C.Structure):
     _fields_ = ([("A", _P)] + [(n, _L) for n in ("a_bo", "a_bi", "a_sm", "a_sk")] + [("B", _P)] + [(n, _L) for n in ("b_bo", "b_bi", "b_sk", "b_sn")]
                 + [("C", _P)] + [(n, _L) for n in ("c_bo", "c_bi", "c_sm")] + [(n, _P) for n in ("bias", "R", "C2", "H")]
@@ -381,7 +399,8 @@ NL_EXPORTS = tuple(_NL_PROTOS)
 
 # The transformer families by the word in their entry names (`i2v_<word>_*`)
 FAMILY_PROTOS = {"vit": _VIT_PROTOS, "swin": _SWIN_PROTOS, "convnext": _CONVNEXT_PROTOS, "mixer": _MIXER_PROTOS, "cait": _CAIT_PROTOS,
-                 "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS, "pit": _PIT_PROTOS, "coat": _COAT_PROTOS}
+                 "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS, "pit": _PIT_PROTOS, "coat": _COAT_PROTOS,
+                 "tnt": _TNT_PROTOS}
 
 
 def bind(cdll, protos=_PROTOS):

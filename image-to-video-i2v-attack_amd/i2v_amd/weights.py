@@ -14,7 +14,7 @@ from typing import Dict
 
 import torch
 
-from .graphs import BeitSpec, CaitSpec, CoatSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TwinsSpec, VitSpec, XcitSpec
+from .graphs import BeitSpec, CaitSpec, CoatSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TntSpec, TwinsSpec, VitSpec, XcitSpec
 
 BN_EPS = 1e-5   # torchvision BatchNorm2d default, used by every ResNet BN
 
@@ -316,6 +316,31 @@ def _coat_synthetic(spec: CoatSpec, seed: int) -> Dict[str, torch.Tensor]:
     return sd
 
 
+def _tnt_synthetic(spec: TntSpec, seed: int) -> Dict[str, torch.Tensor]:
+    """Seeded stand-in for a trained TNT, drawn per key as `_coat_synthetic` draws: Linears and the pixel convolution ~ fan_in^-0.5
+    N(0, 1) (every attention's `proj`, the step's `proj` and every `fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases
+    0.02 N(0, 1).  What is new must show in the tests: `cls_token` is N(0, 1) and the two position tables 0.5 N(0, 1), so that the
+    pixel order inside a patch moves the features."""
+    sd = {}
+    for k, shp in spec.param_shapes().items():
+        g = _gen(seed, k)
+        if k == "cls_token":
+            sd[k] = torch.randn(*shp, generator=g)
+        elif k in ("patch_pos", "pixel_pos"):
+            sd[k] = 0.5 * torch.randn(*shp, generator=g)
+        elif "norm" in k and k.endswith("weight"):
+            sd[k] = 1.0 + 0.1 * torch.randn(*shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.02 * torch.randn(*shp, generator=g)
+        else:
+            fan_in = 1
+            for v in shp[1:]:
+                fan_in *= v
+            half = k.endswith(("fc2.weight", "proj.weight")) and not k.startswith("pixel_embed")
+            sd[k] = torch.randn(*shp, generator=g) * ((0.5 if half else 1.0) * fan_in ** -0.5)
+    return sd
+
+
 def check_coat_duplicates(spec: CoatSpec, sd, where: str) -> None:
     """timm registers a stage's shared `cpe` and `crpe` again inside every serial block, so its checkpoints carry them under block-level
     keys too.  The stage-level keys are the ones loaded; a block-level duplicate that differs describes another model: refused by key
@@ -388,6 +413,8 @@ def synthetic_state_dict(graph: Graph, seed: int = 0) -> Dict[str, torch.Tensor]
         return _pit_synthetic(graph, seed)
     if isinstance(graph, CoatSpec):
         return _coat_synthetic(graph, seed)
+    if isinstance(graph, TntSpec):
+        return _tnt_synthetic(graph, seed)
     sd = {}
     for nd in graph.nodes:
         if nd.op == "se":

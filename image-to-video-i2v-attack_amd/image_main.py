@@ -53,7 +53,8 @@ def arg_parse(argv=None, ucf101=False):
                              + ", ".join(graphs.TWINS_MODELS) + "; and timm's BEiTs at 224 x 224 with patch 16: "
                              + ", ".join(graphs.BEIT_MODELS) + "; and timm's PiTs at 224 x 224: "
                              + ", ".join(graphs.PIT_MODELS) + "; and timm's serial CoaT-Lites at 224 x 224: "
-                             + ", ".join(graphs.COAT_MODELS) + ")")
+                             + ", ".join(graphs.COAT_MODELS) + "; and timm's TNTs at 224 x 224: "
+                             + ", ".join(graphs.TNT_MODELS) + ")")
     # additions (not in the reference)
     parser.add_argument("--anno", type=str, default=os.environ.get("I2V_ANNO", ""),
                         help="sample list csv `path,gt_label,clip_index` (the reference's kinetics400_attack_samples.csv, utils.py:29); without it 400 synthetic names with labels 0..399 are used")
@@ -96,7 +97,8 @@ def arg_parse(argv=None, ucf101=False):
                                        (graphs.is_twins_name, graphs.twins_named, "the last block of stages {}"),
                                        (graphs.is_beit_name, graphs.beit_named, "blocks {}"),
                                        (graphs.is_pit_name, graphs.pit_named, "blocks {}, numbered across the stages"),
-                                       (graphs.is_coat_name, graphs.coat_named, "the last block of stages {}")):
+                                       (graphs.is_coat_name, graphs.coat_named, "the last block of stages {}"),
+                                       (graphs.is_tnt_name, graphs.tnt_named, "the outer stream after blocks {}")):
             if not is_name(args.direction_image_model):
                 continue
             try:
