@@ -13,7 +13,7 @@ from typing import List, Sequence
 import torch
 
 from . import lib as _lib
-from .graphs import BeitSpec, CaitSpec, CoatSpec, ConvitSpec, ConvNextSpec, Graph, MixerSpec, PitSpec, SwinSpec, TntSpec, TwinsSpec, VitSpec, XcitSpec
+from .graphs import FAMILIES, FAMILY_OF, Graph
 from .weights import fold_affine, fold_pre_affine
 
 
@@ -40,7 +40,8 @@ def _hptr(t: torch.Tensor):
 
 class Engine:
     """One per (process, device) -- mirrors the reference's single `.cuda()` device
-    (`image_attacks.py:103`).  `capi` is injected only by the planner unit tests."""
+    (`image_attacks.py:103`).  `capi` is injected only by the planner unit tests.  The `build_<word>_net` methods of the transformer
+    families are set in the loop directly behind this class."""
 
     def __init__(self, device="cuda:0", capi=None):
         self.device = torch.device(device)
@@ -88,18 +89,9 @@ class Engine:
         return self._build(Net, graph, state_dict, list(hook_tensors), max_frames, relu_gain)
 
     def build_token_net(self, spec, state_dict, hooks: Sequence[int], max_frames: int) -> "TokenNet":
-        """A transformer surrogate of whichever family `spec` belongs to (`TOKEN_FAMILIES`; `include/i2v_<family>.h`): weights packed
-        and uploaded and the arena planned for up to `max_frames` frames.  The `build_<family>_net` methods are this call."""
-        return self._build(TOKEN_FAMILIES[type(spec)][0], spec, state_dict, list(hooks), max_frames)
-
-    def build_vit_net(self, spec: VitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "VitNet":
-        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
-
-    def build_swin_net(self, spec: SwinSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "SwinNet":
-        return self.build_token_net(spec, state_dict, hook_stages, max_frames)
-
-    def build_convnext_net(self, spec: ConvNextSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "ConvNextNet":
-        return self.build_token_net(spec, state_dict, hook_stages, max_frames)
+        """A transformer surrogate of whichever family `spec` belongs to (`graphs.FAMILIES`; `include/i2v_<word>.h`): weights packed
+        and uploaded and the arena planned for up to `max_frames` frames.  The `build_<word>_net` methods are this call."""
+        return self._build(TokenNet, spec, state_dict, list(hooks), max_frames)
 
     def convnext_dw(self, x: torch.Tensor, filt: torch.Tensor, bias=None, add=None) -> torch.Tensor:
         """The ConvNeXt block's depthwise 7 x 7 launch on its own (`i2v_convnext_dw_f32`): x (frames, H, W, C) token-major, filt (49, C),
@@ -111,9 +103,6 @@ class Engine:
                                                             _ptr(add, self) if add is not None else None, _ptr(y, self), n, H, W, Cn,
                                                             self.stream()))
         return y
-
-    def build_mixer_net(self, spec: MixerSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "MixerNet":
-        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def mixer_tokens(self, z: torch.Tensor, residual: torch.Tensor, w1, b1, w2=None, b2=None, in_scale=None, in_shift=None, out_scale=None,
                      channel_tile: int = 0) -> torch.Tensor:
@@ -145,9 +134,6 @@ class Engine:
                                                                  o(in_scale), o(in_shift), o(out_scale), channel_tile, self.stream()))
         return dz
 
-    def build_cait_net(self, spec: CaitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "CaitNet":
-        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
-
     def cait_attention(self, qkv: torch.Tensor, heads: int, scale: float, wl, bl, ww, bw):
         """Talking-heads attention on its own (`i2v_cait_attention_f32`): qkv (frames, T, 3 heads dh) as the ViT entry takes it, wl / ww
         (heads, heads), bl / bw (heads) -> (out (frames, T, heads dh), probs (frames, heads, T, ld): post-softmax, pre-mix)."""
@@ -172,9 +158,6 @@ class Engine:
                                                                    _ptr(wl, self), _ptr(ww, self), _ptr(bw, self), _ptr(ds, self), _ptr(pm, self),
                                                                    _ptr(dqkv, self), self.stream()))
         return dqkv
-
-    def build_convit_net(self, spec: ConvitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "ConvitNet":
-        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def convit_attention(self, qkv: torch.Tensor, heads: int, scale: float, c=None, table=None):
         """Gated positional attention on its own (`i2v_convit_attention_f32`): qkv (frames, T, 3 heads dh) as the ViT entry takes it, c
@@ -203,9 +186,6 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_convit_attention_bwd_f32(_ptr(qkv, self), _ptr(probs, self), _ptr(dout, self), n, T, heads, dh, scale,
                                                                      o(c), o(table), _ptr(ds, self), _ptr(dqkv, self), self.stream()))
         return dqkv
-
-    def build_xcit_net(self, spec: XcitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "XcitNet":
-        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def xcit_attention(self, qkv: torch.Tensor, heads: int, temperature: torch.Tensor):
         """Cross-covariance attention on its own (`i2v_xcit_attention_f32`): qkv (frames, T, 3 heads dh) as the ViT entry takes it,
@@ -257,9 +237,6 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_xcit_stem_scatter_f32(_ptr(drows, self), None if pre is None else _ptr(pre, self), _ptr(dst, self),
                                                                   n, H, W, Cn, int(nchw), int(into is not None), self.stream()))
         return dst
-
-    def build_twins_net(self, spec: TwinsSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "TwinsNet":
-        return self.build_token_net(spec, state_dict, hook_stages, max_frames)
 
     def twins_attention(self, q: torch.Tensor, kv: torch.Tensor, heads: int, scale: float = None) -> torch.Tensor:
         """Sub-sampled attention on its own (`i2v_twins_attention_f32`): q (frames, Tq, heads dh), kv (frames, Tk, 2 heads dh) ->
@@ -313,9 +290,6 @@ class Engine:
                                                                            _ptr(zeros, self), _ptr(dqkv, self), self.stream()))
         return dqkv
 
-    def build_beit_net(self, spec: BeitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "BeitNet":
-        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
-
     def beit_attention(self, qkv: torch.Tensor, bias, heads: int, scale: float = None) -> torch.Tensor:
         """Biased global attention on its own (`i2v_beit_attention_f32`): qkv (frames, T, 3 heads dh), bias (heads, T, T) or None ->
         out (frames, T, heads dh); `scale` defaults to dh^-0.5."""
@@ -343,9 +317,6 @@ class Engine:
         assert tuple(S.shape[1:]) == tuple(bias.shape)
         _lib.check(self.capi, self.capi.i2v_beit_bias_add_f32(_ptr(S, self), _ptr(bias, self), S.shape[0], bias.numel(), self.stream()))
         return S
-
-    def build_pit_net(self, spec: PitSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "PitNet":
-        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def pit_attention(self, qkv: torch.Tensor, heads: int, scale: float = None):
         """Streaming attention on its own (`i2v_pit_attention_f32`): qkv (frames, T, 3 heads dh), any T -> out (frames, T, heads dh) and the
@@ -405,9 +376,6 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_pit_patch_scatter_f32(_ptr(rows, self), frames, chans, side, p, s, int(into is not None), _ptr(g, self),
                                                                   self.stream()))
         return g
-
-    def build_coat_net(self, spec: CoatSpec, state_dict, hook_stages: Sequence[int], max_frames: int) -> "CoatNet":
-        return self.build_token_net(spec, state_dict, hook_stages, max_frames)
 
     def coat_attention(self, qkv: torch.Tensor, E: torch.Tensor, heads: int, scale: float = None):
         """Factorized attention on its own (`i2v_coat_factor_attention_f32`): qkv (frames, T, 3 heads dh), E (frames, T, heads dh), any T
@@ -474,9 +442,6 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_coat_cell_scatter_f32(_ptr(rows, self), frames, grid, Cn, s, prefix, int(into is not None),
                                                                   _ptr(dx, self), self.stream()))
         return dx
-
-    def build_tnt_net(self, spec: TntSpec, state_dict, hook_blocks: Sequence[int], max_frames: int) -> "TntNet":
-        return self.build_token_net(spec, state_dict, hook_blocks, max_frames)
 
     def tnt_attention(self, qkv: torch.Tensor, heads: int, scale: float = None) -> torch.Tensor:
         """Attention over many short sequences on its own (`i2v_tnt_attention_f32`): qkv (seqs, T, 3 heads dh), T up to 16, dh up to 16
@@ -727,6 +692,12 @@ class Engine:
     def aens_reduce(self, cos, coeffs, feat_sum, weighted):
         L, n = cos.shape
         _lib.check(self.capi, self.capi.i2v_aens_reduce_f32(_ptr(cos, self), _ptr(coeffs, self), L, n, _ptr(feat_sum, self), _ptr(weighted, self), self.stream()))
+
+
+# `Engine.build_vit_net`, `build_swin_net`, `build_convnext_net`, `build_mixer_net`, `build_cait_net`, `build_convit_net`, `build_xcit_net`,
+# `build_twins_net`, `build_beit_net`, `build_pit_net`, `build_coat_net`, `build_tnt_net`: `build_token_net` under the family's name
+for _fam in FAMILIES:
+    setattr(Engine, f"build_{_fam.word}_net", Engine.build_token_net)
 
 
 class HookInfo:
@@ -1013,15 +984,30 @@ class Net:
         return max(self.eng.capi.i2v_cossim_scratch_bytes(hi.D, frames) for hi in self.hooks)
 
 
+def token_config(spec):
+    """The ctypes config of a transformer surrogate: the struct its family's create entry takes (`lib.family_config`), filled from
+    `spec.config_values()` in the struct's order, a sequence padded with zeros to the length of its array field."""
+    word = FAMILY_OF[type(spec)].word
+    struct = _lib.family_config(word)
+    values = list(spec.config_values())
+    assert len(values) == len(struct._fields_), (word, len(values))
+    for i, (_, ctype) in enumerate(struct._fields_):
+        if issubclass(ctype, C.Array):
+            v = list(values[i])
+            values[i] = ctype(*(v + [0] * (ctype._length_ - len(v))))
+    return struct(*values)
+
+
 class TokenNet(Net):
     """A transformer surrogate behind the `Net` interface the attack loop uses (`forward`, `backward`, `save_hook`, `cossim`, `stdloss`,
     `scratch_bytes`, `hooks`): a hook is a residual stream of `hook_shape(i)[0]` tokens, `hook_shape(i)[1]` wide; the loss kernels are
-    the ones every backbone uses.  A family is a row of `TOKEN_FAMILIES`: its subclass sets `_api` (its C entries are `i2v_<_api>_*`),
-    its config builder makes the ctypes config from the spec; the weights come packed from `spec.native_arrays(sd, depth)`."""
-    _api = None
+    the ones every backbone uses.  The family is the spec's row of `graphs.FAMILIES`: its word names the C entries (`i2v_<word>_*`), the
+    spec gives the values of the ctypes config (`token_config`) and the weights packed in the family's native order
+    (`spec.native_arrays(sd, depth)`, `include/i2v_<word>.h`)."""
 
     def __init__(self, eng: Engine, spec, sd, hooks: List[int], max_frames: int):
         self.eng, self.graph, self.max_frames, self.id = eng, spec, max_frames, None
+        self._api = FAMILY_OF[type(spec)].word
         self.hook_tensors = list(hooks)
         self.h = self._create(spec, sd, self.hook_tensors, max_frames)
         self.hooks = []
@@ -1037,17 +1023,12 @@ class TokenNet(Net):
     def _c(self, name):
         return getattr(self.eng.capi, f"i2v_{self._api}_{name}")
 
-    def _weights(self, spec, sd, depth):
-        """The host arrays in the family's native order (`include/i2v_<_api>.h`), for blocks / stages 0 .. depth - 1."""
-        return spec.native_arrays(sd, depth)
-
-    def _create(self, spec, sd, hooks, max_frames, *extra):
-        """`extra`: arguments of the create entry between the config and the weight pointers (ViT's prefix count)."""
-        _, config, units = TOKEN_FAMILIES[type(spec)]
-        depth = min(max(hooks) + 1, units(spec))       # (a hook outside the blocks / stages is the library's to refuse)
-        w = self._weights(spec, sd, depth)              # kept alive until the upload in the create entry
+    def _create(self, spec, sd, hooks, max_frames):
+        extra = spec.create_extra                       # (between the config and the weight pointers: ViT's prefix count)
+        depth = min(max(hooks) + 1, spec.units)         # (a hook outside the blocks / stages is the library's to refuse)
+        w = spec.native_arrays(sd, depth)               # kept alive until the upload in the create entry
         ptrs = (C.c_void_p * len(w))(*[t.data_ptr() for t in w])
-        cfg = config(spec)
+        cfg = token_config(spec)
         hk = (C.c_int32 * len(hooks))(*hooks)
         h = C.c_void_p()
         _lib.check(self.eng.capi, self._c("create" + ("_ex" if extra else ""))(self.eng.device.index or 0, C.byref(cfg), *extra, ptrs, len(w),
@@ -1055,13 +1036,8 @@ class TokenNet(Net):
         return h
 
     def hook_shape(self, i):
-        """(tokens, width, 1) of hook i: per block behind ConViT's join, per stage of a staged family, else the spec's own."""
-        spec, where = self.graph, self.hook_tensors[i]
-        if hasattr(spec, "tokens_at"):
-            return (spec.tokens_at(where), spec.dim, 1)
-        if callable(spec.tokens):
-            return (spec.tokens(where), spec.width(where), 1)
-        return (spec.tokens, spec.dim, 1)
+        """(tokens, width, 1) of hook i."""
+        return (*self.graph.hook_shape(self.hook_tensors[i]), 1)
 
     def close(self):
         if getattr(self, "h", None) and self.eng.h:
@@ -1092,137 +1068,3 @@ class TokenNet(Net):
     def hook_frames(self, i: int, in_frames: int) -> int:
         return in_frames
 
-
-class VitNet(TokenNet):
-    """The ViT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame."""
-    _api = "vit"
-
-    def _weights(self, spec: VitSpec, sd, nb):
-        # native order: patch weight, patch bias, the prefix tokens as one (n_prefix, dim) array (cls_token, then dist_token), pos_embed,
-        # then the blocks
-        prefix = torch.cat([sd[k].detach().float().cpu().reshape(1, spec.dim) for k in spec.prefix_keys], 0)
-        w = [sd[k].detach().float().cpu().contiguous() for k in ("patch_embed.proj.weight", "patch_embed.proj.bias")]
-        w += [prefix.contiguous(), sd["pos_embed"].detach().float().cpu().contiguous()]
-        return w + [sd[k].detach().float().cpu().contiguous() for i in range(nb) for k in spec.block_keys(i)]
-
-    def _create(self, spec: VitSpec, sd, hook_blocks, max_frames):
-        return super()._create(spec, sd, hook_blocks, max_frames, spec.n_prefix)      # i2v_vit_create_ex
-
-
-class SwinNet(TokenNet):
-    """A Swin surrogate: a hook is the stream after the last block of a stage, before that stage's patch merging, (grid^2 * width) floats
-    per frame."""
-    _api = "swin"
-
-    def _weights(self, spec: SwinSpec, sd, ns):
-        # native order (include/i2v_swin.h): the embedding, then per stage its blocks and the merging behind it
-        return [sd[k].detach().float().cpu().contiguous() for k in spec.native_keys(ns)]
-
-
-class ConvNextNet(TokenNet):
-    """A ConvNeXt surrogate: a hook is the stream after the last block of a stage, before the next stage's downsample, (plane^2 * width)
-    floats per frame, token-major.  Packed with the filters transposed, downsamples as Linears, gamma folded into fc2."""
-    _api = "convnext"
-
-
-class MixerNet(TokenNet):
-    """An MLP-Mixer / ResMLP surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame.  ResMLP is
-    packed with its folds made."""
-    _api = "mixer"
-
-
-class CaitNet(TokenNet):
-    """A CaiT surrogate: a hook is the residual stream after one self-attention block, (tokens * dim) floats per frame.  Packed with
-    gamma_1 / gamma_2 folded."""
-    _api = "cait"
-
-
-class ConvitNet(TokenNet):
-    """A ConViT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame before the class token joins
-    and ((tokens + 1) * dim) behind it.  Packed with qk and v stacked, the gate folded into one table and one vector per GPSA block."""
-    _api = "convit"
-
-
-class XcitNet(TokenNet):
-    """An XCiT surrogate: a hook is the residual stream after one block, (tokens * dim) floats per frame.  Packed with the BatchNorm
-    folded into the stem and the three LayerScales folded, 21 arrays per block."""
-    _api = "xcit"
-
-
-class TwinsNet(TokenNet):
-    """A Twins surrogate: a hook is the stream after the last block of a stage, before the next patch embedding, (grid^2 * width) floats
-    per frame.  Packed with the sr convolution in the block gather's column order and the position encoding's filter as (9, dim)."""
-    _api = "twins"
-
-
-class BeitNet(TokenNet):
-    """A BEiT surrogate: a hook is the residual stream after one block, all tokens with the class token, (tokens * dim) floats per
-    frame.  Packed with the qkv bias built, LayerScale folded and the position bias dense, 13 arrays per block."""
-    _api = "beit"
-
-
-class PitNet(TokenNet):
-    """A PiT surrogate: a hook is the residual stream after one block (flat index across the three stages), all tokens with the prefix
-    tokens, before any pooling: (tokens * width) floats per frame of the block's stage.  Packed with the position table token-major."""
-    _api = "pit"
-
-    def hook_shape(self, i):
-        return (*self.graph.hook_shape(self.hook_tensors[i]), 1)
-
-
-class CoatNet(TokenNet):
-    """A CoaT-Lite surrogate: a hook is the residual stream after the last block of a stage, all tokens with the class token, before the
-    next patch embedding: ((1 + grid^2) * width) floats per frame.  Packed with the filters tap-major and the later patch embeddings in
-    the cell gather's column order."""
-    _api = "coat"
-
-
-class TntNet(TokenNet):
-    """A TNT surrogate: a hook is the OUTER residual stream after a block, all tokens with the class token: ((1 + grid^2) * dim) floats
-    per frame.  Packed with qk and v stacked, the pixel filter padded to a multiple of 4 columns and `pixel_pos` pixel-major."""
-    _api = "tnt"
-
-
-def _three(v):
-    return (C.c_int32 * 3)(*v)
-
-
-def _four(v):
-    v = list(v)
-    return (C.c_int32 * 4)(*(v + [0] * (4 - len(v))))
-
-
-def _twins_config(s: TwinsSpec):
-    dims, heads, mlp, depths, sr = s.config_lists()
-    return _lib.TwinsConfig(s.img, s.in_chans, s.patch, s.stages, s.window, _four(dims), _four(heads), _four(mlp), _four(depths), _four(sr),
-                            s.ln_eps, s.pe_eps)
-
-
-def _blocks(s):
-    return s.blocks
-
-
-def _stages(s):
-    return s.stages
-
-
-# spec class -> (net class, ctypes config from the spec, how many blocks / stages the spec has)
-TOKEN_FAMILIES = {
-    VitSpec: (VitNet, lambda s: _lib.VitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
-    SwinSpec: (SwinNet, lambda s: _lib.SwinConfig(s.img, s.patch, s.in_chans, s.dim, s.window, s.stages, _four(s.depths), _four(s.heads),
-                                                  s.ln_eps), _stages),
-    ConvNextSpec: (ConvNextNet, lambda s: _lib.ConvNextConfig(s.img, s.patch, s.in_chans, s.dim, s.stages, _four(s.depths), s.ln_eps), _stages),
-    MixerSpec: (MixerNet, lambda s: _lib.MixerConfig(s.img, s.patch, s.in_chans, s.dim, s.blocks, s.tokens_hidden, s.mlp,
-                                                     1 if s.kind == "resmlp" else 0, s.ln_eps), _blocks),
-    CaitSpec: (CaitNet, lambda s: _lib.CaitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
-    ConvitSpec: (ConvitNet, lambda s: _lib.ConvitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.local_blocks, s.ln_eps),
-                 _blocks),
-    XcitSpec: (XcitNet, lambda s: _lib.XcitConfig(s.img, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
-    TwinsSpec: (TwinsNet, _twins_config, _stages),
-    BeitSpec: (BeitNet, lambda s: _lib.BeitConfig(s.img, s.patch, s.in_chans, s.dim, s.heads, s.mlp, s.blocks, s.ln_eps), _blocks),
-    PitSpec: (PitNet, lambda s: _lib.PitConfig(s.img, s.patch, s.stride, s.in_chans, s.prefix, _three(s.widths), _three(s.heads), _three(s.depths),
-                                               s.ln_eps), _blocks),
-    CoatSpec: (CoatNet, lambda s: _lib.CoatConfig(s.img, s.in_chans, _four(s.widths), s.heads, _four(s.depths), _four(s.mlp_ratios), *s.windows,
-                                                  s.ln_eps), _stages),
-    TntSpec: (TntNet, lambda s: _lib.TntConfig(s.img, s.in_chans, s.dim, s.in_dim, s.heads, s.in_heads, s.mlp_ratio, s.blocks, s.ln_eps), _blocks),
-}

@@ -22,6 +22,8 @@ checkpoint loads unchanged when one is supplied.
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
+from .family import clamped, clamped_tail, ends, Family, fan_in_tail, keys, normal, normal_over, signed_uniform, StagedSpec, starts, TokenSpec, uniform
+
 
 @dataclass
 class TensorSpec:
@@ -896,7 +898,7 @@ VIT_MODELS: Dict[str, Tuple[int, int, int, int, int, int]] = {
 
 
 @dataclass
-class VitSpec:
+class VitSpec(TokenSpec):
     """timm `VisionTransformer`: patch embedding (patch x patch convolution, stride patch, bias), `n_prefix`
     prefix tokens prepended (`cls_token`; with 2, `dist_token` of a distilled DeiT behind it), pos_embed added, then `blocks` pre-norm
     blocks x += proj(MHSA(LN1 x)); x += fc2(GELU(fc1(LN2 x))), LayerNorm eps `ln_eps`, exact GELU, scale (dim / heads) ** -0.5.
@@ -921,13 +923,9 @@ class VitSpec:
             raise ValueError(f"{self.arch}: {self.n_prefix} prefix tokens (1: cls_token, or 2: cls_token and dist_token)")
         if not self.hooks:
             if self.blocks % 4 == 0:
-                self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
+                self.hooks = self.quarter_hooks()
             else:
                 self.hooks = {d: 3 * d - 1 for d in (1, 2, 3, 4) if 3 * d - 1 < self.blocks}
-
-    @property
-    def in_hw(self):
-        return (self.img, self.img)
 
     @property
     def tokens(self) -> int:
@@ -937,12 +935,6 @@ class VitSpec:
     def prefix_keys(self) -> List[str]:
         """The state-dict keys of the prefix tokens, in sequence order."""
         return ["cls_token", "dist_token"][:self.n_prefix]
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def block_keys(self, i: int) -> List[str]:
         p = f"blocks.{i}."
@@ -960,6 +952,23 @@ class VitSpec:
             shapes = [(D,), (D,), (3 * D, D), (3 * D,), (D, D), (D,), (D,), (D,), (H, D), (H,), (D, H), (D,)]
             out.update(zip(self.block_keys(i), shapes))
         return out
+
+    def native_arrays(self, sd, n_blocks: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_vit_create_ex` takes for the first `n_blocks` blocks, as float32 host tensors: patch weight, patch bias, the
+        prefix tokens as one (n_prefix, dim) array (cls_token, then dist_token), pos_embed, then the blocks as they lie."""
+        import torch
+        f = lambda k: sd[k].detach().float().cpu()      # noqa: E731
+        prefix = torch.cat([f(k).reshape(1, self.dim) for k in self.prefix_keys], 0)
+        w = [f(k).contiguous() for k in ("patch_embed.proj.weight", "patch_embed.proj.bias")]
+        w += [prefix.contiguous(), f("pos_embed").contiguous()]
+        return w + [f(k).contiguous() for i in range(n_blocks) for k in self.block_keys(i)]
+
+    def config_values(self):
+        return (self.img, self.patch, self.in_chans, self.dim, self.heads, self.mlp, self.blocks, self.ln_eps)
+
+    @property
+    def create_extra(self):
+        return (self.n_prefix,)
 
     def macs_per_frame(self) -> int:
         T, D, H = self.tokens, self.dim, self.mlp
@@ -1022,6 +1031,22 @@ def vit_tiny(in_hw=(64, 64), n_prefix: int = 1, patch: int = 16) -> VitSpec:
     return VitSpec(arch, int(in_hw[0]), patch, 3, 64, 2, 256, 6, n_prefix=n_prefix)
 
 
+#: Seeded stand-in for a trained ViT, drawn per key like the CNN initialiser: truncated-normal-like (clamped at 2 std) matrices of std
+#: 0.02 as timm initialises them, except qkv at 0.05 so that the attention logits reach O(1) and the softmax is not uniform; LayerNorm
+#: gains near 1; small biases.  The residual stream stays O(1) through the 12 blocks (the tests check the hooks).
+VIT_SYNTHETIC = clamped_tail(ends("norm1.weight", "norm2.weight"), clamped(0.05))
+
+
+def _vit_twin(model_name: str, in_hw):
+    """One test-size twin per token layout: plain, distilled (2 prefix tokens), patch 32."""
+    patch, _, _, _, _, n_prefix = VIT_MODELS[model_name]
+    return vit_tiny(in_hw, n_prefix, patch)
+
+
+VIT_FAMILY = Family("vit", VitSpec, VIT_MODELS, is_vit_name, vit_named, _vit_twin, "timm's plain ViT / DeiT names at 224 x 224", "blocks {}", True,
+                VIT_SYNTHETIC)
+
+
 # ---------------------------------------------------------------------------
 # the Swin surrogates: hierarchical, windowed transformers, planned by a library entry of their own (include/i2v_swin.h)
 # ---------------------------------------------------------------------------
@@ -1035,7 +1060,7 @@ SWIN_MODELS: Dict[str, Tuple[int, Tuple[int, ...], Tuple[int, ...]]] = {
 
 
 @dataclass
-class SwinSpec:
+class SwinSpec(StagedSpec):
     """timm `SwinTransformer`: patch embedding (patch x patch convolution, stride patch, bias) and LayerNorm, no
     class token, no position embedding; stage i is `depths[i]` blocks at width dim * 2^i on a grid of (img / patch) / 2^i, with patch
     merging behind every stage but the last.  A block is x += proj(WMSA(LN1 x)); x += fc2(GELU(fc1(LN2 x))) with window attention
@@ -1069,10 +1094,6 @@ class SwinSpec:
             self.hooks = {d: d - 1 for d in range(1, self.stages + 1)}
 
     @property
-    def in_hw(self):
-        return (self.img, self.img)
-
-    @property
     def stages(self) -> int:
         return len(self.depths)
 
@@ -1097,12 +1118,6 @@ class SwinSpec:
     def n_index(self) -> int:
         return (2 * self.window - 1) ** 2
 
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based stage whose last block depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
-
     def block_keys(self, i: int, j: int) -> List[str]:
         p = f"layers.{i}.blocks.{j}."
         return [p + k for k in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.relative_position_bias_table",
@@ -1125,6 +1140,14 @@ class SwinSpec:
             if i + 1 < n_stages:
                 out += self.merge_keys(i)
         return out
+
+    def native_arrays(self, sd, n_stages: int) -> List["torch.Tensor"]:
+        """The arrays `i2v_swin_create` takes for the first `n_stages` stages, as they lie, as float32 host tensors (include/i2v_swin.h:
+        the embedding, then per stage its blocks and the merging behind it)."""
+        return [sd[k].detach().float().cpu().contiguous() for k in self.native_keys(n_stages)]
+
+    def config_values(self):
+        return (self.img, self.patch, self.in_chans, self.dim, self.window, self.stages, self.depths, self.heads, self.ln_eps)
 
     def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
         """timm `state_dict` key -> shape for every parameter up to the last block (the merging behind the last stage does not exist;
@@ -1221,6 +1244,38 @@ def swin_tiny(in_hw=(64, 64)) -> SwinSpec:
     return SwinSpec("swin_test", int(in_hw[0]), 4, 3, 16, 4, (2, 2), (1, 2))
 
 
+def check_swin_buffers(spec: SwinSpec, sd, where: str) -> None:
+    """timm's Swin checkpoints carry the buffers `relative_position_index` and `attn_mask`; they are computed from the geometry here
+    and never loaded, so one that differs describes another model: refused by key name."""
+    import torch
+    idx = spec.relative_position_index()
+    for i in range(spec.stages):
+        for j in range(spec.depths[i]):
+            p = f"layers.{i}.blocks.{j}."
+            k = p + "attn.relative_position_index"
+            if k in sd and not (tuple(sd[k].shape) == tuple(idx.shape) and torch.equal(sd[k].long(), idx)):
+                raise ValueError(f"{where}: buffer {k} differs from the index computed for window {spec.window}")
+            k = p + "attn_mask"
+            if k in sd and sd[k] is not None:
+                if spec.shift(i, j) == 0:
+                    raise ValueError(f"{where}: buffer {k} is a mask, but block {j} of stage {i} is not shifted")
+                want = spec.attn_mask(i)
+                if not (tuple(sd[k].shape) == tuple(want.shape) and torch.equal(sd[k].float(), want)):
+                    raise ValueError(f"{where}: buffer {k} differs from the mask computed for a {spec.grid(i)} x {spec.grid(i)} grid, "
+                                     f"window {spec.window}, shift {spec.shift(i, j)}")
+
+
+#: Seeded stand-in for a trained Swin, drawn per key: matrices of std 0.02 clamped at 2 std as timm initialises them, except qkv at
+#: width^-0.5, which puts the attention logits at O(1) at every stage's width (96 .. 1536), and the relative-position bias table at
+#: std 0.5, so that the bias visibly shapes the softmax; LayerNorm gains near 1; small biases.  Each block then adds a few tenths to a
+#: unit-variance stream, which stays O(1) through swin_small's 24 blocks (the tests check the hooks' spread).
+SWIN_SYNTHETIC = [(ends("relative_position_bias_table"), clamped(0.5)),
+                  *clamped_tail(ends("norm1.weight", "norm2.weight", "norm.weight"), lambda shp, g: clamped(shp[1] ** -0.5)(shp, g))]
+
+SWIN_FAMILY = Family("swin", SwinSpec, SWIN_MODELS, is_swin_name, swin_named, lambda name, in_hw: swin_tiny(in_hw),
+                "timm's Swin names at 224 x 224", "the last block of stages {}", True, SWIN_SYNTHETIC, check_swin_buffers)
+
+
 # ---------------------------------------------------------------------------
 # the ConvNeXt surrogates: convolutional, but planned on the transformer stack (include/i2v_convnext.h)
 # ---------------------------------------------------------------------------
@@ -1234,7 +1289,7 @@ CONVNEXT_MODELS: Dict[str, Tuple[int, Tuple[int, ...]]] = {
 
 
 @dataclass
-class ConvNextSpec:
+class ConvNextSpec(StagedSpec):
     """timm `ConvNeXt`: the stem is a patch x patch convolution with stride patch and bias, then a LayerNorm over
     channels; stage i is `depths[i]` blocks at width dim * 2^i on a plane of (img / patch) / 2^i squared, with a downsample (LayerNorm
     over channels, then a 2 x 2 / 2 convolution with bias) in front of every stage but the first.  A block is
@@ -1264,10 +1319,6 @@ class ConvNextSpec:
             self.hooks = {d: d - 1 for d in range(1, self.stages + 1)}
 
     @property
-    def in_hw(self):
-        return (self.img, self.img)
-
-    @property
     def stages(self) -> int:
         return len(self.depths)
 
@@ -1283,12 +1334,6 @@ class ConvNextSpec:
     def hook_dim(self, i: int) -> int:
         """Floats per frame of the feature hooked at stage i."""
         return self.tokens(i) * self.width(i)
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based stage whose last block depth `depth` hooks (`whole_module` changes nothing: a stage is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def stem_keys(self) -> List[str]:
         return ["stem.0.weight", "stem.0.bias", "stem.1.weight", "stem.1.bias"]
@@ -1337,6 +1382,9 @@ class ConvNextSpec:
                 out += [f(k[0]).reshape(D, 49).t().contiguous()] + [f(x).contiguous() for x in k[1:6]]
                 out += [(f(k[6]) * gamma[:, None]).contiguous(), (f(k[7]) * gamma).contiguous()]
         return out
+
+    def config_values(self):
+        return (self.img, self.patch, self.in_chans, self.dim, self.stages, self.depths, self.ln_eps)
 
     def macs_per_frame(self) -> int:
         total = self.tokens(0) * self.dim * self.in_chans * self.patch ** 2
@@ -1406,6 +1454,17 @@ def convnext_tiny_twin(in_hw=(64, 64)) -> ConvNextSpec:
     return ConvNextSpec("convnext_test", int(in_hw[0]), 4, 3, 8, (2, 1, 2, 1))
 
 
+#: Seeded stand-in for a trained ConvNeXt, drawn per key: the stem and downsample convolutions at fan_in^-0.5 (a unit-variance stream
+#: stays one), depthwise filters at 1 / 7 (49 taps of unit inputs give unit outputs), fc1 at fan_in^-0.5 and fc2 at 0.5 fan_in^-0.5,
+#: LayerNorm gains near 1, small biases, and `gamma` spread over 0.1 .. 0.5 with random signs -- far from the ones a forgotten fold
+#: would use.  Each block then adds a few tenths to its stream, which stays O(1) through 36 blocks.
+CONVNEXT_SYNTHETIC = [(ends("gamma"), signed_uniform(0.1, 0.4)), (ends("conv_dw.weight"), normal_over(7.0)),
+                      *fan_in_tail(ends("norm.weight", "stem.1.weight", "downsample.0.weight"), half=ends("fc2.weight"))]
+
+CONVNEXT_FAMILY = Family("convnext", ConvNextSpec, CONVNEXT_MODELS, is_convnext_name, convnext_named, lambda name, in_hw: convnext_tiny_twin(in_hw),
+                "timm's ConvNeXts at 224 x 224", "the last block of stages {}", True, CONVNEXT_SYNTHETIC)
+
+
 # ---------------------------------------------------------------------------
 # the all-MLP surrogates: MLP-Mixer and ResMLP, planned on the transformer stack (include/i2v_mixer.h)
 # ---------------------------------------------------------------------------
@@ -1428,7 +1487,7 @@ MIXER_MODELS: Dict[str, Tuple[str, int, int, int]] = {
 
 
 @dataclass
-class MixerSpec:
+class MixerSpec(TokenSpec):
     """timm 0.5.0 `MlpMixer`: the stem is a patch x patch convolution with stride patch and bias -- no norm, no
     prefix token, no pos_embed --, giving `tokens` = (img / patch)^2 tokens of `dim` channels; then `blocks` blocks.
       kind "mixer"  (`MixerBlock`)  x += mlp_tokens(LN1(x)^T)^T, fc1 (tokens_hidden, tokens), GELU, fc2 (tokens, tokens_hidden), down the
@@ -1457,11 +1516,7 @@ class MixerSpec:
         if self.blocks % 4:
             raise ValueError(f"{self.arch}: {self.blocks} blocks: depths 1..4 hook blocks d * blocks / 4 - 1")
         if not self.hooks:
-            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
-
-    @property
-    def in_hw(self):
-        return (self.img, self.img)
+            self.hooks = self.quarter_hooks()
 
     @property
     def tokens(self) -> int:
@@ -1479,12 +1534,6 @@ class MixerSpec:
     def hook_dim(self, i: int = 0) -> int:
         """Floats per frame of the feature hooked at block i (the same for every block)."""
         return self.tokens * self.dim
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def block_keys(self, i: int) -> List[str]:
         p = f"blocks.{i}."
@@ -1529,6 +1578,9 @@ class MixerSpec:
             out += [(w1 * a2.double()[None, :]).float().contiguous(), (c1 + w1 @ b2.double()).float().contiguous()]
             out += [(w2 * ls2.double()[:, None]).float().contiguous(), (c2 * ls2.double()).float().contiguous()]
         return out
+
+    def config_values(self):
+        return (self.img, self.patch, self.in_chans, self.dim, self.blocks, self.tokens_hidden, self.mlp, 1 if self.kind == "resmlp" else 0, self.ln_eps)
 
     def macs_per_frame(self) -> int:
         S, D, Sh, H = self.tokens, self.dim, self.tokens_hidden, self.mlp
@@ -1593,6 +1645,24 @@ def mixer_tiny_twin(kind: str = "mixer", patch: int = 16, in_hw=(64, 64)) -> Mix
     return MixerSpec(arch, int(in_hw[0]), patch, 3, 32, 8, kind)
 
 
+#: Seeded stand-in for a trained MLP-Mixer / ResMLP, drawn per key: Linears (the stem as one) at fan_in^-0.5, the second Linear of an
+#: MLP at 0.5 fan_in^-0.5, LayerNorm gains near 1, small biases.  ResMLP's `ls1` / `ls2` are spread over 0.1 .. 0.4 with random signs,
+#: `alpha` over 0.5 .. 1.5 and `beta` ~ 0.3 N(0, 1): far from timm's initial 1e-4 / 1 / 0 and from the ones and zeros a forgotten fold
+#: would use.
+MIXER_SYNTHETIC = [(ends(".ls1", ".ls2"), signed_uniform(0.1, 0.3)), (ends(".alpha"), uniform(0.5)), (ends(".beta"), normal(0.3)),
+                   *fan_in_tail(ends("norm1.weight", "norm2.weight"), half=ends("fc2.weight"))]
+
+
+def _mixer_twin(model_name: str, in_hw):
+    """One twin per kind: the Mixer one follows the name's patch, the ResMLP one has 4 tokens."""
+    kind, patch, _, _ = MIXER_MODELS[model_name]
+    return mixer_tiny_twin(kind, patch if kind == "mixer" else 32, in_hw)
+
+
+MIXER_FAMILY = Family("mixer", MixerSpec, MIXER_MODELS, is_mixer_name, mixer_named, _mixer_twin, "timm's MLP-Mixers and ResMLPs at 224 x 224",
+                "blocks {}", True, MIXER_SYNTHETIC)
+
+
 # ---------------------------------------------------------------------------
 # the CaiT surrogates: self-attention blocks with talking-heads attention and LayerScale, planned on the transformer stack
 # (include/i2v_cait.h)
@@ -1606,7 +1676,7 @@ CAIT_MODELS: Dict[str, Tuple[int, int, int]] = {
 
 
 @dataclass
-class CaitSpec:
+class CaitSpec(TokenSpec):
     """timm 0.5.0 `Cait` up to its last self-attention block: patch embedding (patch x patch convolution, stride
     patch, bias), pos_embed (tokens, dim) added, NO prefix token -- `cls_token` joins only in the two class-attention blocks, which lie
     behind the last hookable block and never run --, then `blocks` pre-norm blocks
@@ -1633,11 +1703,7 @@ class CaitSpec:
         if self.blocks % 4:
             raise ValueError(f"{self.arch}: {self.blocks} blocks: depths 1..4 hook blocks d * blocks / 4 - 1")
         if not self.hooks:
-            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
-
-    @property
-    def in_hw(self):
-        return (self.img, self.img)
+            self.hooks = self.quarter_hooks()
 
     @property
     def tokens(self) -> int:
@@ -1650,12 +1716,6 @@ class CaitSpec:
     def hook_dim(self, i: int = 0) -> int:
         """Floats per frame of the feature hooked at block i (the same for every block)."""
         return self.tokens * self.dim
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def block_keys(self, i: int) -> List[str]:
         """timm's order: the block's own parameters (the LayerScale vectors) ahead of its children's."""
@@ -1692,6 +1752,9 @@ class CaitSpec:
             out += [f(p + k).contiguous() for k in ("norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias")]
             out += [(f(p + "mlp.fc2.weight").double() * g2[:, None]).float().contiguous(), (f(p + "mlp.fc2.bias").double() * g2).float().contiguous()]
         return out
+
+    def config_values(self):
+        return (self.img, self.patch, self.in_chans, self.dim, self.heads, self.mlp, self.blocks, self.ln_eps)
 
     def macs_per_frame(self) -> int:
         T, D, M, H = self.tokens, self.dim, self.mlp, self.heads
@@ -1745,6 +1808,26 @@ def cait_tiny_twin(in_hw=(64, 64)) -> CaitSpec:
     return CaitSpec("cait_test", int(in_hw[0]), 16, 3, 32, 4, 8)
 
 
+def _mix_draw(shp, g):
+    """A talking-heads mix: the identity plus 0.25 N(0, 1) per entry."""
+    import torch
+    return torch.eye(shp[0]) + 0.25 * torch.randn(*shp, generator=g)
+
+
+#: Seeded stand-in for a trained CaiT, drawn per key so that every piece of the block's arithmetic shows in the hooks: Linears (the
+#: patch embedding as one) ~ fan_in^-0.5 N(0, 1), which keeps a unit-variance stream and puts the attention logits at O(1); `attn.proj`
+#: and `mlp.fc2` at half that; LayerNorm gains 1 + 0.1 N(0, 1); biases 0.02 N(0, 1); pos_embed 0.5 N(0, 1).  The LayerScale vectors
+#: `gamma_1` / `gamma_2` are uniform on [0.5, 1] with random signs -- timm initialises them at 1e-5 or 1e-6, which would make every
+#: block an identity and the tests blind to the kernel.  The talking-heads mixes `attn.proj_l.weight` / `attn.proj_w.weight` are the
+#: identity plus 0.25 N(0, 1) per entry, with `proj_l.bias` ~ 0.5 N(0, 1) and `proj_w.bias` ~ 0.02 N(0, 1): far from the identity and
+#: the zeros a skipped mix would compute.
+CAIT_SYNTHETIC = [(ends(".gamma_1", ".gamma_2"), signed_uniform(0.5, 0.5)), (ends("proj_l.weight", "proj_w.weight"), _mix_draw),
+                  (ends("proj_l.bias"), normal(0.5)), (keys("pos_embed"), normal(0.5)), *fan_in_tail(ends("norm1.weight", "norm2.weight"))]
+
+CAIT_FAMILY = Family("cait", CaitSpec, CAIT_MODELS, is_cait_name, cait_named, lambda name, in_hw: cait_tiny_twin(in_hw),
+                "timm's CaiTs at 224 x 224", "blocks {}", True, CAIT_SYNTHETIC)
+
+
 # ---------------------------------------------------------------------------
 # the ConViT surrogates: gated positional self-attention blocks, then plain blocks behind a class token that joins in mid-stream,
 # planned on the transformer stack (include/i2v_convit.h)
@@ -1759,7 +1842,7 @@ CONVIT_MODELS: Dict[str, Tuple[int, int]] = {
 
 
 @dataclass
-class ConvitSpec:
+class ConvitSpec(TokenSpec):
     """timm 0.5.0 `ConViT` up to its last block: patch embedding (patch x patch convolution, stride patch, bias),
     pos_embed (tokens, dim) added, then `blocks` pre-norm blocks  x += proj(attn(LN1 x));  x += fc2(GELU(fc1(LN2 x))),  LayerNorm eps
     `ln_eps`, exact GELU, no qkv bias.  Blocks 0 .. local_blocks - 1 run on the patch tokens with gated positional self-attention:
@@ -1788,11 +1871,7 @@ class ConvitSpec:
             raise ValueError(f"{self.arch}: {self.blocks} blocks, {self.local_blocks} of them local: depths 1..4 hook blocks d * blocks / 4 "
                              "- 1, and the class token joins before a block 1 .. blocks")
         if not self.hooks:
-            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
-
-    @property
-    def in_hw(self):
-        return (self.img, self.img)
+            self.hooks = self.quarter_hooks()
 
     @property
     def grid(self) -> int:
@@ -1811,15 +1890,12 @@ class ConvitSpec:
         """Tokens block i runs on, and the stream after it holds."""
         return self.tokens + (1 if i >= self.local_blocks else 0)
 
+    def hook_shape(self, i: int):
+        return (self.tokens_at(i), self.dim)
+
     def hook_dim(self, i: int = 0) -> int:
         """Floats per frame of the feature hooked at block i."""
         return self.tokens_at(i) * self.dim
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def block_keys(self, i: int) -> List[str]:
         """timm's order: norm1, the attention (`GPSA`: its own parameter gating_param first, as a state dict lists a module's own
@@ -1886,6 +1962,9 @@ class ConvitSpec:
             out += [f(p + k).contiguous() for k in tail]
         return out
 
+    def config_values(self):
+        return (self.img, self.patch, self.in_chans, self.dim, self.heads, self.mlp, self.blocks, self.local_blocks, self.ln_eps)
+
     def macs_per_frame(self) -> int:
         D, M = self.dim, self.mlp
         total = self.tokens * D * self.in_chans * self.patch ** 2
@@ -1941,6 +2020,33 @@ def convit_tiny_twin(in_hw=(64, 64)) -> ConvitSpec:
     return ConvitSpec("convit_test", int(in_hw[0]), 16, 3, 32, 4, 8, 6)
 
 
+def _pos_proj_draw(shp, g):
+    """timm's local initialisation of `attn.pos_proj.weight` plus seeded noise (see `CONVIT_SYNTHETIC`)."""
+    import torch
+    H = shp[0]
+    ks = int(H ** 0.5)
+    centre = (ks - 1) / 2 if ks % 2 == 0 else ks // 2
+    w = torch.zeros(H, 3)
+    for h1 in range(ks):
+        for h2 in range(ks):
+            w[h1 + ks * h2] = torch.tensor([2.0 * (h2 - centre), 2.0 * (h1 - centre), -1.0])
+    return w + torch.randn(H, 3, generator=g) * torch.tensor([0.3, 0.3, 0.1])
+
+
+#: Seeded stand-in for a trained ConViT, drawn per key as CaiT's is: Linears ~ fan_in^-0.5 N(0, 1) (`attn.proj` and `mlp.fc2` at half
+#: that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1), pos_embed and cls_token 0.5 N(0, 1).  `attn.v` is an ordinary Linear
+#: draw, not timm's identity.  `attn.pos_proj.weight` is timm's local initialisation -- column 2 = -1, and columns 0 / 1 on the head's
+#: offset in a floor(sqrt(heads)) grid: head p = h1 + k h2 gets column 1 = 2 (h1 - centre) and column 0 = 2 (h2 - centre) -- plus seeded
+#: noise, 0.3 N(0, 1) on the two offset columns and 0.1 N(0, 1) on the distance column, so that the x and y columns of every head
+#: differ and a transposed grid convention shows.  `attn.gating_param` ~ N(0, 1), so sigma(g) spans the range (timm starts it at 1);
+#: `attn.pos_proj.bias` ~ 0.5 N(0, 1), far from the zero a dropped bias would equal.
+CONVIT_SYNTHETIC = [(ends("pos_proj.weight"), _pos_proj_draw), (ends("gating_param"), normal()), (ends("pos_proj.bias"), normal(0.5)),
+                    (keys("pos_embed", "cls_token"), normal(0.5)), *fan_in_tail(ends("norm1.weight", "norm2.weight"))]
+
+CONVIT_FAMILY = Family("convit", ConvitSpec, CONVIT_MODELS, is_convit_name, convit_named, lambda name, in_hw: convit_tiny_twin(in_hw),
+                "timm's ConViTs at 224 x 224", "blocks {}", True, CONVIT_SYNTHETIC)
+
+
 # ---------------------------------------------------------------------------
 # the XCiT surrogates: cross-covariance attention (channels attend to channels), a convolutional stem and a depthwise "local patch
 # interaction" per block, planned on the transformer stack (include/i2v_xcit.h)
@@ -1962,7 +2068,7 @@ BN2D_EPS = 1e-5      # torch's BatchNorm2d default: the stem's and the local pat
 
 
 @dataclass
-class XcitSpec:
+class XcitSpec(TokenSpec):
     """timm 0.5.0 `XCiT` up to its last cross-covariance block.  Stem: four 3 x 3 / stride 2 / pad 1 convolutions
     without bias (widths dim / 8, dim / 4, dim / 2, dim), each followed by an eval-mode BatchNorm2d, the first three by the exact GELU;
     then + the Fourier position features of the token grid through a 1 x 1 convolution.  Then `blocks` blocks, LayerNorm eps `ln_eps`:
@@ -1988,13 +2094,9 @@ class XcitSpec:
         if self.blocks % 4:
             raise ValueError(f"{self.arch}: {self.blocks} blocks: depths 1..4 hook blocks d * blocks / 4 - 1")
         if not self.hooks:
-            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
+            self.hooks = self.quarter_hooks()
 
     patch = 16
-
-    @property
-    def in_hw(self):
-        return (self.img, self.img)
 
     @property
     def grid(self) -> int:
@@ -2014,12 +2116,6 @@ class XcitSpec:
 
     def hook_dim(self, i: int = 0) -> int:
         return self.tokens * self.dim
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def block_keys(self, i: int) -> List[str]:
         """timm's order: the block's own parameters gamma1, gamma3, gamma2 first, then norm1, attn (its own `temperature` first), norm3,
@@ -2095,6 +2191,9 @@ class XcitSpec:
                     f32((d(p + "local_mp.conv2.weight").reshape(D, 9) * g3[:, None]).t()), f32(d(p + "local_mp.conv2.bias") * g3)]
         return out
 
+    def config_values(self):
+        return (self.img, self.in_chans, self.dim, self.heads, self.mlp, self.blocks, self.ln_eps)
+
     def macs_per_frame(self) -> int:
         D, M, T, cs = self.dim, self.mlp, self.tokens, self.stem_widths
         total = sum((self.img >> (k + 1)) ** 2 * 9 * cs[k] * cs[k + 1] for k in range(4))
@@ -2151,6 +2250,28 @@ def xcit_tiny_twin(in_hw=(64, 64)) -> XcitSpec:
     return XcitSpec("xcit_test", int(in_hw[0]), 3, 32, 4, 8)
 
 
+#: timm renamed XCiT's `pos_embeder` to `pos_embed` after 0.5.0: the later spelling of the same two arrays is accepted
+XCIT_KEY_ALIASES = {"pos_embed.token_projection.weight": "pos_embeder.token_projection.weight",
+                    "pos_embed.token_projection.bias": "pos_embeder.token_projection.bias"}
+
+#: Seeded stand-in for a trained XCiT, drawn per key as CaiT's is: Linears and convolutions ~ fan_in^-0.5 N(0, 1) (`attn.proj` and
+#: `mlp.fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1) -- the depthwise convolutions' 0.1 N(0, 1), so that a
+#: dropped bias shows --, BatchNorm gains uniform on (0.5, 1.5), shifts and running means 0.1 N(0, 1), running variances uniform on
+#: (0.5, 1.5).  The LayerScales gamma1 / gamma2 / gamma3 are uniform on (0.5, 1.5) -- timm starts them at 1 (or 1e-5 for the 24-block
+#: models) and they train away from it --, each drawn on its own so that exchanging two of them shows; `attn.temperature` is uniform on
+#: (0.5, 4), so that the softmax over channels is neither flat nor one-hot.
+XCIT_SYNTHETIC = [
+    (lambda k: k.endswith(("gamma1", "gamma2", "gamma3", "running_var")) or ".bn.weight" in k
+     or (k.startswith("patch_embed") and k.endswith("1.weight")), uniform(0.5)),
+    (ends("temperature"), uniform(0.5, 3.5)),
+    (lambda k: k.endswith("running_mean") or ".bn.bias" in k or (k.startswith("patch_embed") and k.endswith("1.bias")), normal(0.1)),
+    (ends("conv1.bias", "conv2.bias"), normal(0.1)),
+    *fan_in_tail(ends("norm1.weight", "norm2.weight", "norm3.weight"))]
+
+XCIT_FAMILY = Family("xcit", XcitSpec, XCIT_MODELS, is_xcit_name, xcit_named, lambda name, in_hw: xcit_tiny_twin(in_hw),
+                "timm's XCiTs at 224 x 224 with patch 16", "blocks {}", True, XCIT_SYNTHETIC, key_aliases=XCIT_KEY_ALIASES)
+
+
 # ---------------------------------------------------------------------------
 # the Twins surrogates: a four-stage pyramid whose global attention takes its keys from a sub-sampled plane (rectangular attention),
 # with a depthwise conditional position encoding per stage, planned on the transformer stack (include/i2v_twins.h)
@@ -2169,7 +2290,7 @@ TWINS_MODELS: Dict[str, Tuple[Tuple[int, ...], Tuple[int, ...], Tuple[int, ...],
 
 
 @dataclass
-class TwinsSpec:
+class TwinsSpec(StagedSpec):
     """timm 0.5.0 `Twins` up to its last block.  Stage k: `patch_embeds.k`, a convolution with kernel = stride =
     patch (4 for stage 0, 2 after) and LayerNorm eps `pe_eps`; then `depths[k]` pre-norm blocks at width `dims[k]` (norms eps `ln_eps`,
     exact GELU, MLP ratio `mlp_ratios[k]`); `pos_block.k` after block 0: x += dwconv3x3(x) + bias on the grid.
@@ -2215,10 +2336,6 @@ class TwinsSpec:
 
     stages = 4
 
-    @property
-    def in_hw(self):
-        return (self.img, self.img)
-
     def grid(self, k: int) -> int:
         return (self.img // self.patch) >> k
 
@@ -2242,12 +2359,6 @@ class TwinsSpec:
     def hook_dim(self, k: int) -> int:
         """Floats per frame of the feature hooked at stage k."""
         return self.tokens(k) * self.dims[k]
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based stage whose last block depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def embed_keys(self, k: int) -> List[str]:
         p = f"patch_embeds.{k}."
@@ -2321,6 +2432,9 @@ class TwinsSpec:
     def config_lists(self):
         """(dims, heads, MLP widths, depths, sr) as `i2v_twins_config` takes them."""
         return list(self.dims), list(self.heads), [self.mlp(k) for k in range(4)], list(self.depths), list(self.sr_ratios)
+
+    def config_values(self):
+        return (self.img, self.in_chans, self.patch, self.stages, self.window, *self.config_lists(), self.ln_eps, self.pe_eps)
 
     def macs_per_frame(self) -> int:
         total = 0
@@ -2420,6 +2534,22 @@ def twins_tiny_twin(model_name: str = "twins_pcpvt_small", in_hw=(64, 64)) -> Tw
     return TwinsSpec("twins_pcpvt_test", side, (16, 32, 40, 64), (1, 2, 5, 8), (4, 4, 2, 2), (2, 2, 2, 2), 0)
 
 
+#: Seeded stand-in for a trained Twins, drawn per key as XCiT's is: Linears and the patch and sub-sampling convolutions ~ fan_in^-0.5
+#: N(0, 1) (`attn.proj` and `mlp.fc2` at half that), the blocks' LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1).  What is new
+#: shows: `attn.norm` and the patch embeddings' norms have gains uniform on (0.5, 1.5) and shifts 0.1 N(0, 1), so that a sub-sampled
+#: plane that skipped its LayerNorm is seen; `attn.sr.bias` is 0.1 N(0, 1); the position encoding's depthwise filter is N(0, 1) / 3
+#: with a bias of 0.1 N(0, 1), so that its term is of the size of the stream it is added to.
+TWINS_SYNTHETIC = [
+    (lambda k: k.endswith("attn.norm.weight") or (k.startswith("patch_embeds") and k.endswith("norm.weight")), uniform(0.5)),
+    (lambda k: k.endswith("attn.norm.bias") or (k.startswith("patch_embeds") and k.endswith("norm.bias")) or k.endswith("attn.sr.bias")
+     or (k.startswith("pos_block") and k.endswith("bias")), normal(0.1)),
+    (starts("pos_block"), normal_over(3.0)),
+    *fan_in_tail(ends("norm1.weight", "norm2.weight"))]
+
+TWINS_FAMILY = Family("twins", TwinsSpec, TWINS_MODELS, is_twins_name, twins_named, twins_tiny_twin, "timm's Twins (PCPVT and SVT) at 224 x 224",
+                "the last block of stages {}", True, TWINS_SYNTHETIC)
+
+
 # ---------------------------------------------------------------------------
 # the BEiT surrogates: a ViT-shaped stack without a position embedding, whose every block adds a learned relative position bias to its
 # attention scores and scales its two branches by LayerScale vectors, planned on the transformer stack (include/i2v_beit.h)
@@ -2432,7 +2562,7 @@ BEIT_MODELS: Dict[str, Tuple[int, int, int, int, int]] = {
 
 
 @dataclass
-class BeitSpec:
+class BeitSpec(TokenSpec):
     """timm 0.5.0 `Beit` up to its last block: `patch_embed.proj`, a patch x patch convolution at stride patch
     with bias; one `cls_token` prepended; NO `pos_embed` and no shared `rel_pos_bias`; then `blocks` pre-norm blocks (LayerNorm eps
     `ln_eps`, exact GELU)  x += gamma_1 * proj(attn(norm1 x));  x += gamma_2 * fc2(gelu(fc1(norm2 x))).
@@ -2464,11 +2594,7 @@ class BeitSpec:
         if self.blocks % 4:
             raise ValueError(f"{self.arch}: {self.blocks} blocks: the hooks sit at every quarter of the stack")
         if not self.hooks:
-            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
-
-    @property
-    def in_hw(self):
-        return (self.img, self.img)
+            self.hooks = self.quarter_hooks()
 
     @property
     def grid(self) -> int:
@@ -2486,12 +2612,6 @@ class BeitSpec:
     def hook_dim(self) -> int:
         """Floats per frame of a hooked feature."""
         return self.tokens * self.dim
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def block_keys(self, i: int) -> List[str]:
         """The block's PARAMETERS in timm's state-dict order (the buffer `attn.relative_position_index` sits behind the table there:
@@ -2550,6 +2670,9 @@ class BeitSpec:
                     f32(p + "norm2.weight"), f32(p + "norm2.bias"), f32(p + "mlp.fc1.weight"), f32(p + "mlp.fc1.bias"),
                     (g2[:, None] * f64(p + "mlp.fc2.weight")).float().contiguous(), (g2 * f64(p + "mlp.fc2.bias")).float().contiguous()]
         return out
+
+    def config_values(self):
+        return (self.img, self.patch, self.in_chans, self.dim, self.heads, self.mlp, self.blocks, self.ln_eps)
 
     def macs_per_frame(self) -> int:
         T, D, M = self.tokens, self.dim, self.mlp
@@ -2619,6 +2742,30 @@ def beit_tiny_twin(model_name: str = "beit_base_patch16_224", in_hw=(64, 64)) ->
     return BeitSpec("beit_test_224", 224, 16, 3, 64, 1, 128, 4)
 
 
+def check_beit_buffers(spec: BeitSpec, sd, where: str) -> None:
+    """timm's BEiT checkpoints carry the buffer `attn.relative_position_index` per block; it is computed from the geometry here and
+    never loaded, so one that differs describes another model: refused by key name.  An absent one is fine."""
+    import torch
+    idx = spec.relative_position_index()
+    for i in range(spec.blocks):
+        k = spec.index_key(i)
+        if k in sd and not (tuple(sd[k].shape) == tuple(idx.shape) and torch.equal(sd[k].long(), idx)):
+            raise ValueError(f"{where}: buffer {k} differs from the index computed for a {spec.grid} x {spec.grid} grid")
+
+
+#: Seeded stand-in for a trained BEiT, drawn per key as Twins' is: Linears and the patch convolution ~ fan_in^-0.5 N(0, 1) (`attn.proj`
+#: and `mlp.fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1), `cls_token` 0.02 N(0, 1).  timm's initial values
+#: would blind the tests -- a zero bias table makes the bias a no-op, a LayerScale of 0.1 or 1e-5 silences the blocks -- so what is new
+#: shows: `relative_position_bias_table` is N(0, 1), `gamma_1` / `gamma_2` are uniform on (0.5, 1.5), and `q_bias` / `v_bias` are 0.1
+#: N(0, 1).  The index buffers are not emitted: they are computed from the geometry.
+BEIT_SYNTHETIC = [(ends("gamma_1", "gamma_2"), uniform(0.5)), (ends("relative_position_bias_table"), normal()),
+                  (ends("q_bias", "v_bias"), normal(0.1)),
+                  *fan_in_tail(ends("norm1.weight", "norm2.weight"), bias=lambda k: k.endswith("bias") or k == "cls_token")]
+
+BEIT_FAMILY = Family("beit", BeitSpec, BEIT_MODELS, is_beit_name, beit_named, beit_tiny_twin, "timm's BEiTs at 224 x 224 with patch 16",
+                "blocks {}", True, BEIT_SYNTHETIC, check_beit_buffers)
+
+
 # ---------------------------------------------------------------------------
 # the PiT surrogates: a ViT whose token grid is pooled between three stages like a CNN's, with an overlapping patch embedding and a
 # spatial position table, planned on the transformer stack (include/i2v_pit.h)
@@ -2635,7 +2782,7 @@ PIT_MODELS.update({k.replace("_224", "_distilled_224"): v for k, v in list(PIT_M
 
 
 @dataclass
-class PitSpec:
+class PitSpec(TokenSpec):
     """timm 0.5.0 `PoolingVisionTransformer` up to its last block (restated, UNCHECKED against timm):
     `patch_embed.conv`, a patch x patch convolution at stride `stride` < patch, padding 0, with bias, onto a grid of
     (img - patch) / stride + 1 a side; `pos_embed` (1, C, g, g) added to the grid tokens only; `cls_token` (1, prefix, C) prepended
@@ -2668,10 +2815,6 @@ class PitSpec:
             self.hooks = {1: d[0] - 1, 2: d[0] + d[1] // 2 - 1, 3: d[0] + d[1] - 1, 4: d[0] + d[1] + d[2] - 1}
 
     @property
-    def in_hw(self):
-        return (self.img, self.img)
-
-    @property
     def grids(self) -> Tuple[int, int, int]:
         g0 = (self.img - self.patch) // self.stride + 1
         g1 = (g0 - 1) // 2 + 1
@@ -2692,12 +2835,6 @@ class PitSpec:
 
     def tokens(self, stage: int) -> int:
         return self.prefix + self.grids[stage] ** 2
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based flat block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def hook_shape(self, block: int) -> Tuple[int, int]:
         st = self.stage_of(block)
@@ -2747,6 +2884,9 @@ class PitSpec:
             out += [f32(p + k) for k in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
                                          "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
         return out
+
+    def config_values(self):
+        return (self.img, self.patch, self.stride, self.in_chans, self.prefix, self.widths, self.heads, self.depths, self.ln_eps)
 
     def macs_per_frame(self) -> int:
         total = self.grids[0] ** 2 * self.widths[0] * self.in_chans * self.patch ** 2
@@ -2822,6 +2962,17 @@ def pit_tiny_twin(model_name: str = "pit_s_224", in_hw=(64, 64)) -> PitSpec:
     return PitSpec("pit_test_224", 224, 16, 8, 32, (1, 2, 4), (1, 2, 1), 1)
 
 
+#: Seeded stand-in for a trained PiT, drawn per key as BEiT's is: Linears and the patch convolution ~ fan_in^-0.5 N(0, 1) (`attn.proj`
+#: and `mlp.fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1).  What is new must show in the tests: `pos_embed`
+#: and `cls_token` are N(0, 1) (timm's 0.02 would leave the position table and the prefix tokens below the tests' bounds), and the pool
+#: filter `pool.conv.weight` is N(0, 1) / 3 over its 9 taps, so that a pooled token is of the size of its inputs.
+PIT_SYNTHETIC = [(keys("pos_embed", "cls_token"), normal()), (ends("pool.conv.weight"), normal_over(3.0)),
+                 *fan_in_tail(ends("norm1.weight", "norm2.weight"))]
+
+PIT_FAMILY = Family("pit", PitSpec, PIT_MODELS, is_pit_name, pit_named, pit_tiny_twin, "timm's PiTs at 224 x 224",
+                "blocks {}, numbered across the stages", False, PIT_SYNTHETIC)
+
+
 # ---------------------------------------------------------------------------
 # the CoaT-Lite surrogates: four stages of serial blocks whose attention is FACTORIZED -- a softmax down the token axis of K, a dh x dh
 # product per head -- with a convolutional position encoding, planned on the transformer stack (include/i2v_coat.h)
@@ -2838,7 +2989,7 @@ COAT_PARALLEL = ("coat_tiny", "coat_mini")
 
 
 @dataclass
-class CoatSpec:
+class CoatSpec(StagedSpec):
     """timm 0.5.0 `CoaT` with serial blocks only, up to its last block (restated from memory of coat.py, UNCHECKED
     against timm): `patch_embed1`, a Conv2d(3, C, 4, stride 4) and a LayerNorm; `patch_embed{2,3,4}`, a Conv2d(C', C, 2, stride 2) and
     a LayerNorm on the previous stage's grid tokens, the class token dropped; `cls_token{k}` (1, 1, C) in front of every stage, no
@@ -2873,10 +3024,6 @@ class CoatSpec:
     stages = 4
 
     @property
-    def in_hw(self):
-        return (self.img, self.img)
-
-    @property
     def grids(self) -> Tuple[int, int, int, int]:
         return tuple(self.img // 4 // 2 ** k for k in range(4))
 
@@ -2889,15 +3036,6 @@ class CoatSpec:
 
     def width(self, stage: int) -> int:
         return self.widths[stage]
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based stage whose output depth `depth` hooks (`whole_module` changes nothing: a stage is one module list)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
-
-    def hook_shape(self, stage: int) -> Tuple[int, int]:
-        return (self.tokens(stage), self.widths[stage])
 
     def window_channels(self, stage: int) -> Tuple[int, int, int]:
         """Channels of stage `stage` that pass crpe's 3 x 3, 5 x 5 and 7 x 7."""
@@ -2957,6 +3095,9 @@ class CoatSpec:
                                              "factoratt_crpe.proj.weight", "factoratt_crpe.proj.bias", "norm2.weight", "norm2.bias",
                                              "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
         return out
+
+    def config_values(self):
+        return (self.img, self.in_chans, self.widths, self.heads, self.depths, self.mlp_ratios, *self.windows, self.ln_eps)
 
     def macs_per_frame(self) -> int:
         total = 0
@@ -3026,6 +3167,33 @@ def coat_tiny_twin(model_name: str = "coat_lite_tiny", in_hw=(64, 64)) -> CoatSp
     return CoatSpec("coat_test_224", 224, (32, 64, 64, 96), (1, 1, 1, 1), (8, 8, 4, 4), 8, (2, 3, 3))
 
 
+def check_coat_duplicates(spec: CoatSpec, sd, where: str) -> None:
+    """timm registers a stage's shared `cpe` and `crpe` again inside every serial block, so its checkpoints carry them under block-level
+    keys too.  The stage-level keys are the ones loaded; a block-level duplicate that differs describes another model: refused by key
+    name.  An absent one is fine."""
+    import torch
+    for dup, key in spec.shared_duplicates().items():
+        if dup in sd and not (tuple(sd[dup].shape) == tuple(sd[key].shape) and torch.equal(sd[dup].float(), sd[key].float())):
+            raise ValueError(f"{where}: {dup} differs from the stage's shared {key}")
+
+
+def _window_filter_draw(shp, g):
+    """A depthwise filter of `cpe` / `crpe`: N(0, 1) / window over its window^2 taps."""
+    import torch
+    return torch.randn(*shp, generator=g) / shp[-1]
+
+
+#: Seeded stand-in for a trained CoaT-Lite, drawn per key as PiT's is: Linears and the patch convolutions ~ fan_in^-0.5 N(0, 1)
+#: (`factoratt_crpe.proj` and `mlp.fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1).  What is new must show in
+#: the tests: the class tokens are N(0, 1) and the filters of `cpe` and `crpe` N(0, 1) / window over their window^2 taps, so that each
+#: window moves the features.
+COAT_SYNTHETIC = [(starts("cls_token"), normal()), (lambda k: k.startswith(("cpe", "crpe")) and k.endswith("weight"), _window_filter_draw),
+                  *fan_in_tail(ends("norm1.weight", "norm2.weight", "norm.weight"), half=ends("fc2.weight", "factoratt_crpe.proj.weight"))]
+
+COAT_FAMILY = Family("coat", CoatSpec, COAT_MODELS, is_coat_name, coat_named, coat_tiny_twin, "timm's serial CoaT-Lites at 224 x 224",
+                "the last block of stages {}", False, COAT_SYNTHETIC, check_coat_duplicates)
+
+
 # ---------------------------------------------------------------------------
 # the TNT surrogates (Transformer in Transformer): an inner transformer over the 16 pixel tokens of every patch feeding an outer ViT
 # over the patches, planned on the transformer stack (include/i2v_tnt.h)
@@ -3038,7 +3206,7 @@ TNT_MODELS: Dict[str, Tuple[int, int, int, int, int]] = {
 
 
 @dataclass
-class TntSpec:
+class TntSpec(TokenSpec):
     """timm 0.5.0 `TNT` up to its last block (restated from memory of tnt.py, UNCHECKED against timm).
     `pixel_embed.proj`, a Conv2d(3, in_dim, 7, stride 4, padding 3), gives img / 4 positions a side; the 4 x 4 cell of patch
     n = g py + px is its 16 pixel tokens, p = 4 i + j at conv output (4 py + i, 4 px + j); `pixel_pos` (1, in_dim, 4, 4) is added per
@@ -3072,11 +3240,7 @@ class TntSpec:
         if self.blocks % 4:
             raise ValueError(f"{self.arch}: {self.blocks} blocks: the hooks sit at every quarter of the stack")
         if not self.hooks:
-            self.hooks = {d: d * self.blocks // 4 - 1 for d in (1, 2, 3, 4)}
-
-    @property
-    def in_hw(self):
-        return (self.img, self.img)
+            self.hooks = self.quarter_hooks()
 
     @property
     def grid(self) -> int:
@@ -3095,12 +3259,6 @@ class TntSpec:
     def hook_dim(self) -> int:
         """Floats per frame of a hooked feature."""
         return self.tokens * self.dim
-
-    def hook_for(self, depth: int, whole_module: bool = False) -> int:
-        """Zero-based block whose output depth `depth` hooks (`whole_module` changes nothing: a block is one module)."""
-        if depth not in self.hooks:
-            raise KeyError(depth)
-        return self.hooks[depth]
 
     def param_shapes(self) -> Dict[str, Tuple[int, ...]]:
         """timm `state_dict` key -> shape for every parameter up to the last block."""
@@ -3142,6 +3300,9 @@ class TntSpec:
                         torch.zeros(3 * w), f32(p + att + ".proj.weight"), f32(p + att + ".proj.bias"), f32(p + nm + ".weight"), f32(p + nm + ".bias"),
                         f32(p + mlp + ".fc1.weight"), f32(p + mlp + ".fc1.bias"), f32(p + mlp + ".fc2.weight"), f32(p + mlp + ".fc2.bias")]
         return out
+
+    def config_values(self):
+        return (self.img, self.in_chans, self.dim, self.in_dim, self.heads, self.in_heads, self.mlp_ratio, self.blocks, self.ln_eps)
 
     def macs_per_frame(self) -> int:
         d, D, np_, T, r = self.in_dim, self.dim, self.grid ** 2, self.tokens, self.mlp_ratio
@@ -3204,6 +3365,28 @@ def tnt_tiny_twin(model_name: str = "tnt_s_patch16_224", in_hw=(64, 64)) -> TntS
     return TntSpec("tnt_test_224", 224, 32, 24, 4, 1, 4)
 
 
+#: Seeded stand-in for a trained TNT, drawn per key as CoaT-Lite's is: Linears and the pixel convolution ~ fan_in^-0.5 N(0, 1) (every
+#: attention's `proj`, the step's `proj` and every `fc2` at half that), LayerNorm gains 1 + 0.1 N(0, 1), biases 0.02 N(0, 1).  What is
+#: new must show in the tests: `cls_token` is N(0, 1) and the two position tables 0.5 N(0, 1), so that the pixel order inside a patch
+#: moves the features.
+TNT_SYNTHETIC = [(keys("cls_token"), normal()), (keys("patch_pos", "pixel_pos"), normal(0.5)),
+                 *fan_in_tail(lambda k: "norm" in k and k.endswith("weight"),
+                              half=lambda k: k.endswith(("fc2.weight", "proj.weight")) and not k.startswith("pixel_embed"))]
+
+TNT_FAMILY = Family("tnt", TntSpec, TNT_MODELS, is_tnt_name, tnt_named, tnt_tiny_twin, "timm's TNTs at 224 x 224",
+                "the outer stream after blocks {}", False, TNT_SYNTHETIC)
+
+
+# ---------------------------------------------------------------------------
+# the transformer surrogate families as one table (`family.Family`)
+# ---------------------------------------------------------------------------
+#: the rows, in the order the resolvers and the command line ask them
+FAMILIES = (VIT_FAMILY, SWIN_FAMILY, CONVNEXT_FAMILY, MIXER_FAMILY, CAIT_FAMILY, CONVIT_FAMILY, XCIT_FAMILY,
+            TWINS_FAMILY, BEIT_FAMILY, PIT_FAMILY, COAT_FAMILY, TNT_FAMILY)
+#: spec class -> its row
+FAMILY_OF = {f.spec: f for f in FAMILIES}
+
+
 # ---------------------------------------------------------------------------
 # name -> graph, following the reference's `get_model` vocabulary
 # ---------------------------------------------------------------------------
@@ -3235,24 +3418,9 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
         return densenet(32, (6, 12, 24, 16), 64, 4, in_hw, "densenet121")
     if model_name == "densenet161":
         return densenet(48, (6, 12, 36, 24), 96, 4, in_hw, "densenet161")
-    if is_vit_name(model_name):         # extension: the transformer surrogate of `get_vits()` (TPAMI_attack.py:88-98) and its timm family
-        return vit_named(model_name, in_hw)
-    if is_swin_name(model_name):        # extension: timm's Swin Transformer family (hierarchical, windowed attention)
-        return swin_named(model_name, in_hw)
-    if is_convnext_name(model_name):    # extension: timm's ConvNeXt family (7 x 7 depthwise blocks, planned on the transformer stack)
-        return convnext_named(model_name, in_hw)
-    if is_mixer_name(model_name):       # extension: timm's all-MLP models, MLP-Mixer and ResMLP (token mixing down the token axis)
-        return mixer_named(model_name, in_hw)
-    if is_cait_name(model_name):        # extension: timm's CaiT family (talking-heads attention, LayerScale, no prefix token)
-        return cait_named(model_name, in_hw)
-    if is_convit_name(model_name):      # extension: timm's ConViT family (gated positional attention, a class token that joins at block 10)
-        return convit_named(model_name, in_hw)
-    if is_xcit_name(model_name):        # extension: timm's XCiT family (cross-covariance attention, a convolutional stem, LPI)
-        return xcit_named(model_name, in_hw)
-    if is_twins_name(model_name):       # extension: timm's Twins family (sub-sampled global attention, window attention, PEG)
-        return twins_named(model_name, in_hw)
-    if is_beit_name(model_name):        # extension: timm's BEiT family (relative position bias in every block, LayerScale, no pos_embed)
-        return beit_named(model_name, in_hw)
+    for fam in FAMILIES:                # extension: the transformer surrogate of `get_vits()` (TPAMI_attack.py:88-98) and timm's families
+        if fam.in_build and fam.is_name(model_name):
+            return fam.named(model_name, in_hw)
     if model_name == "densenet":
         # The reference constructs densenet161 (`image_attacks.py:96-97`) but no attack class
         # has a densenet branch in `_find_target_layer` (`:260-271`): the hook lookup returns
@@ -3263,15 +3431,12 @@ def build(model_name: str, in_hw=(224, 224)) -> Graph:
 
 
 def build_surrogate(model_name: str, in_hw=(224, 224)):
-    """The name resolver of the image-guided attack classes and the command line: `build`, with timm's PiT family in front (three
-    stages pooled by a depthwise convolution, overlapping patches: `pit_named`), CoaT-Lite and TNT next to it.  `build` itself keeps its vocabulary as it stands --
-    there a `pit_*` name is an unknown name, as in the reference -- so a family is added here without changing what `build` answers."""
-    if is_pit_name(model_name):
-        return pit_named(model_name, in_hw)
-    if is_coat_name(model_name):            # (timm's CoaT-Lite: factorized attention, `coat_named`)
-        return coat_named(model_name, in_hw)
-    if is_tnt_name(model_name):             # (timm's TNT: an inner transformer over every patch's pixels, `tnt_named`)
-        return tnt_named(model_name, in_hw)
+    """The name resolver of the image-guided attack classes and the command line: `build`, with the families in front that `build` does
+    not know (`Family.in_build`: PiT, CoaT-Lite, TNT).  `build` itself keeps its vocabulary as it stands -- there a `pit_*` name is an
+    unknown name, as in the reference -- so a family is added here without changing what `build` answers."""
+    for fam in FAMILIES:
+        if not fam.in_build and fam.is_name(model_name):
+            return fam.named(model_name, in_hw)
     return build(model_name, in_hw)
 
 
@@ -3299,33 +3464,9 @@ def build_tiny(model_name: str, in_hw=(64, 64)) -> Graph:
         return squeezenet(4, in_hw, "squeezenet_tiny")
     if model_name in ("densenet121", "densenet161"):
         return densenet(8, (2, 3, 2, 2), 16, 2, in_hw, "densenet_tiny")
-    if model_name in VIT_MODELS:        # one test-size twin per token layout: plain, distilled (2 prefix tokens), patch 32
-        patch, _, _, _, _, n_prefix = VIT_MODELS[model_name]
-        return vit_tiny(in_hw, n_prefix, patch)
-    if model_name in SWIN_MODELS:
-        return swin_tiny(in_hw)
-    if model_name in CONVNEXT_MODELS:
-        return convnext_tiny_twin(in_hw)
-    if model_name in MIXER_MODELS:      # one twin per kind: the Mixer one follows the name's patch, the ResMLP one has 4 tokens
-        kind, patch, _, _ = MIXER_MODELS[model_name]
-        return mixer_tiny_twin(kind, patch if kind == "mixer" else 32, in_hw)
-    if model_name in CAIT_MODELS:
-        return cait_tiny_twin(in_hw)
-    if model_name in CONVIT_MODELS:
-        return convit_tiny_twin(in_hw)
-    if model_name in XCIT_MODELS:
-        return xcit_tiny_twin(in_hw)
-    if model_name in TWINS_MODELS:
-        return twins_tiny_twin(model_name, in_hw)
-    if model_name in BEIT_MODELS:
-        return beit_tiny_twin(model_name, in_hw)
-    if is_pit_name(model_name):
-        pit_named(model_name)               # (a name outside the table is refused with the served names)
-        return pit_tiny_twin(model_name, in_hw)
-    if is_coat_name(model_name):
-        coat_named(model_name)              # (a name outside the table is refused with the served names)
-        return coat_tiny_twin(model_name, in_hw)
-    if is_tnt_name(model_name):
-        tnt_named(model_name)               # (a name outside the table is refused with the served names)
-        return tnt_tiny_twin(model_name, in_hw)
+    for fam in FAMILIES:
+        if fam.is_name(model_name):
+            if model_name not in fam.models:
+                fam.named(model_name)           # (a name outside the table is refused with the served names)
+            return fam.tiny_twin(model_name, in_hw)
     return build(model_name, in_hw)

@@ -403,6 +403,12 @@ FAMILY_PROTOS = {"vit": _VIT_PROTOS, "swin": _SWIN_PROTOS, "convnext": _CONVNEXT
                  "tnt": _TNT_PROTOS}
 
 
+def family_config(word):
+    """The config struct of a transformer family: the one `_net_protos` gave its `i2v_<word>_create` a pointer to."""
+    argtypes = FAMILY_PROTOS[word][f"i2v_{word}_create"][0]
+    return next(a._type_ for a in argtypes if isinstance(getattr(a, "_type_", None), type) and issubclass(a._type_, C.Structure))
+
+
 def bind(cdll, protos=_PROTOS):
     for name, (args, res) in protos.items():
         fn = getattr(cdll, name)

@@ -39,22 +39,14 @@ def arg_parse(argv=None, ucf101=False):
     parser.add_argument("--mode", type=str, default="direction", help="diff_norm\\direction")
     parser.add_argument("--step_size", type=float, default=0.004, help="")
     parser.add_argument("--dropout", type=float, default=0.1, help="")
+    # the tables of served names behind the reference's own: the transformer families' (`graphs.FAMILIES`), the CNN ones behind Swin's
+    tables = [(f.help, f.models) for f in graphs.FAMILIES]
+    behind_swin = [f.word for f in graphs.FAMILIES].index("swin") + 1
+    tables[behind_swin:behind_swin] = [("torchvision's other ResNets, Wide ResNets and ResNeXts", graphs.RESNET_FAMILY), ("torchvision's MNASNets", graphs.MNASNET_MODELS),
+                   ("timm's SE-ResNets / SE-ResNeXts", graphs.SERESNET_FAMILY)]
     parser.add_argument("--direction_image_model", type=str, default="resnet",
-                        help="resnet, densenet, squeezenet, vgg, alexnet (added: resnet50, densenet121, densenet161, and timm's plain "
-                             "ViT / DeiT names at 224 x 224: " + ", ".join(graphs.VIT_MODELS) + "; and timm's Swin names at 224 x 224: "
-                             + ", ".join(graphs.SWIN_MODELS) + "; and torchvision's other ResNets, Wide ResNets and ResNeXts: "
-                             + ", ".join(graphs.RESNET_FAMILY) + "; and torchvision's MNASNets: " + ", ".join(graphs.MNASNET_MODELS)
-                             + "; and timm's SE-ResNets / SE-ResNeXts: " + ", ".join(graphs.SERESNET_FAMILY) + "; and timm's ConvNeXts at 224 x 224: "
-                             + ", ".join(graphs.CONVNEXT_MODELS) + "; and timm's MLP-Mixers and ResMLPs at 224 x 224: "
-                             + ", ".join(graphs.MIXER_MODELS) + "; and timm's CaiTs at 224 x 224: "
-                             + ", ".join(graphs.CAIT_MODELS) + "; and timm's ConViTs at 224 x 224: "
-                             + ", ".join(graphs.CONVIT_MODELS) + "; and timm's XCiTs at 224 x 224 with patch 16: "
-                             + ", ".join(graphs.XCIT_MODELS) + "; and timm's Twins (PCPVT and SVT) at 224 x 224: "
-                             + ", ".join(graphs.TWINS_MODELS) + "; and timm's BEiTs at 224 x 224 with patch 16: "
-                             + ", ".join(graphs.BEIT_MODELS) + "; and timm's PiTs at 224 x 224: "
-                             + ", ".join(graphs.PIT_MODELS) + "; and timm's serial CoaT-Lites at 224 x 224: "
-                             + ", ".join(graphs.COAT_MODELS) + "; and timm's TNTs at 224 x 224: "
-                             + ", ".join(graphs.TNT_MODELS) + ")")
+                        help="resnet, densenet, squeezenet, vgg, alexnet (added: resnet50, densenet121, densenet161, and "
+                             + "; and ".join(f"{phrase}: " + ", ".join(names) for phrase, names in tables) + ")")
     # additions (not in the reference)
     parser.add_argument("--anno", type=str, default=os.environ.get("I2V_ANNO", ""),
                         help="sample list csv `path,gt_label,clip_index` (the reference's kinetics400_attack_samples.csv, utils.py:29); without it 400 synthetic names with labels 0..399 are used")
@@ -85,29 +77,18 @@ def arg_parse(argv=None, ucf101=False):
     if not ucf101:
         check_video_flags(parser, args)
     if args.attack_method in ("ImageGuidedStd_Adam", "ImageGuidedFMDirection_Adam"):
-        # a ViT / DeiT or a Swin name: refused here with the served names when it is not offered, and --depth checked against the spec's
-        # hooked blocks / stages
-        for is_name, named, hooked in ((graphs.is_vit_name, graphs.vit_named, "blocks {}"),
-                                       (graphs.is_swin_name, graphs.swin_named, "the last block of stages {}"),
-                                       (graphs.is_convnext_name, graphs.convnext_named, "the last block of stages {}"),
-                                       (graphs.is_mixer_name, graphs.mixer_named, "blocks {}"),
-                                       (graphs.is_cait_name, graphs.cait_named, "blocks {}"),
-                                       (graphs.is_convit_name, graphs.convit_named, "blocks {}"),
-                                       (graphs.is_xcit_name, graphs.xcit_named, "blocks {}"),
-                                       (graphs.is_twins_name, graphs.twins_named, "the last block of stages {}"),
-                                       (graphs.is_beit_name, graphs.beit_named, "blocks {}"),
-                                       (graphs.is_pit_name, graphs.pit_named, "blocks {}, numbered across the stages"),
-                                       (graphs.is_coat_name, graphs.coat_named, "the last block of stages {}"),
-                                       (graphs.is_tnt_name, graphs.tnt_named, "the outer stream after blocks {}")):
-            if not is_name(args.direction_image_model):
+        # a name of a transformer family: refused here with the served names when it is not offered, and --depth checked against the
+        # spec's hooked blocks / stages
+        for fam in graphs.FAMILIES:
+            if not fam.is_name(args.direction_image_model):
                 continue
             try:
-                spec = named(args.direction_image_model, (args.hw, args.hw))
+                spec = fam.named(args.direction_image_model, (args.hw, args.hw))
             except ValueError as e:
                 parser.error(f"--direction_image_model: {e}")
             if args.depth not in spec.hooks:
                 parser.error(f"--depth {args.depth}: {spec.arch} hooks depths {sorted(spec.hooks)} "
-                             f"({hooked.format([spec.hooks[d] for d in sorted(spec.hooks)])})")
+                             f"({fam.hooked.format([spec.hooks[d] for d in sorted(spec.hooks)])})")
     if args.synthetic_weights:
         os.environ["I2V_SYNTHETIC_WEIGHTS"] = "1"
     args.adv_path = os.path.join(OPT_PATH, "{}-{}-{}-{}".format("Image", args.attack_method, args.step, args.file_prefix))

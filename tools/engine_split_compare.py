@@ -7,9 +7,9 @@
         (kind Cd K HWg frames pw, GFLOP, MB).  I2V_AUTOTUNE=0 makes the plan deterministic.  With a third argument, the path of a
         host-simulation library (tests/hostsim/libi2v_hostsim.so), the same on the CPU with the tiny graphs of the tests.
     I2V_LIB=<library> python tools/engine_split_compare.py tokens OUT.json
-        the transformer families on their test-size twins (graphs.build_tiny at its smallest frame, synthetic weights of seed 0), ViT, DeiT distilled,
-        Swin, ConvNeXt, Mixer, ResMLP, CaiT, ConViT, XCiT, Twins-PCPVT, Twins-SVT and BEiT, and the I2V_BEIT_ATTN=0 / I2V_TWINS_ATTN=0
-        routes: two steps of the adaptive attack (AENS_I2V_MF) with hooks at the shallowest and the deepest depth on one clip of 3
+        the transformer families on their test-size twins (graphs.build_tiny, synthetic weights of seed 0), ViT, DeiT distilled, Swin,
+        ConvNeXt, Mixer, ResMLP, CaiT, ConViT, XCiT, Twins-PCPVT, Twins-SVT, BEiT, PiT (64 and 70), CoaT-Lite and TNT (64 and 48), and the
+        I2V_BEIT_ATTN=0 / I2V_TWINS_ATTN=0 / I2V_PIT_ATTN=0 routes: two steps of the adaptive attack (AENS_I2V_MF) with hooks at the shallowest and the deepest depth on one clip of 3
         frames, then on its first 2 frames with the same nets (planned for 3), and per run workspace_bytes() and a sha256 of every hook
         activation, every hook gradient, the input gradient and the adversarial clip.  With a third argument, the path of a
         host-simulation library, the families that library exports, on the CPU.
@@ -64,15 +64,17 @@ def plan(out_path, hostsim=None):
     print({k: (v["workspace_bytes"], v["fusion_info"], v["dump_lines"]) for k, v in record.items()})
 
 
-# (record name, model name the twin stands for, the twin's smallest frame side, environment of the run)
-TOKEN_CASES = [("vit", "vit_base_patch16_224", 64, {}), ("deit_distilled", "deit_tiny_distilled_patch16_224", 64, {}),
-               ("swin", "swin_tiny_patch4_window7_224", 64, {}), ("convnext", "convnext_tiny", 64, {}), ("mixer", "mixer_b16_224", 64, {}),
-               ("resmlp", "resmlp_12_224", 64, {}), ("cait", "cait_xxs24_224", 64, {}), ("convit", "convit_tiny", 64, {}),
-               ("xcit", "xcit_nano_12_p16_224", 64, {}), ("twins_pcpvt", "twins_pcpvt_small", 64, {}),
-               ("twins_svt", "twins_svt_small", 128, {}), ("beit", "beit_base_patch16_224", 64, {}),
-               ("twins_pcpvt_attn0", "twins_pcpvt_small", 64, {"I2V_TWINS_ATTN": "0"}),
-               ("twins_svt_attn0", "twins_svt_small", 128, {"I2V_TWINS_ATTN": "0"}),
-               ("beit_attn0", "beit_base_patch16_224", 64, {"I2V_BEIT_ATTN": "0"})]
+# (record name, the word in the family's entry names, model name the twin stands for, the twin's frame side, environment of the run)
+TOKEN_CASES = [("vit", "vit", "vit_base_patch16_224", 64, {}), ("deit_distilled", "vit", "deit_tiny_distilled_patch16_224", 64, {}),
+               ("swin", "swin", "swin_tiny_patch4_window7_224", 64, {}), ("convnext", "convnext", "convnext_tiny", 64, {}),
+               ("mixer", "mixer", "mixer_b16_224", 64, {}), ("resmlp", "mixer", "resmlp_12_224", 64, {}), ("cait", "cait", "cait_xxs24_224", 64, {}),
+               ("convit", "convit", "convit_tiny", 64, {}), ("xcit", "xcit", "xcit_nano_12_p16_224", 64, {}),
+               ("twins_pcpvt", "twins", "twins_pcpvt_small", 64, {}), ("twins_svt", "twins", "twins_svt_small", 128, {}),
+               ("beit", "beit", "beit_base_patch16_224", 64, {}), ("pit", "pit", "pit_s_224", 64, {}), ("pit_70", "pit", "pit_s_224", 70, {}),
+               ("coat", "coat", "coat_lite_tiny", 64, {}), ("tnt", "tnt", "tnt_s_patch16_224", 64, {}), ("tnt_48", "tnt", "tnt_s_patch16_224", 48, {}),
+               ("twins_pcpvt_attn0", "twins", "twins_pcpvt_small", 64, {"I2V_TWINS_ATTN": "0"}),
+               ("twins_svt_attn0", "twins", "twins_svt_small", 128, {"I2V_TWINS_ATTN": "0"}),
+               ("beit_attn0", "beit", "beit_base_patch16_224", 64, {"I2V_BEIT_ATTN": "0"}), ("pit_attn0", "pit", "pit_s_224", 64, {"I2V_PIT_ATTN": "0"})]
 
 
 def tokens(out_path, hostsim=None):
@@ -80,14 +82,15 @@ def tokens(out_path, hostsim=None):
     import torch
     from i2v_amd import attacks, graphs, lib
     from i2v_amd.engine import Engine
-    families = ("vit", "swin", "convnext", "mixer", "cait", "convit", "xcit", "twins", "beit")      # the word in a family's entry names
+    # the word in a family's entry names: the rows of the family table (a commit from before the table has `lib.FAMILY_PROTOS` only)
+    families = [f.word for f in graphs.FAMILIES] if hasattr(graphs, "FAMILIES") else list(lib.FAMILY_PROTOS)
     if hostsim:
         import ctypes
         cd = ctypes.CDLL(hostsim)
         capi = lib.bind(cd)
         have = [f for f in families if hasattr(cd, f"i2v_{f}_create")]
         for f in have:
-            lib.bind(capi, getattr(lib, f"_{f.upper()}_PROTOS"))
+            lib.bind(capi, lib.FAMILY_PROTOS[f])
         eng = Engine("cpu", capi=capi)
     else:
         eng, have = Engine("cuda:0"), families
@@ -96,10 +99,10 @@ def tokens(out_path, hostsim=None):
         return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
     record = {}
-    for name, model, side, env in TOKEN_CASES:
+    for name, word, model, side, env in TOKEN_CASES:
         vid = torch.randn(1, 3, 3, side, side, generator=torch.Generator().manual_seed(0))
         spec = graphs.build_tiny(model, (side, side))
-        if type(spec).__name__[:-4].lower() not in have:      # (VitSpec -> "vit": the word in the family's entry names)
+        if word not in have:
             continue
         common = sorted(set(spec.hooks) & set(graphs.build_tiny(model, (224, 224)).hooks))      # (the attack checks depths at 224 x 224)
         os.environ.update(env)                                 # read when the net is planned
