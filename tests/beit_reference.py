@@ -11,10 +11,10 @@ bias) is tested, not assumed.
              a = a + table[index].view(T, T, heads).permute(2, 0, 1);  softmax;  a @ v
 `norm` / `fc_norm` and `head` lie behind every hook and are not restated.
 """
-from typing import Sequence
-
 import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 
 def relative_position_index(g: int) -> torch.Tensor:
@@ -87,24 +87,6 @@ def streams(x, sd, spec, n_blocks, skip=()):
     return outs
 
 
-class BeitReference:
-    """The interface of the other references (`forward` -> the hooked features as (frames, D), `backward` of hook gradients -> the input
-    gradient by autograd), which `oracle.restate.run_attack` drives.  `skip` names what the sensitivity checks leave out: "bias" (a
-    table of zeros), "gamma" (LayerScale of 1)."""
-
-    def __init__(self, spec, state_dict, hook_blocks: Sequence[int], dtype=torch.float64, device="cpu", skip=()):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_blocks)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self.skip = tuple(skip)
-        self._x = self._feats = None
-
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        outs = streams(self._x, self.sd, self.spec, max(self.hooks) + 1, self.skip)
-        self._feats = [outs[b].reshape(x.shape[0], -1) for b in self.hooks]
-        return [f.detach() for f in self._feats]
-
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+#: `skip` names what the sensitivity checks leave out: "bias" (a table of zeros), "gamma" (LayerScale of 1).
+class BeitReference(StreamsReference):
+    streams = staticmethod(streams)

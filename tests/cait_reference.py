@@ -8,10 +8,9 @@ written as timm writes it -- the two `nn.Linear`s over the head axis applied to 
                           a = proj_w(a over heads);  out = proj((a @ v) heads joined)
 The class-attention blocks, `norm` and `head` lie behind every hook and are not restated.
 """
-from typing import Sequence
-
-import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 
 def talking_heads(qkv, heads, scale, wl, bl, ww, bw, identity_mix: bool = False):
@@ -47,27 +46,16 @@ def block(x, sd, spec, i: int, identity_mix: bool = False, gamma=None):
     return x + g2 * t
 
 
-class CaitReference:
-    """The interface of the other references (`forward` -> the hooked features as (frames, D), `backward` of hook gradients -> the input
-    gradient by autograd), which `oracle.restate.run_attack` drives.  `identity_mix`: both head mixes replaced by the identity with zero
-    biases; `gamma`: both LayerScale vectors replaced by this constant -- what the sensitivity checks compare against."""
+def streams(x, sd, spec, n_blocks, identity_mix: bool = False, gamma=None):
+    """The residual streams behind the blocks 0 .. n_blocks - 1, each (frames, tokens, dim)."""
+    t, outs = stem(x, sd, spec), []
+    for i in range(n_blocks):
+        t = block(t, sd, spec, i, identity_mix, gamma)
+        outs.append(t)
+    return outs
 
-    def __init__(self, spec, state_dict, hook_blocks: Sequence[int], dtype=torch.float64, device="cpu", identity_mix: bool = False, gamma=None):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_blocks)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self.identity_mix, self.gamma = identity_mix, gamma
-        self._x = self._feats = None
 
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        t, outs = stem(self._x, self.sd, self.spec), {}
-        for i in range(max(self.hooks) + 1):
-            t = block(t, self.sd, self.spec, i, self.identity_mix, self.gamma)
-            outs[i] = t
-        self._feats = [outs[b].reshape(x.shape[0], -1) for b in self.hooks]
-        return [f.detach() for f in self._feats]
-
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+#: What the sensitivity checks compare against: `identity_mix` -- both head mixes replaced by the identity with zero biases; `gamma` --
+#: both LayerScale vectors replaced by this constant.
+class CaitReference(StreamsReference):
+    streams = staticmethod(streams)

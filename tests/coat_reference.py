@@ -14,10 +14,10 @@ are tested, not assumed.
              (3 x 3, 5 x 5, 7 x 7 depthwise, "same" padding, bias)
 `norm*`, `head` and `aggregate` lie behind every hook and are not restated.
 """
-from typing import Sequence
-
 import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 def crpe(v, filters, biases, g, prefix=1):
     """E of v (frames, prefix + g^2, C): `filters[i]` (n_i, 1, K_i, K_i) on the next n_i channels; zeros on the prefix rows."""
@@ -101,24 +101,7 @@ def streams(x, sd, spec, n_stages, skip=()):
     return outs
 
 
-class CoatReference:
-    """The interface of the other references (`forward` -> the hooked features as (frames, D), `backward` of hook gradients -> the input
-    gradient by autograd), which `oracle.restate.run_attack` drives.  `skip` names what the sensitivity checks leave out: "cpe" (no
-    convolutional position encoding), "crpe0" / "crpe1" / "crpe2" (one window's filter zero), "cls" (class tokens of zeros)."""
-
-    def __init__(self, spec, state_dict, hook_stages: Sequence[int], dtype=torch.float64, device="cpu", skip=()):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_stages)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self.skip = tuple(skip)
-        self._x = self._feats = None
-
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        outs = streams(self._x, self.sd, self.spec, max(self.hooks) + 1, self.skip)
-        self._feats = [outs[k].reshape(x.shape[0], -1) for k in self.hooks]
-        return [f.detach() for f in self._feats]
-
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+#: `skip` names what the sensitivity checks leave out: "cpe" (no convolutional position encoding), "crpe0" / "crpe1" / "crpe2" (one
+#: window's filter zero), "cls" (class tokens of zeros).
+class CoatReference(StreamsReference):
+    streams = staticmethod(streams)

@@ -12,10 +12,10 @@ so that the folds of `ConvitSpec.native_arrays` (no bias, no division, one stack
   MHSA (blocks >= local)  q, k, v = qkv(x) split (3, heads, dh);  a = softmax((q @ k^T) * scale);  out = proj((a @ v) heads joined)
 `norm` and `head` lie behind every hook and are not restated.
 """
-from typing import Sequence
-
 import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 
 def rel_indices(grid: int, dtype=torch.float64):
@@ -81,32 +81,19 @@ def block(x, sd, spec, i: int, local: bool, rel, plain: bool = False, swap_xy: b
     return x + F.linear(F.gelu(F.linear(t, sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"])), sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"])
 
 
-class ConvitReference:
-    """The interface of the other references (`forward` -> the hooked features as (frames, D), `backward` of hook gradients -> the input
-    gradient by autograd), which `oracle.restate.run_attack` drives.  What the sensitivity checks compare against: `plain` -- every GPSA
-    block computes content attention only (c = 1 with a zero table); `swap_xy` -- the x and y columns of `pos_proj.weight` exchanged.
-    The class token joins before block `spec.local_blocks`: a spec with another `local_blocks` moves the join."""
+def streams(x, sd, spec, n_blocks, plain: bool = False, swap_xy: bool = False):
+    """The residual streams behind the blocks 0 .. n_blocks - 1, each (frames, tokens, dim)."""
+    rel = rel_indices(spec.grid, x.dtype).to(x.device)
+    t, outs = stem(x, sd, spec), []
+    for i in range(n_blocks):
+        if i == spec.local_blocks:          # the class token joins here: a spec with another `local_blocks` moves the join
+            t = torch.cat([sd["cls_token"].expand(t.shape[0], -1, -1), t], dim=1)
+        t = block(t, sd, spec, i, i < spec.local_blocks, rel, plain, swap_xy)
+        outs.append(t)
+    return outs
 
-    def __init__(self, spec, state_dict, hook_blocks: Sequence[int], dtype=torch.float64, device="cpu", plain: bool = False,
-                 swap_xy: bool = False):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_blocks)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self.plain, self.swap_xy = plain, swap_xy
-        self.rel = rel_indices(spec.grid, dtype).to(self.device)
-        self._x = self._feats = None
 
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        t, outs = stem(self._x, self.sd, self.spec), {}
-        for i in range(max(self.hooks) + 1):
-            if i == self.spec.local_blocks:
-                t = torch.cat([self.sd["cls_token"].expand(t.shape[0], -1, -1), t], dim=1)
-            t = block(t, self.sd, self.spec, i, i < self.spec.local_blocks, self.rel, self.plain, self.swap_xy)
-            outs[i] = t
-        self._feats = [outs[b].reshape(x.shape[0], -1) for b in self.hooks]
-        return [f.detach() for f in self._feats]
-
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+#: What the sensitivity checks compare against: `plain` -- every GPSA block computes content attention only (c = 1 with a zero table);
+#: `swap_xy` -- the x and y columns of `pos_proj.weight` exchanged.
+class ConvitReference(StreamsReference):
+    streams = staticmethod(streams)

@@ -8,8 +8,9 @@ flattened -- the layout the engine hands to the loss kernels.
 """
 from typing import Sequence
 
-import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 
 def layer_norm_c(x, w, b, eps):
@@ -55,23 +56,10 @@ def dwconv_token_major(x, filt, bias=None):
     return F.conv2d(x.permute(0, 3, 1, 2), w, bias, padding=3, groups=C).permute(0, 2, 3, 1)
 
 
-class ConvNextReference:
-    """The interface of the other references (`forward` -> the hooked features as (frames, D), `backward` of hook gradients -> the input
-    gradient by autograd), which `oracle.restate.run_attack` drives."""
+def streams(x, sd, spec, n_stages, unit_gamma: bool = False):
+    """The planes behind the stages 0 .. n_stages - 1, token-major: each (frames, H, W, C)."""
+    return [o.permute(0, 2, 3, 1) for o in run_stages(stem(x, sd, spec), sd, spec, list(range(n_stages)), unit_gamma)]
 
-    def __init__(self, spec, state_dict, hook_stages: Sequence[int], dtype=torch.float64, device="cpu", unit_gamma: bool = False):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_stages)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self.unit_gamma = unit_gamma
-        self._x = self._feats = None
 
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        outs = run_stages(stem(self._x, self.sd, self.spec), self.sd, self.spec, self.hooks, self.unit_gamma)
-        self._feats = [o.permute(0, 2, 3, 1).reshape(x.shape[0], -1) for o in outs]      # token-major
-        return [f.detach() for f in self._feats]
-
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+class ConvNextReference(StreamsReference):
+    streams = staticmethod(streams)

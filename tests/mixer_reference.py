@@ -8,10 +8,10 @@ timm writes it, with the two transposes around an `nn.Linear`-style product -- n
   ResBlock (ResMLP)    x = x + ls1 * linear_tokens(Affine1(x)^T)^T            Affine(x) = alpha * x + beta
                        x = x + ls2 * mlp_channels(Affine2(x))
 """
-from typing import Sequence
-
 import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 
 def stem(x, sd, spec):
@@ -50,31 +50,16 @@ def token_mix(z, residual, w1, b1, w2=None, b2=None, in_scale=None, in_shift=Non
     return residual + (u if out_scale is None else out_scale * u)
 
 
-class MixerReference:
-    """The interface of the other references (`forward` -> the hooked features as (frames, D), `backward` of hook gradients -> the input
-    gradient by autograd), which `oracle.restate.run_attack` drives.  `unit_ls` / `no_norm2`: a ResMLP with its layer scales set to one,
-    or without the affine in front of its channel MLP -- what a dropped fold would compute."""
+def streams(x, sd, spec, n_blocks, unit_ls: bool = False, no_norm2: bool = False):
+    """The residual streams behind the blocks 0 .. n_blocks - 1, each (frames, tokens, dim)."""
+    t, outs = stem(x, sd, spec), []
+    for i in range(n_blocks):
+        t = mixer_block(t, sd, spec, i) if spec.kind == "mixer" else res_block(t, sd, spec, i, unit_ls, no_norm2)
+        outs.append(t)
+    return outs
 
-    def __init__(self, spec, state_dict, hook_blocks: Sequence[int], dtype=torch.float64, device="cpu", unit_ls: bool = False,
-                 no_norm2: bool = False):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_blocks)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self.unit_ls, self.no_norm2 = unit_ls, no_norm2
-        self._x = self._feats = None
 
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        t, outs = stem(self._x, self.sd, self.spec), {}
-        for i in range(max(self.hooks) + 1):
-            if self.spec.kind == "mixer":
-                t = mixer_block(t, self.sd, self.spec, i)
-            else:
-                t = res_block(t, self.sd, self.spec, i, self.unit_ls, self.no_norm2)
-            outs[i] = t
-        self._feats = [outs[b].reshape(x.shape[0], -1) for b in self.hooks]
-        return [f.detach() for f in self._feats]
-
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+#: `unit_ls` / `no_norm2`: a ResMLP with its layer scales set to one, or without the affine in front of its channel MLP -- what a
+#: dropped fold would compute.
+class MixerReference(StreamsReference):
+    streams = staticmethod(streams)

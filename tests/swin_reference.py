@@ -16,6 +16,7 @@ from typing import Sequence
 import torch
 import torch.nn.functional as F
 
+from tests.family_harness import StreamsReference
 from tests.vit_family_reference import gelu, layer_norm
 
 
@@ -125,19 +126,10 @@ def run_stages(t, sd, spec, hook_stages: Sequence[int]):
     return [outs[s] for s in hook_stages]
 
 
-class SwinReference:
-    def __init__(self, spec, state_dict, hook_stages: Sequence[int], dtype=torch.float64, device="cpu"):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_stages)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self._x = self._feats = None
+def streams(x, sd, spec, n_stages):
+    """The streams behind the stages 0 .. n_stages - 1 (the hooks of this family number stages), each before its patch merging."""
+    return run_stages(embed(x, sd, spec), sd, spec, list(range(n_stages)))
 
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        outs = run_stages(embed(self._x, self.sd, self.spec), self.sd, self.spec, self.hooks)
-        self._feats = [o.reshape(x.shape[0], -1) for o in outs]
-        return [f.detach() for f in self._feats]
 
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+class SwinReference(StreamsReference):
+    streams = staticmethod(streams)

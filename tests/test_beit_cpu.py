@@ -22,6 +22,7 @@ from oracle import restate
 from tests import beit_reference as br
 from tests import make_beit_fixtures as mk
 from tests.beit_reference import BeitReference
+from tests.family_harness import bound, check_net, check_trajectory, rand as _rand, rel as _rel, run_twin as _run_twin
 from tests.hostsim_util import hostsim_engine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,18 +32,6 @@ TABLE = {"beit_base_patch16_224": (16, 768, 12, 3072, 12), "beit_large_patch16_2
 NAMES = sorted(TABLE)
 BASE, LARGE = "beit_base_patch16_224", "beit_large_patch16_224"
 NET_FLOOR, FWD_FLOOR, BWD_FLOOR = 1e-5, 1e-6, 1e-5
-
-
-def bound(fp32_err, floor=NET_FLOOR):
-    return max(floor, 4.0 * fp32_err)
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
 
 
 # ---- the specs ---------------------------------------------------------------------------------------------------------------------
@@ -379,27 +368,6 @@ def test_planned_bytes_are_counted_in_64_bits_and_grow_as_the_saves_do():
 
 
 # ---- the planner (csrc/i2v_beit.cpp) on the host simulation ------------------------------------------------------------------------
-def _write_hook_grads(net, hg):
-    for hi, g in zip(net.hooks, hg):
-        flat = g.float().reshape(g.shape[0], -1).contiguous()
-        for n in range(flat.shape[0]):
-            C.memmove(hi.grad + 4 * n * hi.grad_stride, flat[n].data_ptr(), 4 * hi.D)
-
-
-def _run_twin(eng, spec, sd, hooks, x, hg, max_frames=None):
-    net = eng.build_beit_net(spec, sd, hooks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(hooks, max_frames or x.shape[0])      # the formula against the plan
-    xf = x.float().contiguous()
-    net.forward(xf)
-    feats = [net.save_hook(i, x.shape[0]).reshape(x.shape[0], -1) for i in range(len(hooks))]
-    assert all(f.shape[1] == spec.hook_dim == hi.D for f, hi in zip(feats, net.hooks))
-    _write_hook_grads(net, hg)
-    gx = torch.empty_like(xf)
-    net.backward(gx)
-    net.close()
-    return feats, gx
-
-
 @pytest.fixture(scope="module")
 def twin_refs():
     """The float64 reference of each twin case, computed once: label -> (spec, sd, x, hooks, features, hook gradients, input gradient)."""
@@ -416,15 +384,6 @@ def twin_refs():
     return out
 
 
-def _check(label, feats, gx, rf, want_gx):
-    fp = FP32[label]
-    errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, want_gx)
-    print(f"{label} vs float64: hooks {errs} grad {gerr}; fp32 CPU: {fp['hooks']} {fp['grad']}")
-    for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
-
-
 @pytest.mark.parametrize("label", sorted(mk.TWINS))
 def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
     """Features at all four depths and the input gradient with all four hook gradients flowing; reruns and a net planned for 5 frames
@@ -433,7 +392,7 @@ def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
     spec, sd, x, hooks, rf, hg, want_gx = twin_refs[label]
     assert spec.arch == label
     feats, gx = _run_twin(eng, spec, sd, hooks, x, hg)
-    _check(label, feats, gx, rf, want_gx)
+    check_net(label, feats, gx, rf, want_gx, FP32[label], NET_FLOOR)
     f1, g1 = _run_twin(eng, spec, sd, hooks, x[:1], [h[:1] for h in hg])
     assert all(torch.equal(a[:1], b) for a, b in zip(feats, f1)) and torch.equal(gx[:1], g1)
     feats2, gx2 = _run_twin(eng, spec, sd, hooks, x, hg, max_frames=5)
@@ -444,7 +403,7 @@ def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
     assert torch.equal(fa[0], feats[1])
     ref1 = BeitReference(spec, sd, [hooks[1]])
     ref1.forward(x)
-    assert _rel(ga, ref1.backward([hg[1]])) < bound(FP32[label]["grad"])
+    assert _rel(ga, ref1.backward([hg[1]])) < bound(FP32[label]["grad"], NET_FLOOR)
 
 
 @pytest.mark.parametrize("label", ["beit_test", "beit_test_96"])
@@ -459,7 +418,7 @@ def test_twin_on_the_shared_launch_route_against_float64(eng, twin_refs, label, 
     T, ld = spec.tokens, (spec.tokens + 3) // 4 * 4
     probs = x.shape[0] * spec.heads * T * ld
     assert spec.workspace_bytes(hooks, x.shape[0]) - plain == 4 * ((spec.blocks + 1) * probs + spec.blocks * spec.heads * T * ld)
-    _check(label, feats, gx, rf, want_gx)
+    check_net(label, feats, gx, rf, want_gx, FP32[label], NET_FLOOR)
     f1, g1 = _run_twin(eng, spec, sd, hooks, x[:1], [h[:1] for h in hg])
     assert all(torch.equal(a[:1], b) for a, b in zip(feats, f1)) and torch.equal(gx[:1], g1)
     monkeypatch.delenv("I2V_BEIT_ATTN")
@@ -475,7 +434,7 @@ def test_leaving_the_new_arithmetic_out_is_seen(eng, twin_refs, what):
     feats, _ = _run_twin(eng, spec, sd, hooks, x, hg)
     without = BeitReference(spec, sd, hooks, skip=(what,)).forward(x)
     for got, want, wo, cpu in zip(feats, rf, without, FP32["beit_test"]["hooks"]):
-        assert _rel(wo, want) > 100 * bound(cpu) and _rel(got, wo) > 100 * bound(cpu)
+        assert _rel(wo, want) > 100 * bound(cpu, NET_FLOOR) and _rel(got, wo) > 100 * bound(cpu, NET_FLOOR)
     blind = dict(sd)                                                       # ... and through the packing: the same state dict with the term silenced
     for i in range(spec.blocks):
         p = f"blocks.{i}."
@@ -485,7 +444,7 @@ def test_leaving_the_new_arithmetic_out_is_seen(eng, twin_refs, what):
             blind[p + "gamma_1"], blind[p + "gamma_2"] = torch.ones(spec.dim), torch.ones(spec.dim)
     fb, _ = _run_twin(eng, spec, blind, hooks, x, hg)
     for got, b, wo, cpu in zip(feats, fb, without, FP32["beit_test"]["hooks"]):
-        assert _rel(b, got) > 100 * bound(cpu) and _rel(b, wo) < bound(cpu)
+        assert _rel(b, got) > 100 * bound(cpu, NET_FLOOR) and _rel(b, wo) < bound(cpu, NET_FLOOR)
 
 
 def test_planner_refusals_on_the_host_simulation(eng):
@@ -518,9 +477,7 @@ def test_i2v_trajectory_on_the_twin_matches_the_reference(eng):
     atk = attacks.ImageGuidedFMDirection_Adam([BASE], depth=4, step_size=0.005, steps=4, engine=eng, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(1, dtype=torch.long), ["t"])
     g = graphs.build_tiny(BASE, (64, 64))
-    ref = restate.run_attack([BeitReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(4)], dtype=torch.float32)], vid, steps=4, step_size=0.005)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"]).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, BeitReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(4)], dtype=torch.float32), vid, rtol=2e-4, steps=4)
 
 
 def test_aens_of_the_twin_with_tiny_resnet_matches_the_oracle(eng):

@@ -22,6 +22,7 @@ from oracle import restate
 from tests import convit_reference as cr
 from tests import make_convit_fixtures as mk
 from tests.convit_reference import ConvitReference
+from tests.family_harness import bound, check_trajectory, rand as _rand, rel as _rel, run_twin as _run_twin
 from tests.hostsim_util import hostsim_engine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,18 +32,6 @@ TABLE = {"convit_tiny": (192, 4), "convit_small": (432, 9), "convit_base": (768,
 NAMES = sorted(TABLE)
 TINY, SMALL = "convit_tiny", "convit_small"
 NET_FLOOR, FWD_FLOOR, BWD_FLOOR = 1e-5, 1e-6, 1e-5
-
-
-def bound(fp32_err, floor=NET_FLOOR):
-    return max(floor, 4.0 * fp32_err)
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
 
 
 # ---- the specs ---------------------------------------------------------------------------------------------------------------------
@@ -335,27 +324,6 @@ def test_planned_bytes_are_counted_in_64_bits_and_grow_as_the_saves_do():
 
 
 # ---- the planner (csrc/i2v_convit.cpp) on the host simulation ----------------------------------------------------------------------
-def _write_hook_grads(net, hg):
-    for hi, g in zip(net.hooks, hg):
-        flat = g.float().reshape(g.shape[0], -1).contiguous()
-        for n in range(flat.shape[0]):
-            C.memmove(hi.grad + 4 * n * hi.grad_stride, flat[n].data_ptr(), 4 * hi.D)
-
-
-def _run_twin(eng, spec, sd, blocks, x, hg, max_frames=None):
-    net = eng.build_convit_net(spec, sd, blocks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(blocks, max_frames or x.shape[0])      # the formula against the plan
-    xf = x.float().contiguous()
-    net.forward(xf)
-    feats = [net.save_hook(i, x.shape[0]).reshape(x.shape[0], -1) for i in range(len(blocks))]
-    assert all(f.shape[1] == spec.hook_dim(b) == hi.D for f, b, hi in zip(feats, blocks, net.hooks))
-    _write_hook_grads(net, hg)
-    gx = torch.empty_like(xf)
-    net.backward(gx)
-    net.close()
-    return feats, gx
-
-
 @pytest.fixture(scope="module")
 def twin_refs():
     """The float64 reference of each twin case, computed once: label -> (spec, sd, x, features, hook gradients, input gradient)."""
@@ -384,8 +352,8 @@ def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
     errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, want_gx)
     print(f"{label} on the host simulation vs float64: hooks {errs} grad {gerr}; fp32 CPU: {fp['hooks']} {fp['grad']}")
     for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
+        assert e < bound(cpu, NET_FLOOR)
+    assert gerr < bound(fp["grad"], NET_FLOOR)
     feats2, gx2 = _run_twin(eng, spec, sd, blocks, x, hg, max_frames=5)
     assert all(torch.equal(a, b) for a, b in zip(feats, feats2)) and torch.equal(gx, gx2)
     f1, g1 = _run_twin(eng, spec, sd, blocks, x[:1], [h[:1] for h in hg])
@@ -397,7 +365,7 @@ def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
         assert torch.equal(fa[0], feats[i])
         ref1 = ConvitReference(spec, sd, [blocks[i]])
         ref1.forward(x)
-        assert _rel(ga, ref1.backward([hg[i]])) < bound(fp["grad"])
+        assert _rel(ga, ref1.backward([hg[i]])) < bound(fp["grad"], NET_FLOOR)
 
 
 def test_the_cases_can_see_the_gate_the_grid_and_the_join(eng, twin_refs):
@@ -412,17 +380,17 @@ def test_the_cases_can_see_the_gate_the_grid_and_the_join(eng, twin_refs):
     plain = ConvitReference(spec, sd, blocks, plain=True).forward(x)
     swapped = ConvitReference(spec, sd, blocks, swap_xy=True).forward(x)
     for got, want, pl, sw, cpu in zip(feats, rf, plain, swapped, FP32["convit_test"]["hooks"]):
-        b = bound(cpu)
+        b = bound(cpu, NET_FLOOR)
         assert _rel(pl, want) > 100 * b and _rel(sw, want) > 100 * b
         assert _rel(got, pl) > 100 * b and _rel(got, sw) > 100 * b
     spec_e, sd_e = mk.early_join(spec, sd)
     early = ConvitReference(spec_e, sd_e, blocks).forward(x)
     assert early[2].shape[1] == 17 * 32 != rf[2].shape[1] and early[3].shape == rf[3].shape
-    b = bound(FP32["convit_test"]["hooks"][3])
+    b = bound(FP32["convit_test"]["hooks"][3], NET_FLOOR)
     assert _rel(early[3], rf[3]) > 100 * b and _rel(feats[3], early[3]) > 100 * b
     got_e, _ = _run_twin(eng, spec_e, sd_e, blocks, x, [_rand(*f.shape, seed=40 + i) for i, f in enumerate(early)])
     for g, w, cpu in zip(got_e, early, FP32[mk.EARLY]["hooks"]):
-        assert _rel(g, w) < bound(cpu)
+        assert _rel(g, w) < bound(cpu, NET_FLOOR)
 
 
 def test_planner_refusals_on_the_host_simulation(eng):
@@ -451,10 +419,7 @@ def test_i2v_trajectory_on_the_twin_matches_the_reference(eng):
                                               weight_seed=0)
     adv = atk(vid, torch.zeros(1, dtype=torch.long), ["t"])
     g = graphs.build_tiny(SMALL, (64, 64))
-    ref = restate.run_attack([ConvitReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(4)], dtype=torch.float32)], vid,
-                             steps=4, step_size=0.005)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"]).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, ConvitReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(4)], dtype=torch.float32), vid, rtol=2e-4, steps=4)
 
 
 def test_aens_of_the_twin_with_tiny_resnet_matches_the_oracle(eng):

@@ -22,6 +22,7 @@ from tests import convnext_reference as cr
 from tests import make_convnext_fixtures as mk
 from tests import swin_reference as sr
 from tests.convnext_reference import ConvNextReference
+from tests.family_harness import bound, check_trajectory, rand as _rand, rel as _rel, run_twin as _run_twin
 from tests.hostsim_util import hostsim_engine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,18 +33,6 @@ TABLE = {"convnext_tiny": (96, (3, 3, 9, 3)), "convnext_small": (96, (3, 3, 27, 
 NAMES = sorted(TABLE)
 TINY = "convnext_tiny"
 FLOOR = 1e-5
-
-
-def bound(fp32_err):
-    return max(FLOOR, 4.0 * fp32_err)
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -204,8 +193,8 @@ def test_native_packing_transposes_permutes_and_folds_gamma():
     want = ConvNextReference(spec, sd, [0, 1, 2, 3]).forward(x)
     ones = ConvNextReference(spec, sd, [0, 1, 2, 3], unit_gamma=True).forward(x)
     for gf, wf, of, fp in zip(got, want, ones, FP32["convnext_test"]["hooks"]):
-        assert _rel(gf, wf) < bound(fp)                    # (the arrays are float32 roundings of the float64 weights: ~1e-7)
-        assert _rel(of, wf) > 1000 * bound(fp)             # gamma = 1 misses the true features by far more than the bound
+        assert _rel(gf, wf) < bound(fp, FLOOR)                    # (the arrays are float32 roundings of the float64 weights: ~1e-7)
+        assert _rel(of, wf) > 1000 * bound(fp, FLOOR)             # gamma = 1 misses the true features by far more than the bound
     assert len(spec.native_arrays(sd, 2)) == 4 + 4 + 3 * 8
 
 
@@ -250,7 +239,7 @@ def test_depthwise_launch_on_the_host_simulation_against_float64(eng, Cc, H, W, 
     fp = FP32["nodes"][f"{Cc}x{H}x{W}x{N}"]
     e_f, e_b = _rel(y, ref.detach()), _rel(gx, want_gx)
     print(f"dw {Cc} x {H} x {W}, {N} frames: forward {e_f:.3e} (fp32 CPU {fp['fwd']:.3e}) input gradient {e_b:.3e} (fp32 CPU {fp['bwd']:.3e})")
-    assert e_f < bound(fp["fwd"]) and e_b < bound(fp["bwd"])
+    assert e_f < bound(fp["fwd"], FLOOR) and e_b < bound(fp["bwd"], FLOOR)
     _, y2, gx2 = _node(eng, Cc, H, W, N)
     assert torch.equal(y, y2) and torch.equal(gx, gx2)                    # reruns: the same bits
 
@@ -338,27 +327,6 @@ def test_new_native_symbols_are_exported_by_the_library_and_the_host_simulation(
 
 
 # ---- the planner (csrc/i2v_convnext.cpp) on the host simulation: the shared launches as scalar code (csrc/i2v_xf_host.h) ----------
-def _write_hook_grads(net, hg):
-    for hi, g in zip(net.hooks, hg):
-        flat = g.float().reshape(g.shape[0], -1).contiguous()
-        for n in range(flat.shape[0]):
-            C.memmove(hi.grad + 4 * n * hi.grad_stride, flat[n].data_ptr(), 4 * hi.D)
-
-
-def _run_twin(eng, spec, sd, stages, x, hg, max_frames=None):
-    net = eng.build_convnext_net(spec, sd, stages, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(stages, max_frames or x.shape[0])
-    xf = x.float().contiguous()
-    net.forward(xf)
-    feats = [net.save_hook(i, x.shape[0]).reshape(x.shape[0], -1) for i in range(len(stages))]
-    assert all(f.shape[1] == spec.hook_dim(s) == hi.D for f, s, hi in zip(feats, stages, net.hooks))
-    _write_hook_grads(net, hg)
-    gx = torch.empty_like(xf)
-    net.backward(gx)
-    net.close()
-    return feats, gx
-
-
 def test_tiny_twin_on_the_host_simulation_against_float64(eng):
     """Features at all four depths and the input gradient with all four hook gradients flowing, 3 frames; reruns bit-identical; frame 0
     of the 3-frame run with the bits of a 1-frame run; a net planned for more frames than it runs gives the same bits."""
@@ -375,8 +343,8 @@ def test_tiny_twin_on_the_host_simulation_against_float64(eng):
     errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, want_gx)
     print(f"convnext_test on the host simulation vs float64: hooks {errs} grad {gerr}; fp32 CPU: {fp['hooks']} {fp['grad']}")
     for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
+        assert e < bound(cpu, FLOOR)
+    assert gerr < bound(fp["grad"], FLOOR)
     feats2, gx2 = _run_twin(eng, spec, sd, stages, x, hg, max_frames=5)
     assert all(torch.equal(a, b) for a, b in zip(feats, feats2)) and torch.equal(gx, gx2)
     f1, g1 = _run_twin(eng, spec, sd, stages, x[:1], [h[:1] for h in hg])
@@ -386,7 +354,7 @@ def test_tiny_twin_on_the_host_simulation_against_float64(eng):
     assert torch.equal(fa[0], feats[1])
     ref1 = ConvNextReference(spec, sd, [1])
     ref1.forward(x)
-    assert _rel(ga, ref1.backward([hg[1]])) < bound(fp["grad"])
+    assert _rel(ga, ref1.backward([hg[1]])) < bound(fp["grad"], FLOOR)
 
 
 def test_planner_refusals_on_the_host_simulation(eng):
@@ -413,10 +381,7 @@ def test_i2v_trajectory_on_the_tiny_twin_matches_the_reference(eng):
                                               weight_seed=0)
     adv = atk(vid, torch.zeros(1, dtype=torch.long), ["t"])
     g = graphs.build_tiny(TINY, (64, 64))
-    ref = restate.run_attack([ConvNextReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(3)], dtype=torch.float32)], vid,
-                             steps=4, step_size=0.005)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"]).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, ConvNextReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(3)], dtype=torch.float32), vid, rtol=2e-4, steps=4)
 
 
 def test_aens_and_ens_of_the_twin_with_tiny_resnet_plan_and_run(eng):

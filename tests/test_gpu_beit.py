@@ -13,24 +13,21 @@ import ctypes as C
 import json
 import os
 
-import numpy as np
 import pytest
 import torch
 
 from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
-from oracle import restate
 from tests import make_beit_fixtures as mk
 from tests.beit_reference import BeitReference
+from tests.family_harness import bound, check_net, check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, run_net as _run, stat
 
 pytestmark = pytest.mark.gpu
 BASE = "beit_base_patch16_224"
 FP32 = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "beit_fp32_cpu_errors.json")))
 NET_FLOOR, FWD_FLOOR, BWD_FLOOR = 1e-5, 1e-6, 1e-5
-
-
-def bound(fp32_err, floor=NET_FLOOR):
-    return max(floor, 4.0 * fp32_err)
+COUNTER = b"beit_attention_launches"
+TRAJECTORY_RTOL = 2e-4      # of the trajectory's costs against the float64 run
 
 
 @pytest.fixture(scope="module")
@@ -46,19 +43,6 @@ def host():
     e = hostsim_engine()
     _lib.bind(e.capi, _lib._BEIT_PROTOS)
     return e
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def stat(eng, name=b"beit_attention_launches"):
-    return int(eng.capi.i2v_backend_stat(name))
 
 
 def _dev(v):
@@ -86,9 +70,9 @@ def run_attn(eng, d):
 @pytest.mark.parametrize("F,T,H,dh,kind", mk.ATTN_CASES)
 def test_attention_kernel_against_float64_autograd(eng, host, F, T, H, dh, kind):
     d = mk.attn_case(F, T, H, dh, kind)
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     got = run_attn(eng, d)
-    assert stat(eng) - s0 == 3                                            # one launch forward; backward two: dq, then dk / dv
+    assert stat(eng, COUNTER) - s0 == 3                                            # one launch forward; backward two: dq, then dk / dv
     want = mk.attn_reference(d)
     fp = FP32["attention"][mk.case_key(F, T, H, dh, kind)]
     errs = {"fwd": _rel(got[0], want[0]), "dv": _rel(got[3], want[3])}
@@ -127,7 +111,7 @@ def test_the_launches_refuse_what_they_cannot_run(eng):
     z = torch.zeros(65536, device="cuda")
     p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
     capi = eng.capi
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     fwd = lambda *, qkv=p(z), bias=p(z), frames=1, T=4, H=2, dh=8, out=p(z): capi.i2v_beit_attention_f32(qkv, bias, frames, T, H, dh, 0.5, out, None)      # noqa: E731
     off = C.c_void_p(z.data_ptr() + 4)
     for kw, why in ((dict(T=209, H=1), b"more than 208 tokens"), (dict(H=1, dh=68), b"wider than 64"), (dict(dh=6), b"multiple of 4"),
@@ -142,7 +126,7 @@ def test_the_launches_refuse_what_they_cannot_run(eng):
                     (dict(dqkv=None), b"null"), (dict(dqkv=off), b"alignment")):
         assert bwd(**kw) != 0
         assert b"beit_attention_bwd" in capi.i2v_last_error() and why in capi.i2v_last_error()
-    assert stat(eng) == s0                                                # nothing was launched
+    assert stat(eng, COUNTER) == s0                                                # nothing was launched
     spec = graphs.build_tiny(BASE, (64, 64))
     sd = weights.synthetic_state_dict(spec, 0)
     with pytest.raises(_lib.I2VError, match="hooked twice"):
@@ -159,59 +143,13 @@ def test_the_launches_refuse_what_they_cannot_run(eng):
     assert _rel(run_attn(eng, d)[0], mk.attn_reference(d)[0]) < 1e-6
 
 
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
-def _set_hook_grads(net, hg):
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        assert gd.numel() == g.shape[0] * hi.D
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-
-
-def _run(net, spec, hooks, x, hg=None):
-    xd = x.float().cuda()
-    net.forward(xd)
-    n = x.shape[0]
-    feats = [net.save_hook(i, n).reshape(n, -1) for i in range(len(hooks))]
-    assert all(f.shape[1] == spec.hook_dim == hi.D for f, hi in zip(feats, net.hooks))
-    if hg is None:
-        hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    _set_hook_grads(net, hg)
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    return [f.cpu() for f in feats], gx.cpu(), hg
-
-
 def _hooks_and_grad(eng, spec, sd, hooks, x, max_frames=None):
-    net = eng.build_beit_net(spec, sd, hooks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(hooks, max_frames or x.shape[0])
-    s0 = stat(eng)
-    feats, gx, hg = _run(net, spec, hooks, x)
-    assert stat(eng) - s0 == 3 * (max(hooks) + 1)                         # per block: one attention launch forward, two backward
-    net.close()
-    return (feats, gx), hg
+    launches = 3 * (max(hooks) + 1)      # per block: one attention launch forward, two backward
+    return hooks_and_grad(eng, spec, sd, hooks, x, max_frames, launches=(COUNTER, launches))
 
 
 def _check(label, feats, gx, ref, x, hg):
-    rf = ref.forward(x)
-    errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, ref.backward(hg))
-    fp = FP32[label]
-    print(f"{label}: HIP vs float64: hooks {errs} grad {gerr}; fp32 CPU vs float64: {fp}")
-    for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
+    check_net(label, feats, gx, ref.forward(x), ref.backward(hg), FP32[label], NET_FLOOR)
 
 
 @pytest.mark.parametrize("label", sorted(mk.TWINS))
@@ -246,9 +184,9 @@ def test_twin_on_the_shared_launch_route(eng, label, monkeypatch):
     monkeypatch.setenv("I2V_BEIT_ATTN", "0")
     net = eng.build_beit_net(spec, sd, hooks, x.shape[0])
     assert net.workspace_bytes() == spec.workspace_bytes(hooks, x.shape[0]) > spec.workspace_bytes(hooks, x.shape[0], composed=False)
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     feats, gx, hg = _run(net, spec, hooks, x)
-    assert stat(eng) == s0
+    assert stat(eng, COUNTER) == s0
     net.close()
     _check(label, feats, gx, BeitReference(spec, sd, hooks), x, hg)
     net = eng.build_beit_net(spec, sd, hooks, 1)
@@ -281,11 +219,7 @@ def test_i2v_trajectory_on_the_twin_matches_the_float64_trajectory():
     adv = atk(vid, torch.zeros(clip[0], dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(name, (side, side))
     assert spec.arch == label
-    ref = restate.run_attack([BeitReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(depth)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    print("costs", atk.last_costs, "float64", ref["costs"])
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"].float()).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, BeitReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(depth)], dtype=torch.float64), vid, rtol=TRAJECTORY_RTOL)
 
 
 def test_workspace_of_beit_base_at_128_frames_depth_3(eng):

@@ -18,34 +18,20 @@ from i2v_amd import attacks, graphs, weights
 from oracle import restate
 from tests import make_cait_fixtures as mk
 from tests.cait_reference import CaitReference
+from tests.family_harness import bound, check_net, check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, run_net as _run, stat, video as _video
 
 pytestmark = pytest.mark.gpu
 S24, XXS = "cait_s24_224", "cait_xxs24_224"
 FP32 = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cait_fp32_cpu_errors.json")))
 NET_FLOOR, FWD_FLOOR, BWD_FLOOR = 1e-5, 1e-6, 1e-5
-
-
-def bound(fp32_err, floor=NET_FLOOR):
-    return max(floor, 4.0 * fp32_err)
+COUNTER = b"cait_attention_launches"
+TRAJECTORY_RTOL = 2e-4      # of the trajectory's costs against the float64 run
 
 
 @pytest.fixture(scope="module")
 def eng():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return attacks.get_engine("cuda:0")
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def stat(eng, name=b"cait_attention_launches"):
-    return int(eng.capi.i2v_backend_stat(name))
 
 
 def run_attn(eng, d):
@@ -60,9 +46,9 @@ def run_attn(eng, d):
 @pytest.mark.parametrize("F,T,H,dh", mk.ATTN_CASES)
 def test_attention_kernel_against_float64_autograd(eng, F, T, H, dh):
     d = mk.attn_case(F, T, H, dh)
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     out, probs, dqkv = run_attn(eng, d)
-    assert stat(eng) - s0 == 3                                            # one launch forward, two backward
+    assert stat(eng, COUNTER) - s0 == 3                                            # one launch forward, two backward
     want, want_p, want_g = mk.attn_reference(d)
     fp = FP32["attention"][mk.case_key(F, T, H, dh)]
     e_f, e_p, e_b = _rel(out, want), _rel(probs, want_p), _rel(dqkv, want_g)
@@ -80,7 +66,7 @@ def test_the_launch_refuses_what_it_cannot_run(eng):
     z = torch.zeros(4096, device="cuda")
     p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
     capi = eng.capi
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     fwd = lambda *, frames=1, T=4, H=2, dh=8: capi.i2v_cait_attention_f32(p(z), frames, T, H, dh, 0.5, p(z), p(z), p(z), p(z), p(z), p(z), None)      # noqa: E731
     for kw, why in ((dict(dh=6), b"multiple of 4"), (dict(H=17, dh=4), b"LDS budget"), (dict(T=400, H=8, dh=4), b"LDS budget"),
                     (dict(frames=70000), b"65535"), (dict(frames=40000, T=196, H=8, dh=48), b"2^31")):
@@ -89,61 +75,16 @@ def test_the_launch_refuses_what_it_cannot_run(eng):
         assert b"cait_attention" in err and b"hipErrorInvalidValue" in err and why in err, err
     assert capi.i2v_cait_attention_bwd_f32(p(z), p(z), p(z), 1, 4, 2, 6, 0.5, p(z), p(z), p(z), p(z), p(z), p(z), None) != 0
     assert b"multiple of 4" in capi.i2v_last_error()
-    assert stat(eng) == s0                                                # nothing was launched
-
-
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
-def _set_hook_grads(net, hg):
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-
-
-def _run(net, spec, blocks, x, hg=None):
-    xd = x.float().cuda()
-    net.forward(xd)
-    n = x.shape[0]
-    feats = [net.save_hook(i, n).reshape(n, -1) for i in range(len(blocks))]
-    assert all(f.shape[1] == spec.hook_dim(b) == hi.D for f, b, hi in zip(feats, blocks, net.hooks))
-    if hg is None:
-        hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    _set_hook_grads(net, hg)
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    return [f.cpu() for f in feats], gx.cpu(), hg
+    assert stat(eng, COUNTER) == s0                                                # nothing was launched
 
 
 def _hooks_and_grad(eng, spec, sd, blocks, x, max_frames=None):
-    net = eng.build_cait_net(spec, sd, blocks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(blocks, max_frames or x.shape[0])
-    s0 = stat(eng)
-    feats, gx, hg = _run(net, spec, blocks, x)
-    assert stat(eng) - s0 == 3 * (max(blocks) + 1)                        # per block: one attention launch forward, two backward
-    net.close()
-    return (feats, gx), hg
+    launches = 3 * (max(blocks) + 1)      # per block: one attention launch forward, two backward
+    return hooks_and_grad(eng, spec, sd, blocks, x, max_frames, launches=(COUNTER, launches))
 
 
 def _check(label, feats, gx, ref, x, hg):
-    rf = ref.forward(x)
-    errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, ref.backward(hg))
-    fp = FP32[label]
-    print(f"{label}: HIP vs float64: hooks {errs} grad {gerr}; fp32 CPU vs float64: {fp}")
-    for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
+    check_net(label, feats, gx, ref.forward(x), ref.backward(hg), FP32[label], NET_FLOOR)
 
 
 @pytest.mark.parametrize("label", sorted(mk.TWINS))
@@ -177,24 +118,12 @@ def test_full_size_model_at_224_depths_1_to_4_against_float64(eng, name):
     _check(name, feats, gx, CaitReference(spec, sd, blocks), x, hg)
 
 
-def _video(b, f, hw, seed):
-    gen = torch.Generator().manual_seed(seed)
-    u8 = torch.randint(0, 256, (b, 3, f, hw, hw), generator=gen, dtype=torch.uint8)
-    mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
-    std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
-    return (u8.float() / 255 - mean) / std
-
-
 def test_i2v_trajectory_on_the_twin_matches_the_float64_trajectory():
     vid = _video(2, 4, 64, 23)
     atk = attacks.ImageGuidedFMDirection_Adam([S24], depth=3, step_size=0.005, steps=10, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(2, dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(S24, (64, 64))
-    ref = restate.run_attack([CaitReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    print("costs", atk.last_costs, "float64", ref["costs"])
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"].float()).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, CaitReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64), vid, rtol=TRAJECTORY_RTOL)
 
 
 def test_aens_of_the_twin_with_tiny_resnet_matches_the_oracle():

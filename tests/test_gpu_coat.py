@@ -9,24 +9,23 @@ float64; the refusals, with the engine going on afterwards; the three test-size 
 Bound: relative L2 against float64, at most the larger of the floor for that kind of case (entries 1e-6 forward, 1e-5 backward; nets
 1e-5) and 4 x the error of the float32 CPU run of the same reference on the same inputs (tests/golden/coat_fp32_cpu_errors.json,
 tests/make_coat_fixtures.py).  A case without a recorded error fails (KeyError)."""
-import ctypes as C
 import json
 import os
 
-import numpy as np
 import pytest
 import torch
 
 from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
-from oracle import restate
 from tests import make_coat_fixtures as mk
 from tests.coat_reference import CoatReference
-from tests.test_coat_cpu import FWD_PARTS, bound, check_attn, check_cells, check_dw, check_net, entry_refusals, run_attn, run_cells, run_dw
+from tests.family_harness import bound, check_net, check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, run_net as _run, stat
+from tests.test_coat_cpu import FWD_PARTS, check_attn, check_cells, check_dw, entry_refusals, run_attn, run_cells, run_dw
 
 pytestmark = pytest.mark.gpu
 FP32 = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "coat_fp32_cpu_errors.json")))
 FWD_FLOOR, BWD_FLOOR, NET_FLOOR = 1e-6, 1e-5, 1e-5
+COUNTER = b"coat_attention_launches"
 
 
 @pytest.fixture(scope="module")
@@ -44,21 +43,8 @@ def host():
     return e
 
 
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
 def _cuda(t):
     return t.cuda()
-
-
-def stat(eng, name=b"coat_attention_launches"):
-    return int(eng.capi.i2v_backend_stat(name))
 
 
 def _sync(res):
@@ -69,9 +55,9 @@ def _sync(res):
 @pytest.mark.parametrize("case", mk.ATTN_CASES, ids=lambda c: mk.case_key(*c))
 def test_attention_kernels_against_float64_autograd(eng, host, case):
     d = mk.attn_case(*case)
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     got = _sync(run_attn(eng, d, _cuda))
-    assert stat(eng) - s0 == 4                                            # two launches forward (reduce, apply), two backward
+    assert stat(eng, COUNTER) - s0 == 4                                            # two launches forward (reduce, apply), two backward
     check_attn(got, case)
     again = _sync(run_attn(eng, d, _cuda))
     assert all(torch.equal(a, b) for a, b in zip(got, again))             # reruns: the same bits
@@ -105,53 +91,14 @@ def test_cell_kernels_against_float64(eng, case):
 
 
 def test_refusals_launch_nothing_and_the_engine_goes_on(eng):
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     entry_refusals(eng, _cuda)
-    assert stat(eng) - s0 == 2                                            # only the forward that follows the refusals
-
-
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
-def _set_hook_grads(net, hg):
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        assert gd.numel() == g.shape[0] * hi.D
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-
-
-def _run(net, hooks, x, hg=None):
-    xd = x.float().cuda()
-    net.forward(xd)
-    n = x.shape[0]
-    feats = [net.save_hook(i, n).reshape(n, -1) for i in range(len(hooks))]
-    if hg is None:
-        hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    _set_hook_grads(net, hg)
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    return [f.cpu() for f in feats], gx.cpu(), hg
+    assert stat(eng, COUNTER) - s0 == 2                                            # only the forward that follows the refusals
 
 
 def _hooks_and_grad(eng, spec, sd, hooks, x, max_frames=None):
-    net = eng.build_coat_net(spec, sd, hooks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(hooks, max_frames or x.shape[0])
-    s0 = stat(eng)
-    feats, gx, hg = _run(net, hooks, x)
-    assert stat(eng) - s0 == 4 * sum(spec.depths[:max(hooks) + 1])        # per block: two attention launches forward, two backward
-    net.close()
-    return (feats, gx), hg
+    launches = 4 * sum(spec.depths[:max(hooks) + 1])      # per block: two attention launches forward, two backward
+    return hooks_and_grad(eng, spec, sd, hooks, x, max_frames, launches=(COUNTER, launches))
 
 
 def _reference(spec, sd, hooks, x, hg):
@@ -168,11 +115,11 @@ def test_twin_hooks_at_depths_1_to_4_and_input_gradient(eng, label):
     x = mk.twin_input(label)
     hooks = [spec.hook_for(d) for d in (1, 2, 3, 4)]
     (feats, gx), hg = _hooks_and_grad(eng, spec, sd, hooks, x)
-    check_net(label, feats, gx, *_reference(spec, sd, hooks, x, hg))
+    check_net(label, feats, gx, *_reference(spec, sd, hooks, x, hg), FP32[label], NET_FLOOR)
     (feats2, gx2), _ = _hooks_and_grad(eng, spec, sd, hooks, x, max_frames=5)      # a second net, planned for more frames: the same bits
     assert all(torch.equal(a, b) for a, b in zip(feats, feats2)) and torch.equal(gx, gx2)
     net = eng.build_coat_net(spec, sd, hooks, 1)                                   # frame 0 of the n-frame run against a 1-frame run
-    f1, g1, _ = _run(net, hooks, x[:1], [h[:1] for h in hg])
+    f1, g1, _ = _run(net, spec, hooks, x[:1], [h[:1] for h in hg])
     net.close()
     assert all(torch.equal(a[:1], b) for a, b in zip(feats, f1)) and torch.equal(gx[:1], g1)
     for i in (0, 2):                                                               # a single hook: the net is truncated there
@@ -180,7 +127,7 @@ def test_twin_hooks_at_depths_1_to_4_and_input_gradient(eng, label):
         assert torch.equal(fa[0], feats[i])
         ref1 = CoatReference(spec, sd, [hooks[i]])
         ref1.forward(x)
-        assert _rel(ga, ref1.backward([_rand(*fa[0].shape, seed=30)])) < bound(FP32[label]["grad"])
+        assert _rel(ga, ref1.backward([_rand(*fa[0].shape, seed=30)])) < bound(FP32[label]["grad"], NET_FLOOR)
 
 
 @pytest.mark.parametrize("name", mk.FULL)
@@ -191,7 +138,7 @@ def test_full_size_model_at_224_depths_1_to_4_against_float64(eng, name):
     hooks = [spec.hook_for(d) for d in (1, 2, 3, 4)]
     (feats, gx), hg = _hooks_and_grad(eng, spec, sd, hooks, x)
     assert [f.shape[1] for f in feats] == [3137 * 64, 785 * 128, 197 * 256, 50 * 320]
-    check_net(name, feats, gx, *_reference(spec, sd, hooks, x, hg))
+    check_net(name, feats, gx, *_reference(spec, sd, hooks, x, hg), FP32[name], NET_FLOOR)
 
 
 def test_i2v_trajectory_on_the_twin_matches_the_float64_trajectory():
@@ -200,17 +147,13 @@ def test_i2v_trajectory_on_the_twin_matches_the_float64_trajectory():
     label, depth = "coat_test", mk.TRAJECTORY_DEPTH
     name, side, _ = mk.TWINS[label]
     clip = mk.TRAJECTORY_CLIP
-    rtol = bound(FP32["trajectory"][label][str(depth)])
+    rtol = bound(FP32["trajectory"][label][str(depth)], NET_FLOOR)
     vid = mk.video(*clip)
     atk = attacks.ImageGuidedFMDirection_Adam([name], depth=depth, step_size=0.005, steps=10, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(clip[0], dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(name, (side, side))
     assert spec.arch == label
-    ref = restate.run_attack([CoatReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(depth)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    print("costs", atk.last_costs, "float64", ref["costs"], "rtol", rtol)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=rtol)
-    assert float((adv - ref["adv"].float()).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, CoatReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(depth)], dtype=torch.float64), vid, rtol=rtol)
 
 
 def test_workspace_of_coat_lite_tiny_at_128_frames_depth_3(eng):

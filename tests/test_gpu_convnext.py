@@ -19,6 +19,7 @@ from oracle import restate
 from tests import convnext_reference as cr
 from tests import make_convnext_fixtures as mk
 from tests.convnext_reference import ConvNextReference
+from tests.family_harness import bound, check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, run_net as _run, stat, video as _video
 from tests.swin_reference import SwinReference
 
 pytestmark = pytest.mark.gpu
@@ -26,29 +27,14 @@ TINY = "convnext_tiny"
 SWIN = "swin_tiny_patch4_window7_224"
 FP32 = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "convnext_fp32_cpu_errors.json")))
 FLOOR = 1e-5
-
-
-def bound(fp32_err):
-    return max(FLOOR, 4.0 * fp32_err)
+COUNTER = b"convnext_dw_launches"
+TRAJECTORY_RTOL = 2e-4      # of the trajectory's costs against the float64 run
 
 
 @pytest.fixture(scope="module")
 def eng():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return attacks.get_engine("cuda:0")
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def stat(eng, name=b"convnext_dw_launches"):
-    return int(eng.capi.i2v_backend_stat(name))
 
 
 def _node(eng, Cc, H, W, N):
@@ -64,16 +50,16 @@ def _node(eng, Cc, H, W, N):
 @pytest.mark.parametrize("Cc,H,W", mk.NODE_CASES)
 @pytest.mark.parametrize("N", [1, 3])
 def test_depthwise_kernel_against_float64_and_the_host_restatement(eng, Cc, H, W, N):
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     (x, w, b, dy, res), y, gx = _node(eng, Cc, H, W, N)
-    assert stat(eng) - s0 == 2
+    assert stat(eng, COUNTER) - s0 == 2
     xr = x.clone().requires_grad_(True)
     ref = cr.dwconv_token_major(xr, w, b)
     want_gx = torch.autograd.grad(ref, xr, dy)[0] + res.float().double()
     fp = FP32["nodes"][f"{Cc}x{H}x{W}x{N}"]
     e_f, e_b = _rel(y, ref.detach()), _rel(gx, want_gx)
     print(f"dw {Cc} x {H} x {W}, {N} frames: forward {e_f:.3e} (fp32 CPU {fp['fwd']:.3e}) input gradient {e_b:.3e} (fp32 CPU {fp['bwd']:.3e})")
-    assert e_f < bound(fp["fwd"]) and e_b < bound(fp["bwd"])
+    assert e_f < bound(fp["fwd"], FLOOR) and e_b < bound(fp["bwd"], FLOOR)
     _, y2, gx2 = _node(eng, Cc, H, W, N)
     assert torch.equal(y, y2) and torch.equal(gx, gx2)                    # reruns: the same bits
     # the host restatement (csrc/i2v_convnext_host.h): no transcendental in the launch, so bit for bit
@@ -109,48 +95,9 @@ def test_the_launch_refuses_what_it_was_not_planned_for(eng):
     assert b"2^31" in capi.i2v_last_error()
 
 
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
-def _set_hook_grads(net, hg):
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-
-
-def _run(net, spec, stages, x, hg=None):
-    xd = x.float().cuda()
-    net.forward(xd)
-    n = x.shape[0]
-    feats = [net.save_hook(i, n).reshape(n, -1) for i in range(len(stages))]
-    assert all(f.shape[1] == spec.hook_dim(s) == hi.D for f, s, hi in zip(feats, stages, net.hooks))
-    if hg is None:
-        hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    _set_hook_grads(net, hg)
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    return [f.cpu() for f in feats], gx.cpu(), hg
-
-
 def _hooks_and_grad(eng, spec, sd, stages, x):
-    net = eng.build_convnext_net(spec, sd, stages, x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(stages, x.shape[0])
-    s0 = stat(eng)
-    feats, gx, hg = _run(net, spec, stages, x)
-    assert stat(eng) - s0 == 2 * sum(spec.depths[:max(stages) + 1])       # one depthwise launch per block and pass
-    net.close()
-    return (feats, gx), hg
+    launches = 2 * sum(spec.depths[:max(stages) + 1])      # one depthwise launch per block and pass
+    return hooks_and_grad(eng, spec, sd, stages, x, launches=(COUNTER, launches))
 
 
 def test_tiny_twin_hooks_at_depths_1_to_4_and_input_gradient(eng):
@@ -165,8 +112,8 @@ def test_tiny_twin_hooks_at_depths_1_to_4_and_input_gradient(eng):
     fp = FP32["convnext_test"]
     print(f"convnext_test: HIP vs float64: hooks {errs} grad {gerr}; fp32 CPU vs float64: {fp}")
     for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
+        assert e < bound(cpu, FLOOR)
+    assert gerr < bound(fp["grad"], FLOOR)
     (feats2, gx2), _ = _hooks_and_grad(eng, spec, sd, stages, x)                 # repeatability: a second net, the same bits
     assert all(torch.equal(a, b) for a, b in zip(feats, feats2)) and torch.equal(gx, gx2)
     # frame 0 of the 3-frame run against a 1-frame run
@@ -190,8 +137,8 @@ def test_convnext_tiny_at_224_depth_3_against_float64(eng):
     err, gerr = _rel(feats[0], rf[0]), _rel(gx, ref.backward(hg))
     fp = FP32["convnext_tiny"]
     print(f"convnext_tiny: HIP vs float64: hook {err} grad {gerr}; fp32 CPU vs float64: {fp}")
-    assert err < bound(fp["hooks"][0])
-    assert gerr < bound(fp["grad"])
+    assert err < bound(fp["hooks"][0], FLOOR)
+    assert gerr < bound(fp["grad"], FLOOR)
 
 
 def test_fewer_frames_on_a_used_handle_give_the_bits_of_a_fresh_one(eng):
@@ -209,23 +156,12 @@ def test_fewer_frames_on_a_used_handle_give_the_bits_of_a_fresh_one(eng):
     assert all(torch.equal(a, b) for a, b in zip(f1, f2)) and torch.equal(g1, g2)
 
 
-def _video(b, f, hw, seed):
-    gen = torch.Generator().manual_seed(seed)
-    u8 = torch.randint(0, 256, (b, 3, f, hw, hw), generator=gen, dtype=torch.uint8)
-    mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
-    std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
-    return (u8.float() / 255 - mean) / std
-
-
 def test_i2v_trajectory_on_the_tiny_twin_matches_the_float64_trajectory():
     vid = _video(2, 4, 64, 23)
     atk = attacks.ImageGuidedFMDirection_Adam([TINY], depth=3, step_size=0.005, steps=10, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(2, dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(TINY, (64, 64))
-    ref = restate.run_attack([ConvNextReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    print("costs", atk.last_costs, "float64", ref["costs"])
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)          # the tolerance of the ViT and Swin trajectories
+    check_trajectory(atk, None, ConvNextReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64), vid, rtol=TRAJECTORY_RTOL)
     mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
     std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
     a, o = adv * std + mean, vid * std + mean

@@ -17,6 +17,7 @@ from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
 from oracle import restate
 from tests import make_mixer_fixtures as mk
+from tests.family_harness import bound, check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, run_net as _run, stat, video as _video
 from tests.mixer_reference import MixerReference
 from tests.swin_reference import SwinReference
 
@@ -25,30 +26,15 @@ MIXER, RESMLP = "mixer_b16_224", "resmlp_12_224"
 SWIN = "swin_tiny_patch4_window7_224"
 FP32 = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mixer_fp32_cpu_errors.json")))
 FLOOR = 1e-5
+COUNTER = b"mixer_tokens_launches"
+TRAJECTORY_RTOL = 2e-4      # of the trajectory's costs against the float64 run
 ALL_CASES = mk.HIDDEN_CASES + [(S, 0, Cn) for S, Cn in mk.LINEAR_CASES]
-
-
-def bound(fp32_err):
-    return max(FLOOR, 4.0 * fp32_err)
 
 
 @pytest.fixture(scope="module")
 def eng():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return attacks.get_engine("cuda:0")
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def stat(eng, name=b"mixer_tokens_launches"):
-    return int(eng.capi.i2v_backend_stat(name))
 
 
 def _dev(d, device):
@@ -67,16 +53,16 @@ def run_case(e, c, tile=0):
 def test_token_kernel_against_float64_and_the_host_restatement(eng, S, Sh, Cn, N):
     d = mk.token_case(S, Sh, Cn, N)
     c = _dev(d, "cuda")
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     out, dz = run_case(eng, c)
     torch.cuda.synchronize()
-    assert stat(eng) - s0 == 2                                            # one launch per pass
+    assert stat(eng, COUNTER) - s0 == 2                                            # one launch per pass
     out, dz = out.cpu(), dz.cpu()
     want, want_dz = mk.token_reference(d)
     fp = FP32["tokens"][mk.case_key(S, Sh, Cn, N)]
     e_f, e_b = _rel(out, want), _rel(dz, want_dz)
     print(f"tokens S {S} Sh {Sh} C {Cn}, {N} frames: forward {e_f:.3e} (fp32 CPU {fp['fwd']:.3e}) input gradient {e_b:.3e} (fp32 CPU {fp['bwd']:.3e})")
-    assert e_f < bound(fp["fwd"]) and e_b < bound(fp["bwd"])
+    assert e_f < bound(fp["fwd"], FLOOR) and e_b < bound(fp["bwd"], FLOOR)
     out2, dz2 = run_case(eng, c)
     assert torch.equal(out, out2.cpu()) and torch.equal(dz, dz2.cpu())    # reruns: the same bits
     # the other channel tile (where both fit the LDS): the same bits
@@ -114,7 +100,7 @@ def test_the_launch_refuses_what_it_was_not_planned_for(eng):
     z = torch.zeros(196 * 512, device="cuda")
     p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
     capi = eng.capi
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     assert capi.i2v_mixer_tokens_f32(p(z), p(z), p(z), 0, 4, 0, 4, p(z), p(z), None, None, None, None, None, 0, None) != 0
     assert capi.i2v_mixer_tokens_f32(p(z), p(z), p(z), 1, 4, 0, 6, p(z), p(z), None, None, None, None, None, 0, None) != 0
     assert b"i2v_mixer_tokens_f32" in capi.i2v_last_error()
@@ -122,51 +108,12 @@ def test_the_launch_refuses_what_it_was_not_planned_for(eng):
     assert b"LDS" in capi.i2v_last_error()                                # (196 + 512) rows of 64 channels: 181 248 bytes
     assert capi.i2v_mixer_tokens_f32(p(z), p(z), p(z), 70000, 4, 0, 4, p(z), p(z), None, None, None, None, None, 0, None) != 0
     assert b"65535" in capi.i2v_last_error()
-    assert stat(eng) == s0                                                # nothing was launched
-
-
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
-def _set_hook_grads(net, hg):
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-
-
-def _run(net, spec, blocks, x, hg=None):
-    xd = x.float().cuda()
-    net.forward(xd)
-    n = x.shape[0]
-    feats = [net.save_hook(i, n).reshape(n, -1) for i in range(len(blocks))]
-    assert all(f.shape[1] == spec.hook_dim(b) == hi.D for f, b, hi in zip(feats, blocks, net.hooks))
-    if hg is None:
-        hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    _set_hook_grads(net, hg)
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    return [f.cpu() for f in feats], gx.cpu(), hg
+    assert stat(eng, COUNTER) == s0                                                # nothing was launched
 
 
 def _hooks_and_grad(eng, spec, sd, blocks, x, max_frames=None):
-    net = eng.build_mixer_net(spec, sd, blocks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(blocks, max_frames or x.shape[0])
-    s0 = stat(eng)
-    feats, gx, hg = _run(net, spec, blocks, x)
-    assert stat(eng) - s0 == 2 * (max(blocks) + 1)                        # one token launch per block and pass
-    net.close()
-    return (feats, gx), hg
+    launches = 2 * (max(blocks) + 1)      # one token launch per block and pass
+    return hooks_and_grad(eng, spec, sd, blocks, x, max_frames, launches=(COUNTER, launches))
 
 
 @pytest.mark.parametrize("twin,name", [("mixer_test", MIXER), ("resmlp_test", RESMLP)])
@@ -182,8 +129,8 @@ def test_twin_hooks_at_depths_1_to_4_and_input_gradient(eng, twin, name):
     fp = FP32[twin]
     print(f"{twin}: HIP vs float64: hooks {errs} grad {gerr}; fp32 CPU vs float64: {fp}")
     for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
+        assert e < bound(cpu, FLOOR)
+    assert gerr < bound(fp["grad"], FLOOR)
     (feats2, gx2), _ = _hooks_and_grad(eng, spec, sd, blocks, x, max_frames=5)     # a second net, planned for more frames: the same bits
     assert all(torch.equal(a, b) for a, b in zip(feats, feats2)) and torch.equal(gx, gx2)
     net = eng.build_mixer_net(spec, sd, blocks, 1)                                 # frame 0 of the 3-frame run against a 1-frame run
@@ -208,16 +155,8 @@ def test_full_size_model_at_224_depths_2_and_4_against_float64(eng, name):
     fp = FP32[name]
     print(f"{name}: HIP vs float64: hooks {errs} grad {gerr}; fp32 CPU vs float64: {fp}")
     for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
-
-
-def _video(b, f, hw, seed):
-    gen = torch.Generator().manual_seed(seed)
-    u8 = torch.randint(0, 256, (b, 3, f, hw, hw), generator=gen, dtype=torch.uint8)
-    mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
-    std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
-    return (u8.float() / 255 - mean) / std
+        assert e < bound(cpu, FLOOR)
+    assert gerr < bound(fp["grad"], FLOOR)
 
 
 def test_i2v_trajectory_on_the_mixer_twin_matches_the_float64_trajectory():
@@ -225,11 +164,7 @@ def test_i2v_trajectory_on_the_mixer_twin_matches_the_float64_trajectory():
     atk = attacks.ImageGuidedFMDirection_Adam([MIXER], depth=3, step_size=0.005, steps=4, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(2, dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(MIXER, (64, 64))
-    ref = restate.run_attack([MixerReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64)],
-                             vid, steps=4, step_size=0.005)
-    print("costs", atk.last_costs, "float64", ref["costs"])
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"].float()).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, MixerReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64), vid, rtol=TRAJECTORY_RTOL, steps=4)
 
 
 def test_aens_of_the_mixer_twin_with_tiny_resnet_and_tiny_swin_matches_the_oracle():

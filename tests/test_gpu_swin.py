@@ -14,10 +14,12 @@ from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
 from oracle import restate
 from tests import swin_reference as sr
+from tests.family_harness import check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, run_net as _run, video as _video
 from tests.swin_reference import SwinReference
 from tests.vit_family_reference import VitFamilyReference
 
 pytestmark = pytest.mark.gpu
+TRAJECTORY_RTOL = 2e-4      # of the trajectory's costs against the float64 run
 TINY, BASE = "swin_tiny_patch4_window7_224", "swin_base_patch4_window7_224"
 HOOK_BOUND, GRAD_BOUND = 2e-4, 1e-3            # relative L2 against float64: the bounds of the full ViT tests (tests/test_gpu_vit_family.py)
 # fp32 CPU run of the restatement against its float64 run on this file's full-size inputs (tests/golden/make_swin_fp32_cpu_errors.py)
@@ -32,15 +34,6 @@ def eng():
 
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    return (torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64) * scale)
 
 
 # grids 56 / 28 / 14 / 7 with window 7, shift 0 and 3, heads 3 / 4 / 24, head width 32; the test-size twin's 16 / 8 grids with window 4,
@@ -126,47 +119,8 @@ def test_embedding_without_prefix_rows_and_its_backward(eng, accumulate):
     assert _rel(got, want) < 1e-5
 
 
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
-def _set_hook_grads(net, hg):
-    """Random hook gradients written straight into the gradient views, where the loss kernels would write them."""
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-
-
-def _run(net, spec, stages, x, hg=None):
-    xd = x.float().cuda()
-    net.forward(xd)
-    n = x.shape[0]
-    feats = [net.save_hook(i, n).reshape(n, -1) for i in range(len(stages))]
-    assert all(f.shape[1] == spec.hook_dim(s) == hi.D for f, s, hi in zip(feats, stages, net.hooks))
-    if hg is None:
-        hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    _set_hook_grads(net, hg)
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    return [f.cpu() for f in feats], gx.cpu(), hg
-
-
 def _hooks_and_grad(eng, spec, sd, stages, x):
-    net = eng.build_swin_net(spec, sd, stages, x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(stages, x.shape[0])
-    feats, gx, hg = _run(net, spec, stages, x)
-    net.close()
-    return (feats, gx), hg
+    return hooks_and_grad(eng, spec, sd, stages, x)
 
 
 def test_tiny_twin_hooks_and_input_gradient(eng):
@@ -238,22 +192,12 @@ def test_fewer_frames_on_a_used_handle_give_the_bits_of_a_fresh_one(eng):
     assert all(torch.equal(a, b) for a, b in zip(f1, f2)) and torch.equal(g1, g2)
 
 
-def _video(b, f, hw, seed):
-    gen = torch.Generator().manual_seed(seed)
-    u8 = torch.randint(0, 256, (b, 3, f, hw, hw), generator=gen, dtype=torch.uint8)
-    mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
-    std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
-    return (u8.float() / 255 - mean) / std
-
-
 def test_i2v_trajectory_on_the_tiny_twin_matches_the_restatement():
     vid = _video(2, 4, 64, 23)
     atk = attacks.ImageGuidedFMDirection_Adam([TINY], depth=2, step_size=0.005, steps=10, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(2, dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(TINY, (64, 64))
-    ref = restate.run_attack([SwinReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(2)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
+    check_trajectory(atk, None, SwinReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(2)], dtype=torch.float64), vid, rtol=TRAJECTORY_RTOL)
     mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
     std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
     a, o = adv * std + mean, vid * std + mean

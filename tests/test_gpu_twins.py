@@ -21,16 +21,15 @@ from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
 from oracle import restate
 from tests import make_twins_fixtures as mk
+from tests.family_harness import bound, check_net, check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, run_net as _run, stat
 from tests.twins_reference import TwinsReference
 
 pytestmark = pytest.mark.gpu
 PCPVT, SVT = "twins_pcpvt_small", "twins_svt_small"
 FP32 = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "twins_fp32_cpu_errors.json")))
 NET_FLOOR, FWD_FLOOR, BWD_FLOOR = 1e-5, 1e-6, 1e-5
-
-
-def bound(fp32_err, floor=NET_FLOOR):
-    return max(floor, 4.0 * fp32_err)
+COUNTER = b"twins_attention_launches"
+TRAJECTORY_RTOL = 2e-4      # of the trajectory's costs against the float64 run
 
 
 @pytest.fixture(scope="module")
@@ -46,19 +45,6 @@ def host():
     e = hostsim_engine()
     _lib.bind(e.capi, _lib._TWINS_PROTOS)
     return e
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def stat(eng, name=b"twins_attention_launches"):
-    return int(eng.capi.i2v_backend_stat(name))
 
 
 def _dev(v):
@@ -77,9 +63,9 @@ def run_attn(eng, d):
 @pytest.mark.parametrize("F,Tq,Tk,H,dh,kind", mk.ATTN_CASES)
 def test_attention_kernel_against_float64_autograd(eng, host, F, Tq, Tk, H, dh, kind):
     d = mk.attn_case(F, Tq, Tk, H, dh, kind)
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     out, dq, dkv = run_attn(eng, d)
-    assert stat(eng) - s0 == 3                                            # one launch forward; backward two: dq, then dk / dv
+    assert stat(eng, COUNTER) - s0 == 3                                            # one launch forward; backward two: dq, then dk / dv
     want, want_q, want_kv = mk.attn_reference(d)
     fp = FP32["attention"][mk.case_key(F, Tq, Tk, H, dh, kind)]
     e_f, e_kv = _rel(out, want), _rel(dkv, want_kv)
@@ -130,7 +116,7 @@ def test_the_launches_refuse_what_they_cannot_run(eng):
     z = torch.zeros(16384, device="cuda")
     p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
     capi = eng.capi
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     fwd = lambda *, q=p(z), kv=p(z), frames=1, Tq=4, Tk=4, H=2, dh=8: capi.i2v_twins_attention_f32(q, kv, frames, Tq, Tk, H, dh, 0.5, p(z), None)      # noqa: E731
     off = C.c_void_p(z.data_ptr() + 4)
     for kw, why in ((dict(Tk=65), b"more than 64 keys"), (dict(H=1, dh=68), b"wider than 64"), (dict(dh=6), b"multiple of 4"), (dict(q=None), b"null"),
@@ -147,7 +133,7 @@ def test_the_launches_refuse_what_they_cannot_run(eng):
     assert capi.i2v_twins_block_gather_f32(p(z), y, 1, 4, 4, 8, 3, None) != 0 and b"2, 4 or 8" in capi.i2v_last_error()
     assert capi.i2v_twins_block_scatter_f32(p(z), y, 1, 6, 4, 8, 4, 0, None) != 0 and b"whole number of blocks" in capi.i2v_last_error()
     assert capi.i2v_twins_block_gather_f32(p(z), None, 1, 4, 4, 8, 2, None) != 0 and b"null" in capi.i2v_last_error()
-    assert stat(eng) == s0                                                # nothing was launched
+    assert stat(eng, COUNTER) == s0                                                # nothing was launched
     spec = graphs.build_tiny(PCPVT, (64, 64))
     sd = weights.synthetic_state_dict(spec, 0)
     with pytest.raises(_lib.I2VError, match="hooked twice"):
@@ -164,63 +150,17 @@ def test_the_launches_refuse_what_they_cannot_run(eng):
     assert _rel(run_attn(eng, d)[0], mk.attn_reference(d)[0]) < 1e-6
 
 
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
-def _set_hook_grads(net, hg):
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        assert gd.numel() == g.shape[0] * hi.D
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-
-
-def _run(net, spec, stages, x, hg=None):
-    xd = x.float().cuda()
-    net.forward(xd)
-    n = x.shape[0]
-    feats = [net.save_hook(i, n).reshape(n, -1) for i in range(len(stages))]
-    assert all(f.shape[1] == spec.hook_dim(s) == hi.D for f, s, hi in zip(feats, stages, net.hooks))
-    if hg is None:
-        hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    _set_hook_grads(net, hg)
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    return [f.cpu() for f in feats], gx.cpu(), hg
-
-
 def _gsa_blocks(spec, stages):
     return sum(not spec.is_lsa(k, j) for k in range(max(stages) + 1) for j in range(spec.depths[k]))
 
 
 def _hooks_and_grad(eng, spec, sd, stages, x, max_frames=None):
-    net = eng.build_twins_net(spec, sd, stages, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(stages, max_frames or x.shape[0])
-    s0 = stat(eng)
-    feats, gx, hg = _run(net, spec, stages, x)
-    assert stat(eng) - s0 == 3 * _gsa_blocks(spec, stages)                # per GSA block: one attention launch forward, two backward
-    net.close()
-    return (feats, gx), hg
+    launches = 3 * _gsa_blocks(spec, stages)      # per GSA block: one attention launch forward, two backward
+    return hooks_and_grad(eng, spec, sd, stages, x, max_frames, launches=(COUNTER, launches))
 
 
 def _check(label, feats, gx, ref, x, hg):
-    rf = ref.forward(x)
-    errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, ref.backward(hg))
-    fp = FP32[label]
-    print(f"{label}: HIP vs float64: hooks {errs} grad {gerr}; fp32 CPU vs float64: {fp}")
-    for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
+    check_net(label, feats, gx, ref.forward(x), ref.backward(hg), FP32[label], NET_FLOOR)
 
 
 @pytest.mark.parametrize("label", sorted(mk.TWINS))
@@ -255,9 +195,9 @@ def test_twin_on_the_shared_launch_route(eng, label, monkeypatch):
     monkeypatch.setenv("I2V_TWINS_ATTN", "0")
     net = eng.build_twins_net(spec, sd, mk.HOOKS, x.shape[0])
     assert net.workspace_bytes() == spec.workspace_bytes(mk.HOOKS, x.shape[0]) > spec.workspace_bytes(mk.HOOKS, x.shape[0], composed=False)
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     feats, gx, hg = _run(net, spec, mk.HOOKS, x)
-    assert stat(eng) == s0
+    assert stat(eng, COUNTER) == s0
     net.close()
     _check(label, feats, gx, TwinsReference(spec, sd, mk.HOOKS), x, hg)
     net = eng.build_twins_net(spec, sd, mk.HOOKS, 1)
@@ -290,11 +230,7 @@ def test_i2v_trajectory_on_the_twin_matches_the_float64_trajectory():
     atk = attacks.ImageGuidedFMDirection_Adam([name], depth=3, step_size=0.005, steps=10, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(clip[0], dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(name, (clip[2], clip[2]))
-    ref = restate.run_attack([TwinsReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    print("costs", atk.last_costs, "float64", ref["costs"])
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"].float()).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, TwinsReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64), vid, rtol=TRAJECTORY_RTOL)
 
 
 def test_aens_of_the_twin_with_tiny_resnet_matches_the_oracle():

@@ -13,9 +13,11 @@ import torch
 from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
 from oracle import restate
+from tests.family_harness import check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, video as _video
 from tests.vit_reference import VitReference, gelu, layer_norm
 
 pytestmark = pytest.mark.gpu
+TRAJECTORY_RTOL = 2e-4      # of the trajectory's costs against the float64 run
 VIT = graphs.VIT_NAME
 
 
@@ -27,15 +29,6 @@ def eng():
 
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    return (torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64) * scale)
 
 
 @pytest.mark.parametrize("M,K,N", [(2 * 197, 72, 200), (2 * 17, 768, 132), (197, 3072, 768)])
@@ -116,36 +109,8 @@ def test_token_assembly_and_its_backward(eng, F, g, dim):
     assert _rel(gimg - 1, torch.autograd.grad(ref, ir, dt)[0]) < 1e-5
 
 
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
 def _hooks_and_grad(eng, spec, sd, blocks, x):
-    """Hook features and the input gradient of the HIP net for given random hook gradients (written straight into the gradient
-    views, where the loss kernels would write them)."""
-    net = eng.build_vit_net(spec, sd, blocks, x.shape[0])
-    xd = x.float().cuda()
-    net.forward(xd)
-    feats = [net.save_hook(i, x.shape[0]).reshape(x.shape[0], -1) for i in range(len(blocks))]
-    hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    out = [f.cpu() for f in feats], gx.cpu()
-    net.close()
-    return out, hg
+    return hooks_and_grad(eng, spec, sd, blocks, x)
 
 
 def test_tiny_vit_hooks_and_input_gradient(eng):
@@ -182,22 +147,12 @@ def test_full_vit_b16_hooks_and_input_gradient(eng):
     assert _rel(gx, rg) < 1e-3
 
 
-def _video(b, f, hw, seed):
-    gen = torch.Generator().manual_seed(seed)
-    u8 = torch.randint(0, 256, (b, 3, f, hw, hw), generator=gen, dtype=torch.uint8)
-    mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
-    std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
-    return (u8.float() / 255 - mean) / std
-
-
 def test_i2v_trajectory_on_the_tiny_vit_matches_the_restatement():
     vid = _video(2, 4, 64, 23)
     atk = attacks.ImageGuidedFMDirection_Adam([VIT], depth=2, step_size=0.005, steps=10, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(2, dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(VIT, (64, 64))
-    ref = restate.run_attack([VitReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(2)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
+    check_trajectory(atk, None, VitReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(2)], dtype=torch.float64), vid, rtol=TRAJECTORY_RTOL)
     mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
     std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
     a, o = adv * std + mean, vid * std + mean

@@ -14,9 +14,11 @@ import torch
 from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
 from oracle import restate
+from tests.family_harness import _hip, _set_hook_grads, check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, video as _video
 from tests.vit_family_reference import VitFamilyReference, gelu, layer_norm
 
 pytestmark = pytest.mark.gpu
+TRAJECTORY_RTOL = 2e-4      # of the trajectory's costs against the float64 run
 DISTILLED, PATCH32 = "deit_base_distilled_patch16_224", "vit_base_patch32_224"
 HOOK_BOUND, GRAD_BOUND = 2e-4, 1e-3            # relative L2 against float64: the bounds of the full ViT-B/16 test (tests/test_gpu_vit.py)
 # vit_large_patch16_224 (24 blocks), 2 frames, synthetic weights: relative L2 error of an fp32 CPU run of the restatement against its
@@ -33,15 +35,6 @@ def eng():
 
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    return (torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64) * scale)
 
 
 @pytest.mark.parametrize("accumulate", [0, 1])
@@ -145,41 +138,8 @@ def test_layernorm_on_the_family_shapes(eng, rows, Cw):
     assert _rel(dx, gref) < 1e-5
 
 
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
-def _set_hook_grads(net, hg):
-    """Random hook gradients written straight into the gradient views, where the loss kernels would write them."""
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-
-
 def _hooks_and_grad(eng, spec, sd, blocks, x):
-    net = eng.build_vit_net(spec, sd, blocks, x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(blocks, x.shape[0])
-    xd = x.float().cuda()
-    net.forward(xd)
-    feats = [net.save_hook(i, x.shape[0]).reshape(x.shape[0], -1) for i in range(len(blocks))]
-    assert all(f.shape[1] == spec.tokens * spec.dim == hi.D for f, hi in zip(feats, net.hooks))
-    hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    _set_hook_grads(net, hg)
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    out = [f.cpu() for f in feats], gx.cpu()
-    net.close()
-    return out, hg
+    return hooks_and_grad(eng, spec, sd, blocks, x)
 
 
 @pytest.mark.parametrize("name", [DISTILLED, PATCH32])
@@ -320,23 +280,13 @@ def test_create_refuses_more_rows_than_the_kernels_count_before_any_allocation(e
             capi.i2v_vit_destroy(h)
 
 
-def _video(b, f, hw, seed):
-    gen = torch.Generator().manual_seed(seed)
-    u8 = torch.randint(0, 256, (b, 3, f, hw, hw), generator=gen, dtype=torch.uint8)
-    mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
-    std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
-    return (u8.float() / 255 - mean) / std
-
-
 @pytest.mark.parametrize("name", [DISTILLED, PATCH32])
 def test_i2v_trajectory_on_the_tiny_twins_matches_the_restatement(name):
     vid = _video(2, 4, 64, 23)
     atk = attacks.ImageGuidedFMDirection_Adam([name], depth=2, step_size=0.005, steps=10, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(2, dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(name, (64, 64))
-    ref = restate.run_attack([VitFamilyReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(2)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
+    check_trajectory(atk, None, VitFamilyReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(2)], dtype=torch.float64), vid, rtol=TRAJECTORY_RTOL)
     mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
     std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
     a, o = adv * std + mean, vid * std + mean

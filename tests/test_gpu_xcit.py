@@ -21,35 +21,21 @@ from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
 from oracle import restate
 from tests import make_xcit_fixtures as mk
+from tests.family_harness import bound, check_net, check_trajectory, hooks_and_grad, rand as _rand, rel as _rel, run_net as _run, stat, video as _video
 from tests.xcit_reference import XcitReference
 
 pytestmark = pytest.mark.gpu
 NANO, TINY = "xcit_nano_12_p16_224", "xcit_tiny_12_p16_224"
 FP32 = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "xcit_fp32_cpu_errors.json")))
 NET_FLOOR, FWD_FLOOR, BWD_FLOOR = 1e-5, 1e-6, 1e-5
-
-
-def bound(fp32_err, floor=NET_FLOOR):
-    return max(floor, 4.0 * fp32_err)
+COUNTER = b"xcit_attention_launches"
+TRAJECTORY_RTOL = 2e-4      # of the trajectory's costs against the float64 run
 
 
 @pytest.fixture(scope="module")
 def eng():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return attacks.get_engine("cuda:0")
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def stat(eng, name=b"xcit_attention_launches"):
-    return int(eng.capi.i2v_backend_stat(name))
 
 
 def _dev(v):
@@ -68,9 +54,9 @@ def run_attn(eng, d):
 @pytest.mark.parametrize("F,T,H,dh,kind", mk.ATTN_CASES)
 def test_attention_kernel_against_float64_autograd(eng, F, T, H, dh, kind):
     d = mk.attn_case(F, T, H, dh, kind)
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     out, probs, dqkv = run_attn(eng, d)
-    assert stat(eng) - s0 == 2                                            # one launch forward, one backward
+    assert stat(eng, COUNTER) - s0 == 2                                            # one launch forward, one backward
     want, want_p, want_g = mk.attn_reference(d)
     fp = FP32["attention"][mk.case_key(F, T, H, dh, kind)]
     e_f, e_p = _rel(out, want), _rel(probs, want_p)
@@ -121,7 +107,7 @@ def test_the_launches_refuse_what_they_cannot_run(eng):
     z = torch.zeros(8192, device="cuda")
     p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
     capi = eng.capi
-    s0 = stat(eng)
+    s0 = stat(eng, COUNTER)
     fwd = lambda *, q=p(z), frames=1, T=4, H=2, dh=8, t=p(z): capi.i2v_xcit_attention_f32(q, frames, T, H, dh, t, p(z), p(z), p(z), None)      # noqa: E731
     off = C.c_void_p(z.data_ptr() + 4)
     for kw, why in ((dict(q=None), b"null"), (dict(t=None), b"null"), (dict(dh=6), b"multiple of 4"), (dict(H=1, dh=68), b"wider than 64"),
@@ -137,7 +123,7 @@ def test_the_launches_refuse_what_they_cannot_run(eng):
         assert b"xcit_dw3" in capi.i2v_last_error() and why in capi.i2v_last_error(), capi.i2v_last_error()
     assert capi.i2v_xcit_stem_gather_f32(p(z), None, 1, 5, 5, 3, 1, None) != 0 and b"null" in capi.i2v_last_error()
     assert capi.i2v_xcit_stem_scatter_f32(p(z), p(z), p(z), 1, 5, 5, 3, 1, 0, None) != 0 and b"pre-activation" in capi.i2v_last_error()
-    assert stat(eng) == s0                                                # nothing was launched
+    assert stat(eng, COUNTER) == s0                                                # nothing was launched
     spec = graphs.build_tiny(NANO, (64, 64))
     sd = weights.synthetic_state_dict(spec, 0)
     with pytest.raises(_lib.I2VError, match="hooked twice"):
@@ -154,59 +140,13 @@ def test_the_launches_refuse_what_they_cannot_run(eng):
     assert _rel(run_attn(eng, d)[0], mk.attn_reference(d)[0]) < 1e-6
 
 
-def _hip():
-    for path in (os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"), "libamdhip64.so"):
-        try:
-            return C.CDLL(path)
-        except OSError:
-            continue
-    raise OSError("libamdhip64.so not found")
-
-
-def _set_hook_grads(net, hg):
-    hip = _hip()
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    for hi, g in zip(net.hooks, hg):
-        gd = g.float().cuda().contiguous()
-        assert gd.numel() == g.shape[0] * hi.D
-        torch.cuda.synchronize()
-        assert hip.hipMemcpy(hi.grad, gd.data_ptr(), gd.numel() * 4, 3) == 0       # device to device
-
-
-def _run(net, spec, blocks, x, hg=None):
-    xd = x.float().cuda()
-    net.forward(xd)
-    n = x.shape[0]
-    feats = [net.save_hook(i, n).reshape(n, -1) for i in range(len(blocks))]
-    assert all(f.shape[1] == spec.hook_dim(b) == hi.D for f, b, hi in zip(feats, blocks, net.hooks))
-    if hg is None:
-        hg = [_rand(*f.shape, seed=30 + i) for i, f in enumerate(feats)]
-    torch.cuda.synchronize()
-    _set_hook_grads(net, hg)
-    gx = torch.empty_like(xd)
-    net.backward(gx)
-    torch.cuda.synchronize()
-    return [f.cpu() for f in feats], gx.cpu(), hg
-
-
 def _hooks_and_grad(eng, spec, sd, blocks, x, max_frames=None):
-    net = eng.build_xcit_net(spec, sd, blocks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(blocks, max_frames or x.shape[0])
-    s0 = stat(eng)
-    feats, gx, hg = _run(net, spec, blocks, x)
-    assert stat(eng) - s0 == 2 * (max(blocks) + 1)                        # per block: one attention launch forward, one backward
-    net.close()
-    return (feats, gx), hg
+    launches = 2 * (max(blocks) + 1)      # per block: one attention launch forward, one backward
+    return hooks_and_grad(eng, spec, sd, blocks, x, max_frames, launches=(COUNTER, launches))
 
 
 def _check(label, feats, gx, ref, x, hg):
-    rf = ref.forward(x)
-    errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, ref.backward(hg))
-    fp = FP32[label]
-    print(f"{label}: HIP vs float64: hooks {errs} grad {gerr}; fp32 CPU vs float64: {fp}")
-    for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
+    check_net(label, feats, gx, ref.forward(x), ref.backward(hg), FP32[label], NET_FLOOR)
 
 
 @pytest.mark.parametrize("label", sorted(mk.TWINS))
@@ -242,14 +182,6 @@ def test_full_size_model_at_224_depths_1_to_4_against_float64(eng, name):
     _check(name, feats, gx, XcitReference(spec, sd, blocks), x, hg)
 
 
-def _video(b, f, hw, seed):
-    gen = torch.Generator().manual_seed(seed)
-    u8 = torch.randint(0, 256, (b, 3, f, hw, hw), generator=gen, dtype=torch.uint8)
-    mean = torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)
-    std = torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
-    return (u8.float() / 255 - mean) / std
-
-
 def test_i2v_trajectory_on_the_twin_matches_the_float64_trajectory():
     """10 steps at depth 3.  The depth is chosen by the reference's own float32 error on this clip, measured on the CPU with
     `restate.run_attack` in float32 against float64: 7.2e-6 / 5.8e-5 / 4.0e-5 at depths 1 / 2 / 3, but 2.4e-4 at depth 4 -- there the
@@ -259,11 +191,7 @@ def test_i2v_trajectory_on_the_twin_matches_the_float64_trajectory():
     atk = attacks.ImageGuidedFMDirection_Adam([TINY], depth=3, step_size=0.005, steps=10, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(2, dtype=torch.long), ["a", "b"]).cpu()
     spec = graphs.build_tiny(TINY, (64, 64))
-    ref = restate.run_attack([XcitReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    print("costs", atk.last_costs, "float64", ref["costs"])
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"].float()).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, XcitReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(3)], dtype=torch.float64), vid, rtol=TRAJECTORY_RTOL)
 
 
 def test_aens_of_the_twin_with_tiny_resnet_matches_the_oracle():

@@ -19,6 +19,7 @@ from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
 from tests import make_mixer_fixtures as mk
 from tests import mixer_reference as mr
+from tests.family_harness import bound, check_trajectory, rand as _rand, rel as _rel, run_twin as _run_twin
 from tests.hostsim_util import hostsim_engine
 from tests.mixer_reference import MixerReference
 
@@ -35,18 +36,6 @@ MIXER, RESMLP = "mixer_b16_224", "resmlp_12_224"
 TWINS = {"mixer_test": MIXER, "mixer_test_patch32": "mixer_b32_224", "resmlp_test": RESMLP}
 FLOOR = 1e-5
 ALL_CASES = mk.HIDDEN_CASES + [(S, 0, Cn) for S, Cn in mk.LINEAR_CASES]
-
-
-def bound(fp32_err):
-    return max(FLOOR, 4.0 * fp32_err)
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
 
 
 # ---- the specs ---------------------------------------------------------------------------------------------------------------------
@@ -229,15 +218,15 @@ def test_native_packing_runs_the_planner_sequence_to_the_reference(twin):
     hooks = [1, 3, 5, 7]
     want = MixerReference(spec, sd, hooks).forward(x)
     for b, wf, fp in zip(hooks, want, FP32[twin]["hooks"]):
-        assert _rel(got[b], wf) < bound(fp)                    # (the arrays are float32 roundings of the float64 weights: ~1e-7)
+        assert _rel(got[b], wf) < bound(fp, FLOOR)                    # (the arrays are float32 roundings of the float64 weights: ~1e-7)
     assert len(spec.native_arrays(sd, 2)) == 2 + 2 * (12 if spec.kind == "mixer" else 9)
     if spec.kind == "resmlp":                                  # a dropped fold is far outside the bound
         assert tuple(arrays[2].shape) == (32,) and tuple(arrays[5].shape) == (4, 4) and tuple(arrays[7].shape) == (128, 32)
         ones = MixerReference(spec, sd, hooks, unit_ls=True).forward(x)
         nofold = MixerReference(spec, sd, hooks, no_norm2=True).forward(x)
         for b, wf, of, nf, fp in zip(hooks, want, ones, nofold, FP32[twin]["hooks"]):
-            assert _rel(of, wf) > 1000 * bound(fp) and _rel(nf, wf) > 1000 * bound(fp)
-            assert _rel(got[b], of) > 1000 * bound(fp) and _rel(got[b], nf) > 1000 * bound(fp)
+            assert _rel(of, wf) > 1000 * bound(fp, FLOOR) and _rel(nf, wf) > 1000 * bound(fp, FLOOR)
+            assert _rel(got[b], of) > 1000 * bound(fp, FLOOR) and _rel(got[b], nf) > 1000 * bound(fp, FLOOR)
 
 
 # ---- the token launch on the host simulation ---------------------------------------------------------------------------------------
@@ -269,7 +258,7 @@ def test_token_launch_on_the_host_simulation_against_float64(eng, S, Sh, Cn, N):
     fp = FP32["tokens"][mk.case_key(S, Sh, Cn, N)]
     e_f, e_b = _rel(out, want), _rel(dz, want_dz)
     print(f"tokens S {S} Sh {Sh} C {Cn}, {N} frames: forward {e_f:.3e} (fp32 CPU {fp['fwd']:.3e}) input gradient {e_b:.3e} (fp32 CPU {fp['bwd']:.3e})")
-    assert e_f < bound(fp["fwd"]) and e_b < bound(fp["bwd"])
+    assert e_f < bound(fp["fwd"], FLOOR) and e_b < bound(fp["bwd"], FLOOR)
     out2, dz2 = run_case(eng, d)
     assert torch.equal(out, out2) and torch.equal(dz, dz2)                # reruns: the same bits
     if N == 3:                                                            # frame 0 of the 3-frame launch: the bits of a 1-frame launch
@@ -381,27 +370,6 @@ def test_new_native_symbols_are_exported_by_the_library_and_the_host_simulation(
 
 
 # ---- the planner (csrc/i2v_mixer.cpp) on the host simulation -----------------------------------------------------------------------
-def _write_hook_grads(net, hg):
-    for hi, g in zip(net.hooks, hg):
-        flat = g.float().reshape(g.shape[0], -1).contiguous()
-        for n in range(flat.shape[0]):
-            C.memmove(hi.grad + 4 * n * hi.grad_stride, flat[n].data_ptr(), 4 * hi.D)
-
-
-def _run_twin(eng, spec, sd, blocks, x, hg, max_frames=None):
-    net = eng.build_mixer_net(spec, sd, blocks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(blocks, max_frames or x.shape[0])
-    xf = x.float().contiguous()
-    net.forward(xf)
-    feats = [net.save_hook(i, x.shape[0]).reshape(x.shape[0], -1) for i in range(len(blocks))]
-    assert all(f.shape[1] == spec.hook_dim(b) == hi.D for f, b, hi in zip(feats, blocks, net.hooks))
-    _write_hook_grads(net, hg)
-    gx = torch.empty_like(xf)
-    net.backward(gx)
-    net.close()
-    return feats, gx
-
-
 @pytest.mark.parametrize("twin", sorted(TWINS))
 def test_twins_on_the_host_simulation_against_float64(eng, twin):
     """Features at all four depths and the input gradient with all four hook gradients flowing, 3 frames; a net planned for 5 frames
@@ -419,8 +387,8 @@ def test_twins_on_the_host_simulation_against_float64(eng, twin):
     errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, want_gx)
     print(f"{twin} on the host simulation vs float64: hooks {errs} grad {gerr}; fp32 CPU: {fp['hooks']} {fp['grad']}")
     for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
+        assert e < bound(cpu, FLOOR)
+    assert gerr < bound(fp["grad"], FLOOR)
     feats2, gx2 = _run_twin(eng, spec, sd, blocks, x, hg, max_frames=5)
     assert all(torch.equal(a, b) for a, b in zip(feats, feats2)) and torch.equal(gx, gx2)
     f1, g1 = _run_twin(eng, spec, sd, blocks, x[:1], [h[:1] for h in hg])
@@ -433,7 +401,7 @@ def test_twins_on_the_host_simulation_against_float64(eng, twin):
     assert torch.equal(fa[0], feats[1])
     ref1 = MixerReference(spec, sd, [blocks[1]])
     ref1.forward(x)
-    assert _rel(ga, ref1.backward([hg[1]])) < bound(fp["grad"])
+    assert _rel(ga, ref1.backward([hg[1]])) < bound(fp["grad"], FLOOR)
 
 
 def test_planner_refusals_on_the_host_simulation(eng):
@@ -463,10 +431,7 @@ def test_i2v_trajectory_on_the_mixer_twin_matches_the_reference(eng):
                                               weight_seed=0)
     adv = atk(vid, torch.zeros(1, dtype=torch.long), ["t"])
     g = graphs.build_tiny(MIXER, (64, 64))
-    ref = restate.run_attack([MixerReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(3)], dtype=torch.float32)], vid,
-                             steps=4, step_size=0.005)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"]).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, MixerReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(3)], dtype=torch.float32), vid, rtol=2e-4, steps=4)
 
 
 def test_aens_and_ens_of_the_twins_with_tiny_resnet_match_the_oracle(eng):

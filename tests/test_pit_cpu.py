@@ -12,14 +12,13 @@ import ctypes as C
 import json
 import os
 
-import numpy as np
 import pytest
 import torch
 
 from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
-from oracle import restate
 from tests import make_pit_fixtures as mk
+from tests.family_harness import bound, check_net, check_trajectory, rand as _rand, rel as _rel, run_twin as _run_twin
 from tests.hostsim_util import hostsim_engine
 from tests.pit_reference import PitReference
 
@@ -29,18 +28,6 @@ FP32 = json.load(open(os.path.join(ROOT, "tests", "golden", "pit_fp32_cpu_errors
 NAMES = sorted(KEYS["names"])
 S, BD = "pit_s_224", "pit_b_distilled_224"
 NET_FLOOR, FWD_FLOOR, BWD_FLOOR = 1e-5, 1e-6, 1e-5
-
-
-def bound(fp32_err, floor=NET_FLOOR):
-    return max(floor, 4.0 * fp32_err)
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
 
 
 def _f(v):
@@ -316,27 +303,6 @@ def test_entry_refusals_on_the_host_simulation(eng):
 
 
 # ---- the planner (csrc/i2v_pit.cpp) on the host simulation -------------------------------------------------------------------------
-def write_hook_grads(net, hg):
-    for hi, g in zip(net.hooks, hg):
-        flat = g.float().reshape(g.shape[0], -1).contiguous()
-        for n in range(flat.shape[0]):
-            C.memmove(hi.grad + 4 * n * hi.grad_stride, flat[n].data_ptr(), 4 * hi.D)
-
-
-def _run_twin(eng, spec, sd, hooks, x, hg, max_frames=None):
-    net = eng.build_pit_net(spec, sd, hooks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(hooks, max_frames or x.shape[0])      # the formula against the plan
-    xf = x.float().contiguous()
-    net.forward(xf)
-    feats = [net.save_hook(i, x.shape[0]).reshape(x.shape[0], -1) for i in range(len(hooks))]
-    assert all(f.shape[1] == hi.D == spec.hook_shape(b)[0] * spec.hook_shape(b)[1] for f, hi, b in zip(feats, net.hooks, hooks))
-    write_hook_grads(net, hg)
-    gx = torch.empty_like(xf)
-    net.backward(gx)
-    net.close()
-    return feats, gx
-
-
 def twin_reference(label):
     name, side, _ = mk.TWINS[label]
     spec = graphs.build_tiny(name, (side, side))
@@ -355,15 +321,6 @@ def twin_refs():
     return {label: twin_reference(label) for label in mk.TWINS}
 
 
-def check_net(label, feats, gx, rf, want_gx):
-    fp = FP32[label]
-    errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, want_gx)
-    print(f"{label} vs float64: hooks {errs} grad {gerr}; fp32 CPU: {fp['hooks']} {fp['grad']}")
-    for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
-
-
 @pytest.mark.parametrize("label", sorted(mk.TWINS))
 def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
     """Features at all four depths and the input gradient with all four hook gradients flowing (a hook behind the last block of stages 0
@@ -372,7 +329,7 @@ def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
     spec, sd, x, hooks, rf, hg, want_gx = twin_refs[label]
     assert spec.arch == label
     feats, gx = _run_twin(eng, spec, sd, hooks, x, hg)
-    check_net(label, feats, gx, rf, want_gx)
+    check_net(label, feats, gx, rf, want_gx, FP32[label], NET_FLOOR)
     f1, g1 = _run_twin(eng, spec, sd, hooks, x[:1], [h[:1] for h in hg])
     assert all(torch.equal(a[:1], b) for a, b in zip(feats, f1)) and torch.equal(gx[:1], g1)
     feats2, gx2 = _run_twin(eng, spec, sd, hooks[::-1], x, hg[::-1], max_frames=5)
@@ -382,7 +339,7 @@ def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
         assert torch.equal(fa[0], feats[i])
         ref1 = PitReference(spec, sd, [hooks[i]])
         ref1.forward(x)
-        assert _rel(ga, ref1.backward([hg[i]])) < bound(FP32[label]["grad"])
+        assert _rel(ga, ref1.backward([hg[i]])) < bound(FP32[label]["grad"], NET_FLOOR)
 
 
 @pytest.mark.parametrize("label", sorted(mk.TWINS))
@@ -394,7 +351,7 @@ def test_twin_on_the_shared_launch_route_against_float64(eng, twin_refs, label, 
     monkeypatch.setenv("I2V_PIT_ATTN", "0")
     feats, gx = _run_twin(eng, spec, sd, hooks, x, hg)                    # (checks the planned bytes against the formula under the switch)
     assert spec.workspace_bytes(hooks, x.shape[0]) != plain
-    check_net(label, feats, gx, rf, want_gx)
+    check_net(label, feats, gx, rf, want_gx, FP32[label], NET_FLOOR)
     monkeypatch.delenv("I2V_PIT_ATTN")
     feats0, gx0 = _run_twin(eng, spec, sd, hooks, x, hg)
     assert all(_rel(a, b) < 1e-5 for a, b in zip(feats, feats0)) and _rel(gx, gx0) < 1e-5
@@ -412,7 +369,7 @@ def test_leaving_the_new_arithmetic_out_is_seen(eng, twin_refs, what):
     depths = (1, 2, 3) if what == "pool" else (0, 1, 2, 3)
     for i in depths:
         cpu = FP32["pit_test_70"]["hooks"][i]
-        assert _rel(without[i], rf[i]) > 100 * bound(cpu) and _rel(feats[i], without[i]) > 100 * bound(cpu)
+        assert _rel(without[i], rf[i]) > 100 * bound(cpu, NET_FLOOR) and _rel(feats[i], without[i]) > 100 * bound(cpu, NET_FLOOR)
     blind = dict(sd)                                                       # ... and through the packing: the same state dict with the term changed
     if what == "pos":
         blind["pos_embed"] = torch.zeros_like(sd["pos_embed"])
@@ -424,7 +381,7 @@ def test_leaving_the_new_arithmetic_out_is_seen(eng, twin_refs, what):
     fb, _ = _run_twin(eng, spec, blind, hooks, x, hg)
     for i in depths:
         cpu = FP32["pit_test_70"]["hooks"][i]
-        assert _rel(fb[i], feats[i]) > 100 * bound(cpu) and _rel(fb[i], without[i]) < bound(cpu)
+        assert _rel(fb[i], feats[i]) > 100 * bound(cpu, NET_FLOOR) and _rel(fb[i], without[i]) < bound(cpu, NET_FLOOR)
 
 
 def test_planner_refusals_on_the_host_simulation(eng):
@@ -486,6 +443,4 @@ def test_i2v_trajectory_on_the_twin_matches_the_reference(eng):
     atk = attacks.ImageGuidedFMDirection_Adam([S], depth=3, step_size=0.005, steps=4, engine=eng, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(1, dtype=torch.long), ["t"])
     g = graphs.build_tiny(S, (64, 64))
-    ref = restate.run_attack([PitReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(3)], dtype=torch.float32)], vid, steps=4, step_size=0.005)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=2e-4)
-    assert float((adv - ref["adv"]).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, PitReference(g, weights.synthetic_state_dict(g, 0), [g.hook_for(3)], dtype=torch.float32), vid, rtol=2e-4, steps=4)

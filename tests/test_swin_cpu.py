@@ -11,6 +11,7 @@ from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
 from tests import swin_reference as sr
 from tests import vit_family_reference as fam
+from tests.family_harness import rand as _rand
 from tests.swin_reference import SwinReference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,10 +27,6 @@ NAMES = sorted(TABLE)
 TINY = "swin_tiny_patch4_window7_224"
 BLOCK_KEYS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.relative_position_bias_table", "attn.proj.weight",
               "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
 
 
 @pytest.mark.parametrize("name", NAMES)

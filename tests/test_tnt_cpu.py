@@ -10,14 +10,13 @@ import ctypes as C
 import json
 import os
 
-import numpy as np
 import pytest
 import torch
 
 from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
-from oracle import restate
 from tests import make_tnt_fixtures as mk
+from tests.family_harness import bound, check_net, check_trajectory, rand as _rand, rel as _rel, run_twin as _run_twin
 from tests.hostsim_util import hostsim_engine
 from tests.tnt_reference import TntReference
 
@@ -28,18 +27,6 @@ NAMES = sorted(KEYS["names"])
 SMALL = "tnt_s_patch16_224"
 NET_FLOOR, FWD_FLOOR, BWD_FLOOR = 1e-5, 1e-6, 1e-5
 FWD_PARTS = ("out", "gather")
-
-
-def bound(fp32_err, floor=NET_FLOOR):
-    return max(floor, 4.0 * fp32_err)
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
-
-
-def _rel(a, b):
-    return float((a.double().cpu() - b.double().cpu()).norm() / b.double().cpu().norm())
 
 
 def _f(v):
@@ -303,27 +290,6 @@ def test_entry_refusals_on_the_host_simulation(eng):
 
 
 # ---- the planner (csrc/i2v_tnt.cpp) on the host simulation -------------------------------------------------------------------------
-def write_hook_grads(net, hg):
-    for hi, g in zip(net.hooks, hg):
-        flat = g.float().reshape(g.shape[0], -1).contiguous()
-        for n in range(flat.shape[0]):
-            C.memmove(hi.grad + 4 * n * hi.grad_stride, flat[n].data_ptr(), 4 * hi.D)
-
-
-def _run_twin(eng, spec, sd, hooks, x, hg, max_frames=None):
-    net = eng.build_tnt_net(spec, sd, hooks, max_frames or x.shape[0])
-    assert net.workspace_bytes() == spec.workspace_bytes(hooks, max_frames or x.shape[0])      # the formula against the plan
-    xf = x.float().contiguous()
-    net.forward(xf)
-    feats = [net.save_hook(i, x.shape[0]).reshape(x.shape[0], -1) for i in range(len(hooks))]
-    assert all(f.shape[1] == hi.D == spec.hook_dim for f, hi in zip(feats, net.hooks))
-    write_hook_grads(net, hg)
-    gx = torch.empty_like(xf)
-    net.backward(gx)
-    net.close()
-    return feats, gx
-
-
 def twin_reference(label):
     name, side, _ = mk.TWINS[label]
     spec = graphs.build_tiny(name, (side, side))
@@ -342,15 +308,6 @@ def twin_refs():
     return {label: twin_reference(label) for label in mk.TWINS}
 
 
-def check_net(label, feats, gx, rf, want_gx):
-    fp = FP32[label]
-    errs, gerr = [_rel(a, b) for a, b in zip(feats, rf)], _rel(gx, want_gx)
-    print(f"{label} vs float64: hooks {errs} grad {gerr}; fp32 CPU: {fp['hooks']} {fp['grad']}")
-    for e, cpu in zip(errs, fp["hooks"]):
-        assert e < bound(cpu)
-    assert gerr < bound(fp["grad"])
-
-
 @pytest.mark.parametrize("label", sorted(mk.TWINS))
 def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
     """Features at all four depths and the input gradient with all four hook gradients flowing (a hook below the deepest is added to the
@@ -360,7 +317,7 @@ def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
     spec, sd, x, hooks, rf, hg, want_gx = twin_refs[label]
     assert spec.arch == label
     feats, gx = _run_twin(eng, spec, sd, hooks, x, hg)
-    check_net(label, feats, gx, rf, want_gx)
+    check_net(label, feats, gx, rf, want_gx, FP32[label], NET_FLOOR)
     f1, g1 = _run_twin(eng, spec, sd, hooks, x[:1], [h[:1] for h in hg])
     assert all(torch.equal(a[:1], b) for a, b in zip(feats, f1)) and torch.equal(gx[:1], g1)
     feats2, gx2 = _run_twin(eng, spec, sd, hooks[::-1], x, hg[::-1], max_frames=5)
@@ -370,7 +327,7 @@ def test_twin_on_the_host_simulation_against_float64(eng, twin_refs, label):
         assert torch.equal(fa[0], feats[i])
         ref1 = TntReference(spec, sd, [hooks[i]])
         ref1.forward(x)
-        assert _rel(ga, ref1.backward([hg[i]])) < bound(FP32[label]["grad"])
+        assert _rel(ga, ref1.backward([hg[i]])) < bound(FP32[label]["grad"], NET_FLOOR)
 
 
 @pytest.mark.parametrize("what", ["inner", "pixel_pos"])
@@ -380,7 +337,7 @@ def test_leaving_the_new_arithmetic_out_is_seen(twin_refs, what):
     spec, sd, x, hooks, rf, _, _ = twin_refs["tnt_test_48"]
     without = TntReference(spec, sd, hooks, skip=(what,)).forward(x)
     for i in range(4):
-        assert _rel(without[i], rf[i]) > 100 * bound(FP32["tnt_test_48"]["hooks"][i])
+        assert _rel(without[i], rf[i]) > 100 * bound(FP32["tnt_test_48"]["hooks"][i], NET_FLOOR)
 
 
 def test_planner_refusals_on_the_host_simulation(eng):
@@ -436,14 +393,10 @@ def test_i2v_trajectory_on_the_twin_matches_the_float64_trajectory(eng):
     label, depth = "tnt_test", mk.TRAJECTORY_DEPTH
     name, side, _ = mk.TWINS[label]
     clip = mk.TRAJECTORY_CLIP
-    rtol = bound(FP32["trajectory"][label][str(depth)])
+    rtol = bound(FP32["trajectory"][label][str(depth)], NET_FLOOR)
     vid = mk.video(*clip)
     atk = attacks.ImageGuidedFMDirection_Adam([name], depth=depth, step_size=0.005, steps=10, engine=eng, graph_builder=graphs.build_tiny, weight_seed=0)
     adv = atk(vid, torch.zeros(clip[0], dtype=torch.long), ["a", "b"])
     spec = graphs.build_tiny(name, (side, side))
     assert spec.arch == label
-    ref = restate.run_attack([TntReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(depth)], dtype=torch.float64)],
-                             vid, steps=10, step_size=0.005)
-    print("costs", atk.last_costs, "float64", ref["costs"], "rtol", rtol)
-    np.testing.assert_allclose(atk.last_costs, ref["costs"], rtol=rtol)
-    assert float((adv - ref["adv"].float()).abs().mean()) < 5e-3
+    check_trajectory(atk, adv, TntReference(spec, weights.synthetic_state_dict(spec, 0), [spec.hook_for(depth)], dtype=torch.float64), vid, rtol=rtol)

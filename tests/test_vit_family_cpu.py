@@ -10,6 +10,7 @@ import torch
 from i2v_amd import attacks, graphs, weights
 from i2v_amd import lib as _lib
 from tests import vit_family_reference as fam
+from tests.family_harness import rand as _rand
 from tests.vit_family_reference import VitFamilyReference
 from tests.vit_reference import VitReference
 
@@ -33,10 +34,6 @@ TABLE = {
 NAMES = sorted(TABLE)
 BLOCK_KEYS = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
               "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
-
-
-def _rand(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
 
 
 def test_one_prefix_restatement_equals_the_vit_b16_restatement_exactly():

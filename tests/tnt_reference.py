@@ -13,10 +13,10 @@ of `TntSpec.native_arrays` (qk stacked on v, the padded filter rows, pixel_pos p
   attention  qk = Linear(dim, 2 dim) without bias, split (2, heads, dh); v = Linear(dim, dim) without bias; softmax(dh^-0.5 q k^T) v; proj
 `norm` and `head` lie behind every hook and are not restated.
 """
-from typing import Sequence
-
 import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 
 def attention_core(qkv, heads):
@@ -79,24 +79,7 @@ def streams(x, sd, spec, n_blocks, skip=()):
     return outs
 
 
-class TntReference:
-    """The interface of the other references (`forward` -> the hooked features as (frames, D), `backward` of hook gradients -> the input
-    gradient by autograd), which `oracle.restate.run_attack` drives.  `skip` names what the sensitivity checks leave out: "inner" (no
-    inner transformer: the pixel tokens reach every block's proj as embedded), "pixel_pos" (no pixel position table)."""
-
-    def __init__(self, spec, state_dict, hook_blocks: Sequence[int], dtype=torch.float64, device="cpu", skip=()):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_blocks)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self.skip = tuple(skip)
-        self._x = self._feats = None
-
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        outs = streams(self._x, self.sd, self.spec, max(self.hooks) + 1, self.skip)
-        self._feats = [outs[k].reshape(x.shape[0], -1) for k in self.hooks]
-        return [f.detach() for f in self._feats]
-
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+#: `skip` names what the sensitivity checks leave out: "inner" (no inner transformer: the pixel tokens reach every block's proj as
+#: embedded), "pixel_pos" (no pixel position table).
+class TntReference(StreamsReference):
+    streams = staticmethod(streams)

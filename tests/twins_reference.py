@@ -13,10 +13,9 @@ tested, not assumed.
              groups put back;  proj
 `norm` and `head` lie behind every hook and are not restated.
 """
-from typing import Sequence
-
-import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 PE_EPS = 1e-5
 
@@ -89,24 +88,7 @@ def stages(x, sd, spec, n_stages, skip=()):
     return outs
 
 
-class TwinsReference:
-    """The interface of the other references (`forward` -> the hooked features as (frames, D), `backward` of hook gradients -> the input
-    gradient by autograd), which `oracle.restate.run_attack` drives.  `skip` names what the sensitivity checks leave out: "peg" (no
-    position encoding), "sr_norm" (the sub-sampled plane without its LayerNorm)."""
-
-    def __init__(self, spec, state_dict, hook_stages: Sequence[int], dtype=torch.float64, device="cpu", skip=()):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_stages)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self.skip = tuple(skip)
-        self._x = self._feats = None
-
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        outs = stages(self._x, self.sd, self.spec, max(self.hooks) + 1, self.skip)
-        self._feats = [outs[s].reshape(x.shape[0], -1) for s in self.hooks]
-        return [f.detach() for f in self._feats]
-
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+#: `skip` names what the sensitivity checks leave out: "peg" (no position encoding), "sr_norm" (the sub-sampled plane without its
+#: LayerNorm).
+class TwinsReference(StreamsReference):
+    streams = staticmethod(stages)

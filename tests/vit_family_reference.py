@@ -16,6 +16,8 @@ from typing import Sequence
 import torch
 import torch.nn.functional as F
 
+from tests.family_harness import StreamsReference
+
 PREFIX_KEYS = ("cls_token", "dist_token")
 
 
@@ -65,19 +67,9 @@ def run_blocks(t, sd, spec, hook_blocks: Sequence[int]):
     return [outs[b] for b in hook_blocks]
 
 
-class VitFamilyReference:
-    def __init__(self, spec, state_dict, hook_blocks: Sequence[int], dtype=torch.float64, device="cpu"):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_blocks)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self._x = self._feats = None
+def streams(x, sd, spec, n_blocks):
+    return run_blocks(embed(x, sd, spec), sd, spec, list(range(n_blocks)))
 
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        outs = run_blocks(embed(self._x, self.sd, self.spec), self.sd, self.spec, self.hooks)
-        self._feats = [o.reshape(x.shape[0], -1) for o in outs]
-        return [f.detach() for f in self._feats]
 
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+class VitFamilyReference(StreamsReference):
+    streams = staticmethod(streams)

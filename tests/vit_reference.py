@@ -2,10 +2,10 @@
 definition (timm `VisionTransformer`, `vit_base_patch16_224`), independent of the HIP path.  It has the interface of
 `oracle.restate.OracleNet` that `oracle.restate.run_attack` drives: `.dtype`, `.hooks`, `.forward(x) -> [hook features]` and
 `.backward(hook_grads) -> d cost / d x`; every hook feature is (frames, tokens * dim), the residual stream after its block."""
-from typing import Sequence
-
 import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 
 def layer_norm(x, w, b, eps):
@@ -41,23 +41,14 @@ def block(x, sd, spec, i):
     return x + (h @ sd[k + "mlp.fc2.weight"].T + sd[k + "mlp.fc2.bias"])
 
 
-class VitReference:
-    def __init__(self, spec, state_dict, hook_blocks: Sequence[int], dtype=torch.float64, device="cpu"):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_blocks)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self._x = self._feats = None
+def streams(x, sd, spec, n_blocks):
+    """The residual streams behind the blocks 0 .. n_blocks - 1, each (frames, tokens, dim)."""
+    t, outs = embed(x, sd, spec), []
+    for i in range(n_blocks):
+        t = block(t, sd, spec, i)
+        outs.append(t)
+    return outs
 
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        t = embed(self._x, self.sd, self.spec)
-        outs = {}
-        for i in range(max(self.hooks) + 1):
-            t = block(t, self.sd, self.spec, i)
-            outs[i] = t
-        self._feats = [outs[b].reshape(x.shape[0], -1) for b in self.hooks]
-        return [f.detach() for f in self._feats]
 
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype) for h in hook_grads])[0]
-        return g.detach()
+class VitReference(StreamsReference):
+    streams = staticmethod(streams)

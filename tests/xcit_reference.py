@@ -15,10 +15,11 @@ the three LayerScales multiply their branch's output, q and k are normalised BEF
 The class-attention blocks, `cls_token`, `norm` and `head` lie behind every hook and are not restated.
 """
 import math
-from typing import Sequence
 
 import torch
 import torch.nn.functional as F
+
+from tests.family_harness import StreamsReference
 
 BN_EPS = 1e-5
 
@@ -96,27 +97,16 @@ def block(x, sd, spec, i: int, skip=()):
     return x + g2 * F.linear(F.gelu(F.linear(t, sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"])), sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"])
 
 
-class XcitReference:
-    """The interface of the other references (`forward` -> the hooked features as (frames, D), `backward` of hook gradients -> the input
-    gradient by autograd), which `oracle.restate.run_attack` drives.  `skip` names what the sensitivity checks leave out, one fold each:
-    "stem_bn", "pos", "gamma1", "gamma2", "gamma3", "lpi_bn", "temperature" (a BatchNorm skipped, a LayerScale or temperature of one)."""
+def streams(x, sd, spec, n_blocks, skip=()):
+    """The residual streams behind the blocks 0 .. n_blocks - 1, each (frames, tokens, dim)."""
+    t, outs = stem(x, sd, spec, skip), []
+    for i in range(n_blocks):
+        t = block(t, sd, spec, i, skip)
+        outs.append(t)
+    return outs
 
-    def __init__(self, spec, state_dict, hook_blocks: Sequence[int], dtype=torch.float64, device="cpu", skip=()):
-        self.spec, self.dtype, self.device = spec, dtype, torch.device(device)
-        self.hooks = list(hook_blocks)
-        self.sd = {k: v.to(dtype).to(self.device) for k, v in state_dict.items()}
-        self.skip = tuple(skip)
-        self._x = self._feats = None
 
-    def forward(self, x: torch.Tensor):
-        self._x = x.detach().to(self.dtype).to(self.device).requires_grad_(True)
-        t, outs = stem(self._x, self.sd, self.spec, self.skip), {}
-        for i in range(max(self.hooks) + 1):
-            t = block(t, self.sd, self.spec, i, self.skip)
-            outs[i] = t
-        self._feats = [outs[b].reshape(x.shape[0], -1) for b in self.hooks]
-        return [f.detach() for f in self._feats]
-
-    def backward(self, hook_grads: Sequence[torch.Tensor]) -> torch.Tensor:
-        g = torch.autograd.grad(self._feats, self._x, [h.to(self.dtype).to(self.device) for h in hook_grads])[0]
-        return g.detach()
+#: `skip` names what the sensitivity checks leave out, one fold each: "stem_bn", "pos", "gamma1", "gamma2", "gamma3", "lpi_bn",
+#: "temperature" (a BatchNorm skipped, a LayerScale or temperature of one).
+class XcitReference(StreamsReference):
+    streams = staticmethod(streams)

@@ -17,30 +17,11 @@ Times CALLS: one HIP event pair around each side's calls (the ctypes calls and t
 import argparse
 import ctypes as C
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "image-to-video-i2v-attack_amd"), ROOT]
+from bench_util import timed
 #: label -> (T, H, dh)
 SHAPES = {"base": (197, 12, 64), "large": (197, 16, 64)}
 FLOOR_TBS, FLOOR_TFLOPS = 4.7, 157.3
-
-
-def timed(fn, reps):
-    import torch
-    for _ in range(5):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
 
 
 def one(label, Fr, reps):
@@ -99,16 +80,16 @@ def one(label, Fr, reps):
     assert max(agree.values()) < 1e-5, agree                               # the two sides compute the same thing
     xr = qkv.clone().requires_grad_(True)
     with torch.no_grad():
-        eager_f = timed(lambda: attn_core(xr, bias, H), reps)
+        eager_f = timed(lambda: attn_core(xr, bias, H), reps, 5)
     y = attn_core(xr, bias, H)
-    eager_b = timed(lambda: torch.autograd.grad(y, xr, dout, retain_graph=True), reps)
+    eager_b = timed(lambda: torch.autograd.grad(y, xr, dout, retain_graph=True), reps, 5)
     del y
     row = {"shape": label, "frames": Fr, "T": T, "heads": H, "dh": dh, "composition_agrees_to": agree}
     prod = Fr * H * T * T * dh
     for name, fn, comp, floats, flop, eg in (("forward", fwd, comp_fwd, Fr * (qs + os_) + H * T * T, 4 * prod, eager_f),
                                              ("input_gradient", bwd, comp_bwd, Fr * (2 * qs + os_) + H * T * T, 10 * prod, eager_b)):
-        ms, lo, hi = timed(fn, reps)
-        cms, clo, chi = timed(comp, reps)
+        ms, lo, hi = timed(fn, reps, 5)
+        cms, clo, chi = timed(comp, reps, 5)
         bfl, afl = floats * 4 / (FLOOR_TBS * 1e12) * 1e3, flop / (FLOOR_TFLOPS * 1e12) * 1e3
         row[name] = {"call_ms": round(ms, 4), "fastest_slowest_ms": [round(lo, 4), round(hi, 4)], "byte_floor_ms": round(bfl, 4),
                      "arithmetic_floor_ms": round(afl, 4), "bound_by": "bytes" if bfl >= afl else "arithmetic",

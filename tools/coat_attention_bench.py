@@ -14,30 +14,11 @@ Times CALLS: one HIP event pair around each side's calls (the ctypes calls and t
 are timed together, as the entry runs them.  Prints one JSON line per shape."""
 import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "image-to-video-i2v-attack_amd"), ROOT]
+from bench_util import timed
 #: label -> (grid, heads, dh): the four stages of coat_lite_tiny, and stages 2 and 3 of coat_lite_mini / coat_lite_small
 SHAPES = {"t0": (56, 8, 8), "t1": (28, 8, 16), "t2": (14, 8, 32), "t3": (7, 8, 40), "s2": (14, 8, 40), "s3": (7, 8, 64)}
 FLOOR_TBS = 4.7
-
-
-def timed(fn, reps):
-    import torch
-    for _ in range(5):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
 
 
 def one(label, Fr, reps):
@@ -68,8 +49,8 @@ def one(label, Fr, reps):
     agree = {"out": rel(out, y.detach()), "dq": rel(dqkv[:, :, :Cn], gq[:, :, :Cn]), "dv": rel(dqkv[:, :, 2 * Cn:], gq[:, :, 2 * Cn:]), "dE": rel(dE, gE)}
     assert max(agree.values()) < 1e-4, agree
     with torch.no_grad():
-        eager_f = timed(lambda: cr.factor_core(xr, Er, H), reps)
-    eager_b = timed(lambda: torch.autograd.grad(y, (xr, Er), dout, retain_graph=True), reps)
+        eager_f = timed(lambda: cr.factor_core(xr, Er, H), reps, 5)
+    eager_b = timed(lambda: torch.autograd.grad(y, (xr, Er), dout, retain_graph=True), reps, 5)
     del y
 
     def crpe_eager(v):
@@ -80,9 +61,9 @@ def one(label, Fr, reps):
             at += w.shape[0]
         return torch.cat(parts, dim=1).flatten(2).transpose(1, 2)
     with torch.no_grad():
-        eager_dw = timed(lambda: crpe_eager(vr), reps)
+        eager_dw = timed(lambda: crpe_eager(vr), reps, 5)
     ye = crpe_eager(vr)
-    eager_dwb = timed(lambda: torch.autograd.grad(ye, vr, dout[:, 1:], retain_graph=True), reps)
+    eager_dwb = timed(lambda: torch.autograd.grad(ye, vr, dout[:, 1:], retain_graph=True), reps, 5)
     del ye
     row = {"shape": label, "frames": Fr, "T": T, "heads": H, "dh": dh, "eager_agrees_to": agree}
     qs, os_ = Fr * T * 3 * Cn, Fr * T * Cn
@@ -97,7 +78,7 @@ def one(label, Fr, reps):
              ("dwmix", lambda: eng.coat_dwmix(qkv, packed, bcat, g, 1, False, 2 * Cn, Cn), 2 * os_, eager_dw),
              ("dwmix_input_gradient", lambda: eng.coat_dwmix(dE, packed, None, g, 1, False, bwd=True, into=dqkv, into_col=2 * Cn), 3 * os_, eager_dwb))
     for name, fn, floats, eg in cases:
-        ms, lo, hi = timed(fn, reps)
+        ms, lo, hi = timed(fn, reps, 5)
         bfl = floats * 4 / (FLOOR_TBS * 1e12) * 1e3
         row[name] = {"call_ms": round(ms, 4), "fastest_slowest_ms": [round(lo, 4), round(hi, 4)], "byte_floor_ms": round(bfl, 4),
                      "share_of_floor": round(bfl / ms, 3), "eager_ms": round(eg[0], 4), "eager_fastest_slowest_ms": [round(eg[1], 4), round(eg[2], 4)],

@@ -15,30 +15,11 @@ Times CALLS: one HIP event pair around each C entry (the ctypes call and its lau
 of `reps` warm calls after 3 warm-up calls.  Prints one JSON line per shape."""
 import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "image-to-video-i2v-attack_amd"), ROOT]
+from bench_util import timed
 #: name -> (T, H, dh)
 SHAPES = (("convit_tiny", 196, 4, 48), ("convit_small", 196, 9, 48), ("convit_base", 196, 16, 48))
 PEAK_TFLOPS = 157.3
-
-
-def timed(fn, reps):
-    import torch
-    for _ in range(3):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
 
 
 def main():
@@ -79,18 +60,18 @@ def main():
         qr = qkv.clone().requires_grad_(True)
         tab = table[:, :, :T].contiguous()
         with torch.no_grad():
-            eager_f = timed(lambda: blend_attention(qr, H, scale, c, tab), a.reps)
+            eager_f = timed(lambda: blend_attention(qr, H, scale, c, tab), a.reps, 3)[0]
         y, _ = blend_attention(qr, H, scale, c, tab)
-        eager_b = timed(lambda: torch.autograd.grad(y, qr, dout, retain_graph=True), a.reps)
+        eager_b = timed(lambda: torch.autograd.grad(y, qr, dout, retain_graph=True), a.reps, 3)[0]
         del y
-        vit_f = timed(vit_fwd, a.reps)
-        vit_b = timed(vit_bwd, a.reps)
-        null_f = timed(lambda: fwd(None, None), a.reps)
-        null_b = timed(lambda: bwd(None, None), a.reps)
+        vit_f = timed(vit_fwd, a.reps, 3)[0]
+        vit_b = timed(vit_bwd, a.reps, 3)[0]
+        null_f = timed(lambda: fwd(None, None), a.reps, 3)[0]
+        null_b = timed(lambda: bwd(None, None), a.reps, 3)[0]
         row = {"name": name, "frames": Fr, "T": T, "heads": H, "dh": dh, "lds_bytes": 16 * ((T + 15) // 16 * 16 + 4) * 4,
                "workgroups": Fr * H * -(-T // 16)}
         for label, fn, flop, eg, vt, nl in (("forward", fwd, flop_f, eager_f, vit_f, null_f), ("input_gradient", bwd, flop_b, eager_b, vit_b, null_b)):
-            ms = timed(fn, a.reps)
+            ms = timed(fn, a.reps, 3)[0]
             row[label] = {"call_ms": round(ms, 4), "mfma_TFLOP/s": round(flop / ms / 1e9, 2), "flop_floor_ms": round(flop / PEAK_TFLOPS / 1e9, 4),
                           "share_of_flop_floor": round(flop / PEAK_TFLOPS / 1e9 / ms, 3), "eager_ms": round(eg, 4),
                           "eager_over_kernel": round(eg / ms, 2), "vit_attention_ms": round(vt, 4), "kernel_over_vit_attention": round(ms / vt, 2),

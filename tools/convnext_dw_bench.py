@@ -14,29 +14,12 @@ one read and one write of the tensor plus the filter (the backward's residual gr
 4.7 to 5.0 TB/s of DESIGN.md section 4.  Prints one JSON line per shape."""
 import argparse
 import json
-import os
 import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "image-to-video-i2v-attack_amd"), ROOT]
+from bench_util import timed
 SHAPES = ((96, 56), (192, 28), (384, 14), (768, 7))
 FLOOR_TBS = (4.7, 5.0)
-
-
-def timed(fn, reps):
-    import torch
-    for _ in range(3):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
 
 
 def kernels(path, frames):
@@ -80,7 +63,7 @@ def main():
         row = {"C": Cc, "plane": g, "frames": a.frames}
         for name, fn, nbytes in (("forward", lambda: eng.convnext_dw(x, w, b), 2 * tensor + filt),
                                  ("input_gradient", lambda: eng.convnext_dw(x, wm, None, res), 3 * tensor + filt)):
-            ms = timed(fn, a.reps)
+            ms = timed(fn, a.reps, 3)[0]
             gbs = nbytes / ms / 1e6
             row[name] = {"call_ms": round(ms, 4), "GB/s": round(gbs, 1), "floor_ms": [round(nbytes / t / 1e9, 4) for t in FLOOR_TBS],
                          "share_of_floor": [round(gbs / (t * 1e3), 3) for t in FLOOR_TBS]}
@@ -88,10 +71,10 @@ def main():
         xe = x.permute(0, 3, 1, 2).requires_grad_(True)
         we = w.t().reshape(Cc, 1, 7, 7).contiguous()
         assert xe.is_contiguous(memory_format=torch.channels_last)
-        row["eager_forward_ms"] = round(timed(lambda: F.conv2d(xe.detach(), we, b, padding=3, groups=Cc), a.reps), 4)
+        row["eager_forward_ms"] = round(timed(lambda: F.conv2d(xe.detach(), we, b, padding=3, groups=Cc), a.reps, 3)[0], 4)
         y = F.conv2d(xe, we, b, padding=3, groups=Cc)
         dy = res.permute(0, 3, 1, 2)
-        row["eager_input_gradient_ms"] = round(timed(lambda: torch.autograd.grad(y, xe, dy, retain_graph=True), a.reps), 4)
+        row["eager_input_gradient_ms"] = round(timed(lambda: torch.autograd.grad(y, xe, dy, retain_graph=True), a.reps, 3)[0], 4)
         print(json.dumps(row), flush=True)
 
 

@@ -14,33 +14,14 @@ the median of `reps` calls after 3 warm-up calls.  `--tiles`: the channel tiles 
 that does not fit the LDS for a shape is skipped.  Prints one JSON line per shape and tile."""
 import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "image-to-video-i2v-attack_amd"), ROOT]
+from bench_util import timed
 #: name -> (S, Sh, C): the distinct token shapes of graphs.MIXER_MODELS
 SHAPES = (("mixer_s32_224", 49, 256, 512), ("mixer_s16_224", 196, 256, 512), ("mixer_b32_224", 49, 384, 768), ("mixer_b16_224", 196, 384, 768),
           ("mixer_l32_224", 49, 512, 1024), ("mixer_l16_224", 196, 512, 1024), ("resmlp_*_224", 196, 0, 384))
 PEAK_TFLOPS = 157.3
 FLOOR_TBS = (4.7, 5.0)
 LDS = 160 * 1024
-
-
-def timed(fn, reps):
-    import torch
-    for _ in range(3):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
 
 
 def main():
@@ -83,9 +64,9 @@ def main():
                 u = w2 @ F.gelu(u) + b2[:, None]
             return r + (u if osc is None else osc * u)
         with torch.no_grad():
-            eager_f = timed(eager, a.reps)
+            eager_f = timed(eager, a.reps, 3)[0]
         y = eager()
-        eager_b = timed(lambda: torch.autograd.grad(y, zr, g, retain_graph=True), a.reps)
+        eager_b = timed(lambda: torch.autograd.grad(y, zr, g, retain_graph=True), a.reps, 3)[0]
         for tile in [int(t) for t in a.tiles.split(",")]:
             ct = tile or 32
             if (S + Sh) * ct * 4 > LDS:
@@ -101,7 +82,7 @@ def main():
             row = {"name": name, "S": S, "Sh": Sh, "C": Cn, "frames": Fr, "tile": tile, "channel_tile": ct, "lds_bytes": (S + Sh) * ct * 4,
                    "workgroups": Fr * -(-Cn // ct)}
             for label, fn, flop, nbytes, eg in (("forward", fwd, flop_f, bytes_f, eager_f), ("input_gradient", bwd, flop_b, bytes_b, eager_b)):
-                ms = timed(fn, a.reps)
+                ms = timed(fn, a.reps, 3)[0]
                 row[label] = {"call_ms": round(ms, 4), "TFLOP/s": round(flop / ms / 1e9, 2), "flop_floor_ms": round(flop / PEAK_TFLOPS / 1e9, 4),
                               "share_of_flop_floor": round(flop / PEAK_TFLOPS / 1e9 / ms, 3),
                               "byte_floor_ms": [round(nbytes / t / 1e9, 4) for t in FLOOR_TBS], "eager_ms": round(eg, 4),

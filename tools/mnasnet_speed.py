@@ -14,10 +14,10 @@ import csv
 import json
 import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "image-to-video-i2v-attack_amd"), ROOT]
+import bench_util  # noqa: F401 (puts the repository on sys.path)
+from family_speed import clips, eager_attack, time_calls
+
 ARCHS = ("mnasnet1_0", "mnasnet0_5", "mnasnet0_75", "mnasnet1_3")
 
 
@@ -32,34 +32,11 @@ def shares(path):
                       "shares": {k: {"ms": round(v[0] / 1e6, 2), "launches": v[1], "share": round(v[0] / whole, 4)} for k, v in tot.items()}}))
 
 
-def eager_attack(vid, ref, steps, lr=0.005, eps=16 / 255):
-    """image_attacks.py:294-364 (ImageGuidedFMDirection_Adam) in eager PyTorch over the restated net."""
-    import torch
-    from oracle import restate
-    b, c, f, h, w = vid.shape
-    x = vid.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w)
-    mean = torch.tensor(restate.MEAN, device=vid.device).view(1, 3, 1, 1)
-    std = torch.tensor(restate.STD, device=vid.device).view(1, 3, 1, 1)
-    u = x * std + mean
-    with torch.no_grad():
-        init = ref.features(x)[0].reshape(b * f, -1)
-    delta = torch.full_like(x, 0.01 / 255).requires_grad_(True)
-    opt = torch.optim.Adam([delta], lr=lr)
-    for _ in range(steps):
-        xn = (torch.clamp(u + torch.clamp(delta, -eps, eps), 0, 1) - mean) / std
-        cost = torch.nn.functional.cosine_similarity(ref.features(xn)[0].reshape(b * f, -1), init, dim=1, eps=1e-8).sum()
-        opt.zero_grad()
-        cost.backward()
-        opt.step()
-    return delta.detach()
-
-
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "shares":
         return shares(sys.argv[2])
     import torch
     from i2v_amd import attacks, graphs, weights
-    from oracle import restate
     from tests.mnasnet_reference import FamilyRef
     ap = argparse.ArgumentParser()
     ap.add_argument("side", choices=("engine", "eager"))
@@ -69,8 +46,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--reps", type=int, default=2)
     a = ap.parse_args()
-    u8 = torch.randint(0, 256, (a.clips, 3, 32, 224, 224), generator=torch.Generator().manual_seed(0), dtype=torch.uint8)
-    vid = (u8.float() / 255 - torch.tensor(restate.MEAN).view(1, 3, 1, 1, 1)) / torch.tensor(restate.STD).view(1, 3, 1, 1, 1)
+    vid = clips(a.clips, 32)
     if a.side == "engine":
         atk = attacks.ImageGuidedFMDirection_Adam([a.arch], depth=a.depth, step_size=0.005, steps=a.steps, weight_seed=0)
         labels, names = torch.zeros(a.clips, dtype=torch.long), [f"c{i}" for i in range(a.clips)]
@@ -80,15 +56,8 @@ def main():
         ref = FamilyRef(g, weights.synthetic_state_dict(g, 0), [g.hooks[a.depth]], torch.float32)
         ref.sd = {k: v.cuda() for k, v in ref.sd.items()}
         vd = vid.cuda()
-        call = lambda: eager_attack(vd, ref, a.steps)                                            # noqa: E731
-    times = []
-    for r in range(a.reps + 1):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        call()
-        torch.cuda.synchronize()
-        if r:
-            times.append(time.perf_counter() - t0)
+        call = lambda: eager_attack(vd, lambda t: ref.features(t)[0].reshape(t.shape[0], -1), a.steps)      # noqa: E731
+    times = time_calls(call, a.reps)
     print(json.dumps({"side": a.side, "arch": a.arch, "depth": a.depth, "clips": a.clips, "frames": 32, "steps": a.steps,
                       "seconds": [round(t, 4) for t in times], "adv_frames_per_s": round(a.clips * 32 / min(times), 2)}))
 

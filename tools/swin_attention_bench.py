@@ -14,12 +14,10 @@ The two shapes launch kernels of the same names, so only the per-dispatch trace 
 import csv
 import ctypes as C
 import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "image-to-video-i2v-attack_amd")]
+import bench_util  # noqa: F401 (puts the repository on sys.path)
 
 REPS = 5
 SHAPES = ((128, 56, 4), (128, 28, 8))           # frames, grid, heads: stage 0 and stage 1 of swin_base

@@ -15,14 +15,9 @@ counts frames x heads in one grid dimension and refuses a batch over 65 535 (her
 the profiler the same calls give the kernel times, which `stats` reads: per kernel its calls and average, the kernel against its byte
 floor, and eager's kernels summed per call."""
 import argparse
-import csv
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "image-to-video-i2v-attack_amd"), ROOT]
+from bench_util import kernel_rows, timed
 #: label -> (heads, dh): the inner attention of tnt_s and tnt_b; 16 tokens, 196 sequences a frame
 SHAPES = {"s": (4, 6), "b": (4, 10)}
 FLOOR_TBS = 4.7
@@ -33,21 +28,6 @@ def floors(frames, H, dh):
     """(forward, backward) byte floor in ms."""
     S, C = frames * 196, H * dh
     return tuple(S * 16 * C * n * 4 / (FLOOR_TBS * 1e12) * 1e3 for n in (4, 7))
-
-
-def timed(fn, reps):
-    import torch
-    for _ in range(WARM):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
 
 
 def one(label, frames, reps):
@@ -73,8 +53,8 @@ def one(label, frames, reps):
              "dv": rel(split(dqkv, 2), gv)}
     assert max(agree.values()) < 1e-4, agree
     with torch.no_grad():
-        eager_f = timed(core, reps)
-    eager_b = timed(lambda: torch.autograd.grad(y, (q, k, v), g, retain_graph=True), reps)
+        eager_f = timed(core, reps, WARM)
+    eager_b = timed(lambda: torch.autograd.grad(y, (q, k, v), g, retain_graph=True), reps, WARM)
     row = {"shape": label, "frames": frames, "sequences": S, "T": T, "heads": H, "dh": dh, "sequences_per_workgroup": eng.tnt_attention_group(T, H, dh),
            "eager_agrees_to": agree}
     P = lambda t: t.data_ptr()      # noqa: E731
@@ -82,7 +62,7 @@ def one(label, frames, reps):
     ff, fb = floors(frames, H, dh)
     for name, fn, bfl, eg in (("forward", lambda: capi.i2v_tnt_attention_f32(P(qkv), S, T, H, dh, scale, P(out), st), ff, eager_f),
                               ("input_gradient", lambda: capi.i2v_tnt_attention_bwd_f32(P(qkv), P(dout), S, T, H, dh, scale, P(dqkv), st), fb, eager_b)):
-        ms, lo, hi = timed(fn, reps)
+        ms, lo, hi = timed(fn, reps, WARM)
         row[name] = {"call_ms": round(ms, 4), "fastest_slowest_ms": [round(lo, 4), round(hi, 4)], "byte_floor_ms": round(bfl, 4),
                      "share_of_floor": round(bfl / ms, 3), "eager_ms": round(eg[0], 4), "eager_fastest_slowest_ms": [round(eg[1], 4), round(eg[2], 4)],
                      "eager_over_kernel": round(eg[0] / ms, 2)}
@@ -92,11 +72,7 @@ def one(label, frames, reps):
 def stats(path, frames, reps):
     """The profiler's kernel stats of one `run --shape all`: the two TNT kernels per head width, and everything else (eager's kernels and
     the input generators) summed per timed call."""
-    if path.endswith(".db"):       # the profiler's database (its default output): the `kernels` view, one row per dispatch
-        import sqlite3
-        rows = sqlite3.connect(path).execute("select name, count(*), sum(duration) from kernels group by name").fetchall()
-    else:                          # ... or its kernel stats csv (--output-format csv)
-        rows = [(r["Name"], int(r["Calls"]), float(r["TotalDurationNs"])) for r in csv.DictReader(open(path))]
+    rows = kernel_rows(path)
     ours, rest = {}, 0.0
     for name, calls, total in rows:
         if "tnt_attn" in name:

@@ -19,32 +19,15 @@ import argparse
 import ctypes as C
 import json
 import os
-import statistics
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "image-to-video-i2v-attack_amd"), ROOT]
+from bench_util import timed
 #: label -> (Tq, Tk, H, dh): stages 0 .. 3 of the three PCPVT models (head width 64) and of twins_svt_small (head width 32)
 SHAPES = {"pcpvt0": (3136, 49, 1, 64), "pcpvt1": (784, 49, 2, 64), "pcpvt2": (196, 49, 5, 64), "pcpvt3": (49, 49, 8, 64),
           "svt0": (3136, 49, 2, 32), "svt1": (784, 49, 4, 32), "svt2": (196, 49, 8, 32), "svt3": (49, 49, 16, 32)}
 FLOOR_TBS, FLOOR_TFLOPS = 4.7, 157.3
 CHILD_SECONDS = 150
-
-
-def timed(fn, reps):
-    import torch
-    for _ in range(5):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
 
 
 def one(label, Fr, reps):
@@ -101,16 +84,16 @@ def one(label, Fr, reps):
     assert max(agree.values()) < 1e-5, agree                               # the two sides compute the same thing
     qr, kr = q.clone().requires_grad_(True), kv.clone().requires_grad_(True)
     with torch.no_grad():
-        eager_f = timed(lambda: gsa_core(qr, kr, H), reps)
+        eager_f = timed(lambda: gsa_core(qr, kr, H), reps, 5)
     y = gsa_core(qr, kr, H)
-    eager_b = timed(lambda: torch.autograd.grad(y, (qr, kr), dout, retain_graph=True), reps)
+    eager_b = timed(lambda: torch.autograd.grad(y, (qr, kr), dout, retain_graph=True), reps, 5)
     del y
     row = {"shape": label, "frames": Fr, "Tq": Tq, "Tk": Tk, "heads": H, "dh": dh, "composition_agrees_to": agree}
     prod = Fr * H * Tq * Tk * dh
     for name, fn, comp, floats, flop, eg in (("forward", fwd, comp_fwd, Fr * (2 * tok + key), 4 * prod, eager_f),
                                              ("input_gradient", bwd, comp_bwd, Fr * (3 * tok + 2 * key), 10 * prod, eager_b)):
-        ms, lo, hi = timed(fn, reps)
-        cms, clo, chi = timed(comp, reps)
+        ms, lo, hi = timed(fn, reps, 5)
+        cms, clo, chi = timed(comp, reps, 5)
         bfl, afl = floats * 4 / (FLOOR_TBS * 1e12) * 1e3, flop / (FLOOR_TFLOPS * 1e12) * 1e3
         row[name] = {"call_ms": round(ms, 4), "fastest_slowest_ms": [round(lo, 4), round(hi, 4)], "byte_floor_ms": round(bfl, 4),
                      "arithmetic_floor_ms": round(afl, 4), "bound_by": "bytes" if bfl >= afl else "arithmetic",

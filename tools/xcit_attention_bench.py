@@ -15,31 +15,14 @@ calls after 3 warm-up calls.  Prints one JSON line per shape."""
 import argparse
 import json
 import os
-import statistics
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "image-to-video-i2v-attack_amd"), ROOT]
+from bench_util import timed
 #: label -> (T, H, dh): tiny (nano has dh 32), small, medium, large
 SHAPES = {"tiny": (196, 4, 48), "small": (196, 8, 48), "medium": (196, 8, 64), "large": (196, 16, 48)}
 FLOOR_TBS = 4.7
 CHILD_SECONDS = 120
-
-
-def timed(fn, reps):
-    import torch
-    for _ in range(3):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
 
 
 def one(label, Fr, reps):
@@ -65,14 +48,14 @@ def one(label, Fr, reps):
         _lib.check(capi, capi.i2v_xcit_attention_bwd_f32(P(qkv), P(gram), P(probs), P(dout), Fr, T, H, dh, P(temp), P(dqkv), st))
     qr = qkv.clone().requires_grad_(True)
     with torch.no_grad():
-        eager_f = timed(lambda: xca_core(qr, H, temp), reps)
+        eager_f = timed(lambda: xca_core(qr, H, temp), reps, 3)[0]
     y, _ = xca_core(qr, H, temp)
-    eager_b = timed(lambda: torch.autograd.grad(y, qr, dout, retain_graph=True), reps)
+    eager_b = timed(lambda: torch.autograd.grad(y, qr, dout, retain_graph=True), reps, 3)[0]
     del y
     row = {"shape": label, "frames": Fr, "T": T, "heads": H, "dh": dh, "workgroups": Fr * H}
     for name, fn, floats, flop, eg in (("forward", fwd, 4 * Fr * T * C, 4 * Fr * H * T * dh * dh, eager_f),
                                        ("input_gradient", bwd, 7 * Fr * T * C, 8 * Fr * H * T * dh * dh, eager_b)):
-        ms = timed(fn, reps)
+        ms = timed(fn, reps, 3)[0]
         floor = floats * 4 / (FLOOR_TBS * 1e12) * 1e3
         row[name] = {"call_ms": round(ms, 4), "byte_floor_ms": round(floor, 4), "share_of_byte_floor": round(floor / ms, 3),
                      "algorithmic_TB/s": round(floats * 4 / ms / 1e9, 3), "mfma_TFLOP/s": round(flop / ms / 1e9, 2), "eager_ms": round(eg, 4),
