@@ -504,6 +504,7 @@ extern "C" size_t i2v_net_workspace_bytes(i2v_handle h, int net) {
 #include "i2v_tune.cpp"
 #include "i2v_run.cpp"
 #include "i2v_loop_api.cpp"
+#include "i2v_conv_aux_api.cpp" // (the grouped / depthwise packers and the squeeze-and-excitation node on their own, include/i2v_conv_aux_launch.h)
 // ... and the ConvNeXt planner on the scalar restatements of the transformer launches it uses (i2v_xf_host.h), so that the planner
 // tests can run it without a GPU.  i2v_xf.h's file-local `fail` would be ambiguous with eng::fail under this unit's using-directives.
 #define fail xf_fail

@@ -1,5 +1,6 @@
 // Weight packing: every convolution's operands as the kernels read them (see the file header of i2v_engine.cpp).
 #include "i2v_net.h"
+#include "i2v_conv_aux.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -191,33 +192,11 @@ bool gconv_enabled() {
 int pack_gconv(Net& n, Node& nd) {
     const i2v_conv3d_desc& c = nd.cd;
     const int G = nd.groups, gw = c.cin / G, st = c.stride;
-    std::vector<float> wf((size_t)G * gw * 9 * gw);
-    for (int g = 0; g < G; ++g)
-        for (int co = 0; co < gw; ++co)
-            for (int ci = 0; ci < gw; ++ci)
-                for (int t = 0; t < 9; ++t)
-                    wf[(((size_t)g * gw + ci) * 9 + t) * gw + co] = nd.wg[(((size_t)(g * gw + co)) * gw + ci) * 9 + t];
+    std::vector<float> wf(conv_aux::gconv_fwd_floats(G, gw));
+    conv_aux::gconv_pack_fwd(nd.wg.data(), G, gw, wf.data());
     if (upload(n, wf, &nd.gw_fwd)) return 1;
-    std::vector<float> wb((size_t)st * st * G * gw * 9 * gw, 0.f);
-    for (int ph = 0; ph < st; ++ph)
-        for (int pw = 0; pw < st; ++pw) {
-            const int cls = ph * st + pw;
-            int mask = 0;
-            for (int r = 0; r < 3; ++r) {
-                if (posmod(ph + 1 - r, st)) continue;
-                const int a = floordiv(ph + 1 - r, st) + 1;
-                for (int s = 0; s < 3; ++s) {
-                    if (posmod(pw + 1 - s, st)) continue;
-                    const int b = floordiv(pw + 1 - s, st) + 1;
-                    mask |= 1 << (3 * a + b);
-                    for (int g = 0; g < G; ++g)
-                        for (int co = 0; co < gw; ++co)
-                            for (int ci = 0; ci < gw; ++ci)
-                                wb[((((size_t)cls * G + g) * gw + co) * 9 + 3 * a + b) * gw + ci] = nd.wg[(((size_t)(g * gw + co)) * gw + ci) * 9 + 3 * r + s];
-                }
-            }
-            nd.gw_tapmask[cls] = mask;
-        }
+    std::vector<float> wb(conv_aux::gconv_bwd_floats(G, gw, st));
+    conv_aux::gconv_pack_bwd(nd.wg.data(), G, gw, st, wb.data(), nd.gw_tapmask);
     return upload(n, wb, &nd.gw_bwd);
 }
 
@@ -237,25 +216,9 @@ bool dwconv_enabled() {
 // owns (b alike): the mirrored filter, zeros in the slots the class does not own; gw_tapmask has a bit per owned slot.
 int pack_dwconv(Net& n, Node& nd) {
     const i2v_conv3d_desc& c = nd.cd;
-    const int C = c.cin, k = c.kh, pad = c.pad, st = c.stride, nt = k * k;
     if (upload(n, nd.wg, &nd.gw_fwd)) return 1;
-    std::vector<float> wb((size_t)st * st * C * nt, 0.f);
-    for (int ph = 0; ph < st; ++ph)
-        for (int pw = 0; pw < st; ++pw) {
-            const int cls = ph * st + pw;
-            int mask = 0;
-            for (int r = 0; r < k; ++r) {
-                if (posmod(ph + pad - r, st)) continue;
-                const int a = floordiv(ph + pad - r, st) + pad;
-                for (int s = 0; s < k; ++s) {
-                    if (posmod(pw + pad - s, st)) continue;
-                    const int b = floordiv(pw + pad - s, st) + pad;
-                    mask |= 1 << (k * a + b);
-                    for (int ch = 0; ch < C; ++ch) wb[((size_t)cls * C + ch) * nt + k * a + b] = nd.wg[(size_t)ch * nt + k * r + s];
-                }
-            }
-            nd.gw_tapmask[cls] = mask;
-        }
+    std::vector<float> wb(conv_aux::dwconv_bwd_floats(c.cin, c.kh, c.stride));
+    conv_aux::dwconv_pack_bwd(nd.wg.data(), c.cin, c.kh, c.stride, wb.data(), nd.gw_tapmask);
     return upload(n, wb, &nd.gw_bwd);
 }
 

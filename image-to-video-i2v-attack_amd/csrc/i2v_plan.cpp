@@ -1,5 +1,6 @@
 // The planner: a net's nodes as a forward and an input-gradient launch list (see the file header of i2v_engine.cpp).
 #include "i2v_net.h"
+#include "i2v_conv_aux.h"
 #ifndef I2V_HAVE_SE
 #include "i2v_se_host.h"
 #endif
@@ -158,18 +159,13 @@ struct Planner {
         q.src = s.p; q.src_nstride = s.nstride; q.Hs = s.H; q.Ws = s.W;
         q.groups = nd.groups; q.gw = gw;
         q.dst = d.p; q.dst_nstride = d.nstride; q.Ho = d.H; q.Wo = d.W;
+        conv_aux::conv_classes(q, backward, st, 9, nd.gw_tapmask);
         if (!backward) {
-            q.w = nd.gw_fwd; q.S = st; q.os = 1; q.ncls = 1;
-            q.cls[0].Hg = d.H; q.cls[0].Wg = d.W; q.cls[0].tapmask = 0x1FF;
+            q.w = nd.gw_fwd;
             q.shift = nd.shift_d; q.relu = c.relu;
             if (c.relu) { int gs = 0; if (uint32_t* g = gate_rows(c.dst, &gs)) { q.gate_out = g; q.gate_out_stride = gs; } }
         } else {
-            q.w = nd.gw_bwd; q.S = 1; q.os = st; q.ncls = st * st;
-            for (int ph = 0; ph < st; ++ph)
-                for (int pw = 0; pw < st; ++pw) {
-                    I2VGConvClass& k = q.cls[ph * st + pw];
-                    k.Hg = (d.H - ph + st - 1) / st; k.Wg = (d.W - pw + st - 1) / st; k.oh0 = ph; k.ow0 = pw; k.tapmask = nd.gw_tapmask[ph * st + pw];
-                }
+            q.w = nd.gw_bwd;
             if (n.tens[t].post_relu) {
                 int gs = 0;
                 if (uint32_t* g = gate_rows(t, &gs)) { q.gate = g; q.gate_stride = gs; }
@@ -206,18 +202,13 @@ struct Planner {
         q.src = s.p; q.src_nstride = s.nstride; q.Hs = s.H; q.Ws = s.W;
         q.C = c.cin; q.k = k;
         q.dst = d.p; q.dst_nstride = d.nstride; q.Ho = d.H; q.Wo = d.W;
+        conv_aux::conv_classes(q, backward, st, k * k, nd.gw_tapmask);
         if (!backward) {
-            q.w = nd.gw_fwd; q.S = st; q.os = 1; q.ncls = 1;
-            q.cls[0].Hg = d.H; q.cls[0].Wg = d.W; q.cls[0].tapmask = (1 << (k * k)) - 1;
+            q.w = nd.gw_fwd;
             q.shift = nd.shift_d; q.relu = c.relu;
             if (c.relu) { int gs = 0; if (uint32_t* g = gate_rows(c.dst, &gs)) { q.gate_out = g; q.gate_out_stride = gs; } }
         } else {
-            q.w = nd.gw_bwd; q.S = 1; q.os = st; q.ncls = st * st;
-            for (int ph = 0; ph < st; ++ph)
-                for (int pw = 0; pw < st; ++pw) {
-                    I2VDwConvClass& kc = q.cls[ph * st + pw];
-                    kc.Hg = (d.H - ph + st - 1) / st; kc.Wg = (d.W - pw + st - 1) / st; kc.oh0 = ph; kc.ow0 = pw; kc.tapmask = nd.gw_tapmask[ph * st + pw];
-                }
+            q.w = nd.gw_bwd;
             if (n.tens[t].post_relu) {
                 int gs = 0;
                 if (uint32_t* g = gate_rows(t, &gs)) { q.gate = g; q.gate_stride = gs; }

@@ -397,6 +397,36 @@ _NL_PROTOS = {
 NL_EXPORTS = tuple(_NL_PROTOS)
 
 
+class ConvAuxDesc(C.Structure):
+    _fields_ = ([("src", _P), ("src_nstride", _L), ("dst", _P), ("dst_nstride", _L), ("plan_src", _P), ("filter", _P), ("shift", _P),
+                 ("gate_out", _P), ("gate", _P), ("mask", _P), ("mask_nstride", _L), ("gate_out_stride", C.c_int32), ("gate_stride", C.c_int32)]
+                + [(n, C.c_int32) for n in ("N", "C", "H", "W", "stride", "backward", "relu", "groups", "k")])
+
+
+class ConvAuxPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("waves", "rows", "pitch", "lds_bytes", "v4")]
+
+
+class SeLaunchDesc(C.Structure):
+    _fields_ = ([("x", _P), ("x_nstride", _L), ("g", _P), ("g_nstride", _L), ("r", _P), ("r_nstride", _L), ("dst", _P), ("dst_nstride", _L)]
+                + [(n, _P) for n in ("w1", "b1", "w2", "b2", "m", "h", "s", "t", "dmh")] + [("gate_out", _P), ("gate_out_stride", C.c_int32)]
+                + [(n, C.c_int32) for n in ("N", "C", "rd", "HW", "relu", "backward", "launches")])
+
+
+# The grouped, depthwise and squeeze-and-excitation launches on their own (`include/i2v_conv_aux_launch.h`): a header of its own, kept
+# apart from EXPORTS.  The host simulation exports CONV_AUX_HOST_PROTOS: the packers and the node's scalar twin; the two convolution
+# kernels are the device library's alone.
+_CONV_AUX_PROTOS = {
+    "i2v_gconv_f32": ([C.POINTER(ConvAuxDesc), C.POINTER(ConvAuxPlan), _P], _I),
+    "i2v_dwconv_f32": ([C.POINTER(ConvAuxDesc), C.POINTER(ConvAuxPlan), _P], _I),
+    "i2v_gconv_pack_f32": ([_P, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    "i2v_dwconv_pack_f32": ([_P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "i2v_se_f32": ([C.POINTER(SeLaunchDesc), _P], _I),
+}
+CONV_AUX_EXPORTS = tuple(_CONV_AUX_PROTOS)
+CONV_AUX_HOST_PROTOS = {k: v for k, v in _CONV_AUX_PROTOS.items() if k not in ("i2v_gconv_f32", "i2v_dwconv_f32")}
+
+
 # The transformer families by the word in their entry names (`i2v_<word>_*`)
 FAMILY_PROTOS = {"vit": _VIT_PROTOS, "swin": _SWIN_PROTOS, "convnext": _CONVNEXT_PROTOS, "mixer": _MIXER_PROTOS, "cait": _CAIT_PROTOS,
                  "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS, "pit": _PIT_PROTOS, "coat": _COAT_PROTOS,
@@ -431,7 +461,7 @@ def load():
         lib = bind(C.CDLL(path))
         if lib.i2v_backend() != HIP_BACKEND:
             raise I2VError(f"{path} reports backend {lib.i2v_backend()!r}, expected {HIP_BACKEND!r}")
-        for protos in (_LOADER_PROTOS, *FAMILY_PROTOS.values(), _XF_PROTOS, _NL_PROTOS):
+        for protos in (_LOADER_PROTOS, *FAMILY_PROTOS.values(), _XF_PROTOS, _NL_PROTOS, _CONV_AUX_PROTOS):
             bind(lib, protos)
         _lib = lib
     return _lib

@@ -9,9 +9,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "hostsim", "libi2v_hostsim.so")
 CSRC = os.path.join(HERE, "..", "image-to-video-i2v-attack_amd", "csrc")
 SRCS = [os.path.join(HERE, "hostsim", "hostsim_backend.cpp")] + [
-        os.path.join(CSRC, f) for f in ("i2v_engine.cpp", "i2v_pack.cpp", "i2v_plan.cpp", "i2v_tune.cpp", "i2v_run.cpp", "i2v_loop_api.cpp",
+        os.path.join(CSRC, f) for f in ("i2v_engine.cpp", "i2v_pack.cpp", "i2v_plan.cpp", "i2v_tune.cpp", "i2v_run.cpp", "i2v_loop_api.cpp", "i2v_conv_aux_api.cpp", "i2v_conv_aux.h",
                                         "i2v_net.h", "i2v_params.h", "i2v_kernels.h")] + [
-        os.path.join(HERE, "..", "include", h) for h in ("i2v_hip.h", "i2v_nl_launch.h")]
+        os.path.join(HERE, "..", "include", h) for h in ("i2v_hip.h", "i2v_nl_launch.h", "i2v_conv_aux_launch.h")]
 _engine = None
 
 
