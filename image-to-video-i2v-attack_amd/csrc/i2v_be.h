@@ -23,7 +23,7 @@ extern thread_local bool g_be_has_err;
 int hip_fail(hipError_t e, const char* what);
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_, #x); } while (0)
 #define LAUNCH_CHECK(name) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return hip_fail(e_, name); } while (0)
-extern long long g_stat_conv, g_stat_pws, g_stat_bf3, g_stat_igh, g_stat_sth, g_stat_fastblock, g_stat_vfma, g_stat_igv, g_stat_gconv, g_stat_dwconv, g_stat_se, g_stat_cndw, g_stat_mixtok, g_stat_scpair, g_stat_cait, g_stat_convit, g_stat_xcit, g_stat_twins, g_stat_beit, g_stat_pit, g_stat_coat, g_stat_tnt;      // (relaxed counters: diagnostics only)
+extern long long g_stat_conv, g_stat_pws, g_stat_bf3, g_stat_igh, g_stat_sth, g_stat_fastblock, g_stat_vfma, g_stat_igv, g_stat_gconv, g_stat_dwconv, g_stat_se, g_stat_cndw, g_stat_mixtok, g_stat_scpair, g_stat_cait, g_stat_convit, g_stat_xcit, g_stat_twins, g_stat_beit, g_stat_pit, g_stat_coat, g_stat_tnt, g_stat_quality;      // (relaxed counters: diagnostics only)
 
 // n / d for 0 <= n < 2^31 with the precomputed (m, s) of fastdiv_magic: exact
 __device__ __forceinline__ unsigned fastdiv(unsigned n, unsigned m, unsigned s) {

@@ -519,5 +519,6 @@ extern "C" size_t i2v_net_workspace_bytes(i2v_handle h, int net) {
 #include "i2v_coat.cpp"         // (... and the CoaT planner, on the same restatements and i2v_coat_host.h)
 #include "i2v_tnt.cpp"          // (... and the TNT planner, on the same restatements, i2v_beit_host.h and i2v_tnt_host.h)
 #include "i2v_xf_api.cpp"       // (... and the restatements on their own, include/i2v_xf_launch.h)
+#include "i2v_quality.cpp"      // (... and the 8-bit export and the quality launches as scalar code, i2v_quality_host.h)
 #undef fail
 #endif

@@ -43,6 +43,7 @@ long long be_stat(const char* name) {
     if (!strcmp(name, "pit_attention_launches")) return __atomic_load_n(&g_stat_pit, __ATOMIC_RELAXED);
     if (!strcmp(name, "coat_attention_launches")) return __atomic_load_n(&g_stat_coat, __ATOMIC_RELAXED);
     if (!strcmp(name, "tnt_attention_launches")) return __atomic_load_n(&g_stat_tnt, __ATOMIC_RELAXED);
+    if (!strcmp(name, "quality_launches")) return __atomic_load_n(&g_stat_quality, __ATOMIC_RELAXED);
     if (!strcmp(name, "scpair_launches")) return __atomic_load_n(&g_stat_scpair, __ATOMIC_RELAXED);
 #ifdef I2V_EXPERIMENTAL      // 1: the library carries the experimental kernels (fused pair, split-bf16 loop, conv_pw_stream, conv_stem64_halo)
     if (!strcmp(name, "experimental")) return 1;

@@ -510,6 +510,63 @@ class Engine:
         _lib.check(self.capi, self.capi.i2v_clip_from_u8_f32(C.c_void_p(frames_u8.data_ptr()), _ptr(out, self), b, t, h, w, self.stream()))
         return out
 
+    def _quality_api(self):
+        """The entries of `include/i2v_quality.h` with their prototypes: `lib.load()` binds them on the product library; an injected
+        library (the host simulation) gets them on first use."""
+        if not getattr(self, "_quality_bound", False):
+            _lib.bind(self.capi, _lib._QUALITY_PROTOS)
+            self._quality_bound = True
+        return self.capi
+
+    def clip_to_u8(self, video: torch.Tensor, ref: torch.Tensor = None, levels: int = None) -> torch.Tensor:
+        """The way back (`i2v_clip_to_u8`): normalised (b,3,t,h,w) float32 clip -> (b,t,h,w,3) uint8 frames, rounded to the nearest level,
+        half to even.  With `ref` (the clean clip's frames, same shape) and `levels` the result is also clamped to ref +- levels."""
+        assert video.dtype == torch.float32 and video.dim() == 5 and video.shape[1] == 3, (video.dtype, tuple(video.shape))
+        b, _, t, h, w = video.shape
+        out = torch.empty(b, t, h, w, 3, dtype=torch.uint8, device=video.device)
+        if (ref is None) != (levels is None):
+            raise _lib.I2VError("clip_to_u8: `ref` and `levels` go together")
+        if ref is not None and (ref.dtype != torch.uint8 or tuple(ref.shape) != tuple(out.shape) or ref.device != video.device or not ref.is_contiguous()):
+            raise _lib.I2VError(f"clip_to_u8: ref must be contiguous uint8 {tuple(out.shape)} on {video.device}")
+        _lib.check(self.capi, self._quality_api().i2v_clip_to_u8(_ptr(video, self), C.c_void_p(ref.data_ptr()) if ref is not None else None,
+                                                       -1 if levels is None else int(levels), C.c_void_p(out.data_ptr()), b, t, h, w, self.stream()))
+        return out
+
+    def clip_quality_tile(self):
+        """(rows, columns) of valid SSIM positions one tile of the quality launch covers (`i2v_clip_quality_tile`)."""
+        r, c = C.c_int(), C.c_int()
+        self._quality_api().i2v_clip_quality_tile(C.byref(r), C.byref(c))
+        return r.value, c.value
+
+    def clip_quality(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """Per frame (SSE in level^2 over 3 h w, max |a - b| in levels, mean SSIM) of two clips on the device, as a float64 (frames, 3)
+        tensor: both uint8 (frames..., h, w, 3) -- any leading dimensions -- or both float32 normalised (clips, 3, t, h, w), frame
+        clip * t + f (`i2v_clip_quality_u8` / `_f32`).  Nothing synchronises; mixed dtypes or shapes are refused."""
+        if a.dtype != b.dtype or tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+            raise _lib.I2VError(f"clip_quality: operands differ: {a.dtype} {tuple(a.shape)} on {a.device} against {b.dtype} {tuple(b.shape)} on {b.device}")
+        if a.device.type != self.device.type or not (a.is_contiguous() and b.is_contiguous()):
+            raise _lib.I2VError(f"clip_quality: contiguous tensors on {self.device} needed")
+        if a.dtype == torch.uint8 and a.dim() >= 4 and a.shape[-1] == 3:
+            h, w = a.shape[-3:-1]
+            frames, t = a.numel() // (3 * h * w), 0
+        elif a.dtype == torch.float32 and a.dim() == 5 and a.shape[1] == 3:
+            clips, _, t, h, w = a.shape
+            frames = clips * t
+        else:
+            raise _lib.I2VError(f"clip_quality: uint8 (..., h, w, 3) frames or float32 (clips, 3, t, h, w) clips, not {a.dtype} {tuple(a.shape)}")
+        out = torch.empty(max(frames, 1), 3, dtype=torch.float64, device=a.device)
+        nbytes = int(self._quality_api().i2v_clip_quality_scratch_bytes(frames, h, w))
+        scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=a.device)
+        pa, pb, po, ps = (C.c_void_p(x.data_ptr()) for x in (a, b, out, scratch))
+        if t == 0:
+            rc = self.capi.i2v_clip_quality_u8(pa, pb, po, frames, h, w, ps, nbytes, self.stream())
+        else:
+            rc = self.capi.i2v_clip_quality_f32(pa, pb, po, clips, t, h, w, ps, nbytes, self.stream())
+        _lib.check(self.capi, rc)
+        if a.device.type == "cuda":          # the scratch goes back to the caching allocator: it must not be handed out to another stream early
+            scratch.record_stream(torch.cuda.current_stream(a.device))
+        return out[:frames]
+
     def clip_resize_crop(self, frames_u8: torch.Tensor, short_side=256, crop=224) -> torch.Tensor:
         """(b,t,H,W,3) uint8 decoded frames on the device -> the reference's validation transform (datasets.py:86-93:
         resize the short side to `short_side` with cv2-style 8-bit bilinear, centre-crop `crop`, /255, normalise) ->

@@ -427,6 +427,18 @@ CONV_AUX_EXPORTS = tuple(_CONV_AUX_PROTOS)
 CONV_AUX_HOST_PROTOS = {k: v for k, v in _CONV_AUX_PROTOS.items() if k not in ("i2v_gconv_f32", "i2v_dwconv_f32")}
 
 
+# The 8-bit export and the per-frame quality figures (`include/i2v_quality.h`): a header of its own, kept apart from EXPORTS.  Every build
+# exports them: the host simulation runs their scalar twins.
+_QUALITY_PROTOS = {
+    "i2v_clip_to_u8": ([_P, _P, _I, _P, _I, _I, _I, _I, _P], _I),
+    "i2v_clip_quality_scratch_bytes": ([_L, _I, _I], C.c_size_t),
+    "i2v_clip_quality_tile": ([C.POINTER(_I), C.POINTER(_I)], None),
+    "i2v_clip_quality_u8": ([_P, _P, _P, _L, _I, _I, _P, _L, _P], _I),
+    "i2v_clip_quality_f32": ([_P, _P, _P, _I, _I, _I, _I, _P, _L, _P], _I),
+}
+QUALITY_EXPORTS = tuple(_QUALITY_PROTOS)
+
+
 # The transformer families by the word in their entry names (`i2v_<word>_*`)
 FAMILY_PROTOS = {"vit": _VIT_PROTOS, "swin": _SWIN_PROTOS, "convnext": _CONVNEXT_PROTOS, "mixer": _MIXER_PROTOS, "cait": _CAIT_PROTOS,
                  "convit": _CONVIT_PROTOS, "xcit": _XCIT_PROTOS, "twins": _TWINS_PROTOS, "beit": _BEIT_PROTOS, "pit": _PIT_PROTOS, "coat": _COAT_PROTOS,
@@ -461,7 +473,7 @@ def load():
         lib = bind(C.CDLL(path))
         if lib.i2v_backend() != HIP_BACKEND:
             raise I2VError(f"{path} reports backend {lib.i2v_backend()!r}, expected {HIP_BACKEND!r}")
-        for protos in (_LOADER_PROTOS, *FAMILY_PROTOS.values(), _XF_PROTOS, _NL_PROTOS, _CONV_AUX_PROTOS):
+        for protos in (_LOADER_PROTOS, *FAMILY_PROTOS.values(), _XF_PROTOS, _NL_PROTOS, _CONV_AUX_PROTOS, _QUALITY_PROTOS):
             bind(lib, protos)
         _lib = lib
     return _lib

@@ -73,6 +73,12 @@ def arg_parse(argv=None, ucf101=False):
     parser.add_argument("--synthetic_weights", action="store_true",
                         help="run on the seeded synthetic initialiser when no checkpoint lies under $I2V_WEIGHTS_DIR "
                              "(same as I2V_SYNTHETIC_WEIGHTS=1); without it a missing checkpoint is an error")
+    parser.add_argument("--quality", action="store_true",
+                        help="also write quality_info_{batch_index}.json: per clip PSNR (dB), SSIM and L-infinity (levels) of the adversarial "
+                             "clip against its clean clip, measured on the device (Engine.clip_quality)")
+    parser.add_argument("--export_u8", action="store_true",
+                        help="also write <adv_path>/u8/{label}-adv.npy: the adversarial clip as uint8 (t,h,w,3) frames, rounded to the 8-bit "
+                             "grid and held within floor(255 epsilon) levels of the clean frames (Engine.clip_to_u8)")
     args = parser.parse_args(argv)
     if not ucf101:
         check_video_flags(parser, args)
@@ -156,6 +162,44 @@ def build_attack(args, ucf101=False):
     return getattr(image_attacks, args.attack_method)          # AttributeError, as in the reference
 
 
+def measure_and_export(args, attack_method, adv, clean):
+    """On the engine's device and the current stream: the per-frame figures of the float adversarial batch against its clean batch
+    (`--quality`), the batch as 8-bit frames within the budget of the clean frames (`--export_u8`), and with both the figures of those
+    frames against the clean frames.  Tensors, still on the device: `float` (b t, 3), `frames` (b, t, h, w, 3), `u8` (b t, 3)."""
+    from i2v_amd import attacks as _attacks
+    from i2v_amd import quality as _quality
+    eng = _attacks.get_engine()
+    adv = adv.contiguous()
+    clean = clean.to(adv.device, non_blocking=True).contiguous()
+    out = {}
+    if args.quality:
+        out["float"] = eng.clip_quality(adv, clean)
+    if args.export_u8:
+        ref = eng.clip_to_u8(clean)
+        out["frames"] = eng.clip_to_u8(adv, ref, _quality.epsilon_levels(float(getattr(attack_method, "epsilon", 16 / 255))))
+        if args.quality:
+            out["u8"] = eng.clip_quality(out["frames"], ref)
+    return out
+
+
+def write_extra(args, labels, extra, quality_info):
+    """The writer thread's share: `u8/{label}-adv.npy` and the clips' records of `quality_info_{batch_index}.json`."""
+    from i2v_amd import quality as _quality
+    if "frames" in extra:
+        os.makedirs(os.path.join(args.adv_path, "u8"), exist_ok=True)
+        for ind, label in enumerate(labels):
+            np.save(os.path.join(args.adv_path, "u8", "{}-adv".format(label.item())), extra["frames"][ind].numpy())
+    if "float" in extra:
+        b = len(labels)
+        t = extra["float"].shape[0] // b
+        records = _quality.summarise(extra["float"], t, args.hw, args.hw)
+        if "u8" in extra:
+            for rec, u8 in zip(records, _quality.summarise(extra["u8"], t, args.hw, args.hw)):
+                rec["u8"] = u8
+        for label, rec in zip(labels, records):
+            quality_info[str(label.item())] = rec
+
+
 def main(argv=None, ucf101=False):
     """`ucf101`: the behaviour of the reference's `image_main_ucf101.py` (drop-in module of that name): --step defaults to 10, the
     ensemble class receives it, names are `str(val_label)` (:83), and decoded uint8 clips go through the UCF-101 loader's transform
@@ -176,7 +220,8 @@ def main(argv=None, ucf101=False):
         pinned = affinity.pin_rank(args.batch_index - 1, args.batch_nums) if 1 <= args.batch_index <= args.batch_nums else None
     if pinned:
         print("cpu affinity:", pinned)
-    print(args)
+    # (the flags added behind the reference's are shown only when given: without them not a byte of the output changes)
+    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in ("quality", "export_u8") or v}))
     frame_dir = getattr(args, "frame_dir", "")
     if frame_dir:        # UCF-101 jpg frame folders: clip list + LoopPadding(32) + Pillow decoding on the host, transform on the device
         used = args.used_idxs or None
@@ -245,15 +290,18 @@ def main(argv=None, ucf101=False):
             if failed:
                 continue                     # keep draining so that the main loop's done.put() never blocks
             try:
-                labels, host, event = item
+                labels, host, event, extra = item
                 if event is not None:
                     event.synchronize()
                 for ind, label in enumerate(labels):
                     np.save(os.path.join(args.adv_path, "{}-adv".format(label.item())), host[ind].numpy())
+                if extra is not None:
+                    write_extra(args, labels, extra, quality_info)
             except BaseException as e:       # disk full, unwritable directory: end the run with that error
                 writer_error.append(e)
                 failed = True
 
+    quality_info = {}                       # label -> {psnr_db, ssim, linf_levels[, u8]}, filled by the writer thread (--quality)
     threads = [threading.Thread(target=reader, daemon=True), threading.Thread(target=writer, daemon=True)]
     for t in threads:
         t.start()
@@ -303,18 +351,22 @@ def main(argv=None, ucf101=False):
             outs = attack_method.forward_grouped(batches)
         else:
             outs = [attack_method(*bt) for bt in batches]
-        for (_, val_label, _), adv_batches in zip(batches, outs):
+        for (clean_batch, val_label, _), adv_batches in zip(batches, outs):
             if isinstance(adv_batches, tuple):                             # AENS returns (adv, time, costs)
                 adv_batches = adv_batches[0]
             adv_batches = adv_batches.detach()
+            # --quality / --export_u8: measured and quantised on the device, on this stream, before the copy to the host
+            extra = measure_and_export(args, attack_method, adv_batches, clean_batch) if args.quality or args.export_u8 else None
             if adv_batches.is_cuda:
                 host = torch.empty(adv_batches.shape, dtype=adv_batches.dtype, pin_memory=True)
                 host.copy_(adv_batches, non_blocking=True)
+                if extra is not None:
+                    extra = {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True).copy_(v, non_blocking=True) for k, v in extra.items()}
                 event = torch.cuda.Event()
                 event.record(torch.cuda.current_stream(adv_batches.device))
             else:
                 host, event = adv_batches.contiguous(), None
-            done.put((val_label, host, event))
+            done.put((val_label, host, event, extra))
     done.put(None)
     threads[1].join()
     if writer_error:
@@ -323,6 +375,9 @@ def main(argv=None, ucf101=False):
         raise reader_error[0]
     with open(os.path.join(args.adv_path, "loss_info_{}.json".format(args.batch_index)), "w") as opt:
         json.dump(attack_method.loss_info, opt)
+    if args.quality:
+        with open(os.path.join(args.adv_path, "quality_info_{}.json".format(args.batch_index)), "w") as opt:
+            json.dump(quality_info, opt)
     threads[0].join(timeout=60)
     if cuda and __name__ == "__main__":
         del attack_method

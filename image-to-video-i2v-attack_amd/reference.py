@@ -53,14 +53,28 @@ def accuracy(output, target):
     return correct[:1].reshape(-1).float().sum(0) * (100.0 / target.size(0)), pred.reshape(-1)
 
 
+def load_clip(path, device):
+    """A saved clip on `device` as the models take it, normalised float32 (3,t,h,w).  An array saved as uint8 (t,h,w,3) -- an exported
+    clip (`image_main.py --export_u8`), the layout of `{label}-raw.npy` -- is normalised first, as the loader normalises decoded frames:
+    `Engine.clip_from_u8` on a CUDA device, the same correctly rounded fp32 operations in torch on the CPU.  Float files as they are."""
+    arr = torch.from_numpy(np.load(path))
+    if not (arr.dtype == torch.uint8 and arr.dim() == 4 and arr.shape[-1] == 3):
+        return arr.to(device)
+    if device.type == "cuda":
+        from i2v_amd import attacks as _attacks
+        return _attacks.get_engine(str(device)).clip_from_u8(arr.to(device).contiguous()[None])[0]
+    mean = torch.tensor([0.485, 0.456, 0.406], dtype=torch.float32).view(3, 1, 1, 1)
+    std = torch.tensor([0.229, 0.224, 0.225], dtype=torch.float32).view(3, 1, 1, 1)
+    return ((arr.permute(3, 0, 1, 2).to(torch.float32) / 255.0 - mean) / std).contiguous()
+
+
 def evaluate(model, adv_path, files_batch, device, clean_dir=None):
     predictions, labels, hit, seen = [], [], 0.0, 0
     with torch.no_grad():
         for batch in files_batch:
-            clips = torch.stack([torch.from_numpy(np.load(os.path.join(adv_path, f))) for f in batch]).to(device)
+            clips = torch.stack([load_clip(os.path.join(adv_path, f), device) for f in batch])
             if clean_dir:       # score against the model's own clean prediction
-                clean = torch.stack([torch.from_numpy(np.load(os.path.join(clean_dir, f.replace("adv", "ori"))))
-                                     for f in batch]).to(device)
+                clean = torch.stack([load_clip(os.path.join(clean_dir, f.replace("adv", "ori")), device) for f in batch])
                 target = model(clean).argmax(1)
             else:
                 target = torch.tensor([int(f.split("-")[0]) for f in batch], device=device)
