@@ -159,3 +159,7 @@ extern "C" int i2v_cait_attention_bwd_f32(const float* qkv, const float* probs, 
     a.wl = Wl; a.ww = Ww; a.bw = bw; a.P = const_cast<float*>(probs); a.dout = dout; a.dS = ds_scratch; a.Pm = pm_scratch; a.dqkv = dqkv;
     return cait_attention_bwd(a, (hipStream_t)stream);
 }
+
+extern "C" int i2v_cait_add_pos_f32(float* x, const float* pos, int frames, int T, int C, void* stream) {
+    return cait_add_pos(x, pos, frames, T, C, (hipStream_t)stream);
+}

@@ -134,7 +134,8 @@ inline int cait_attention_bwd(const CaitAttn& p, hipStream_t) {
 }
 
 inline int cait_add_pos(float* x, const float* pos, int F, int T, int C, hipStream_t) {
-    if (!x || !pos || F <= 0 || T <= 0 || C <= 0 || C % 4 != 0) return cait_host_refuse("cait_add_pos", "C % 4 == 0 and 16-byte alignment needed");
+    if (!x || !pos || F <= 0 || T <= 0 || C <= 0 || C % 4 != 0 || (((uintptr_t)x | (uintptr_t)pos) & 15))
+        return cait_host_refuse("cait_add_pos", "C % 4 == 0 and 16-byte alignment needed");
     for (int f = 0; f < F; ++f)
         for (int64_t i = 0; i < (int64_t)T * C; ++i) x[(int64_t)f * T * C + i] = x[(int64_t)f * T * C + i] + pos[i];
     return 0;

@@ -205,3 +205,11 @@ extern "C" int i2v_convit_attention_bwd_f32(const float* qkv, const float* probs
     a.P = const_cast<float*>(probs); a.dout = dout; a.dS = ds_scratch; a.dqkv = dqkv;
     return convit_attention_bwd(a, (hipStream_t)stream);
 }
+
+extern "C" int i2v_convit_join_cls_f32(const float* x, const float* cls, float* out, int frames, int T, int C, void* stream) {
+    return convit_join_cls(x, cls, out, frames, T, C, (hipStream_t)stream);
+}
+
+extern "C" int i2v_convit_join_cls_bwd_f32(const float* dout, const float* add, float* dx, int frames, int T, int C, void* stream) {
+    return convit_join_cls_bwd(dout, add, dx, frames, T, C, (hipStream_t)stream);
+}

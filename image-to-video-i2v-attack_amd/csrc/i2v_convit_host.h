@@ -97,8 +97,14 @@ inline int convit_attention_bwd(const ConvitAttn& p, hipStream_t) {
     return 0;
 }
 
+// what the device's join launches refuse (i2v_convit.hip, join_ok): `b` may be null
+inline int convit_host_join_ok(const void* a, const void* b, const void* c, int F, int T, int C) {
+    return a && c && F > 0 && T > 0 && C > 0 && C % 4 == 0 && (int64_t)F * (T + 1) * C < (1ll << 31) &&
+           !(((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15);
+}
+
 inline int convit_join_cls(const float* x, const float* cls, float* out, int F, int T, int C, hipStream_t) {
-    if (!x || !cls || !out || F <= 0 || T <= 0 || C <= 0 || C % 4 != 0)
+    if (!cls || !convit_host_join_ok(x, cls, out, F, T, C))
         return convit_host_refuse("convit_join_cls", "C % 4 == 0, fewer than 2^31 elements and 16-byte alignment needed");
     for (int f = 0; f < F; ++f) {
         float* o = out + (int64_t)f * (T + 1) * C;
@@ -109,7 +115,7 @@ inline int convit_join_cls(const float* x, const float* cls, float* out, int F, 
 }
 
 inline int convit_join_cls_bwd(const float* dout, const float* add, float* dx, int F, int T, int C, hipStream_t) {
-    if (!dout || !dx || F <= 0 || T <= 0 || C <= 0 || C % 4 != 0)
+    if (!convit_host_join_ok(dout, add, dx, F, T, C))
         return convit_host_refuse("convit_join_cls_bwd", "C % 4 == 0, fewer than 2^31 elements and 16-byte alignment needed");
     for (int f = 0; f < F; ++f)
         for (int64_t i = 0; i < (int64_t)T * C; ++i) {

@@ -223,6 +223,7 @@ _CAIT_PROTOS = {
     **_net_protos("cait", CaitConfig),
     "i2v_cait_attention_f32": ([_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P], _I),
     "i2v_cait_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P], _I),
+    "i2v_cait_add_pos_f32": ([_P, _P, _I, _I, _I, _P], _I),
 }
 CAIT_EXPORTS = tuple(_CAIT_PROTOS)
 
@@ -237,6 +238,8 @@ _CONVIT_PROTOS = {
     **_net_protos("convit", ConvitConfig),
     "i2v_convit_attention_f32": ([_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P], _I),
     "i2v_convit_attention_bwd_f32": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P], _I),
+    "i2v_convit_join_cls_f32": ([_P, _P, _P, _I, _I, _I, _P], _I),
+    "i2v_convit_join_cls_bwd_f32": ([_P, _P, _P, _I, _I, _I, _P], _I),
 }
 CONVIT_EXPORTS = tuple(_CONVIT_PROTOS)
 

@@ -76,6 +76,10 @@ int i2v_cait_attention_f32(const float* qkv, int frames, int T, int heads, int d
 int i2v_cait_attention_bwd_f32(const float* qkv, const float* probs, const float* dout, int frames, int T, int heads, int dh, float scale,
                                const float* Wl, const float* Ww, const float* bw, float* ds_scratch, float* pm_scratch, float* dqkv,
                                void* stream);
+/* x (frames, T, C) += pos (T, C) in place: the `+ pos_embed` launch of every stem without a prefix token (CaiT, ConViT, XCiT), one
+ * rounded add per element.  Refused with hipErrorInvalidValue: a null array, frames, T or C not positive, C no multiple of 4, x or pos not
+ * 16-byte aligned. */
+int i2v_cait_add_pos_f32(float* x, const float* pos, int frames, int T, int C, void* stream);
 
 #ifdef __cplusplus
 }

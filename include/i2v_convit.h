@@ -88,6 +88,12 @@ int i2v_convit_attention_f32(const float* qkv, int frames, int T, int heads, int
                              float* probs, float* out, void* stream);
 int i2v_convit_attention_bwd_f32(const float* qkv, const float* probs, const float* dout, int frames, int T, int heads, int dh, float scale,
                                  const float* c, const float* table, float* ds_scratch, float* dqkv, void* stream);
+/* The two launches that let the class token join the stream: out (frames, T + 1, C) = [cls (C); x (frames, T, C)] per frame, a copy; and
+ * its gradient dx (frames, T, C) = rows 1 .. T of dout (frames, T + 1, C), plus add (frames, T, C) where add is not null (one rounded add
+ * per element).  Refused with hipErrorInvalidValue: a null array (but add), frames, T or C not positive, C no multiple of
+ * 4, frames (T + 1) C of 2^31 or more, an array not 16-byte aligned. */
+int i2v_convit_join_cls_f32(const float* x, const float* cls, float* out, int frames, int T, int C, void* stream);
+int i2v_convit_join_cls_bwd_f32(const float* dout, const float* add, float* dx, int frames, int T, int C, void* stream);
 
 #ifdef __cplusplus
 }

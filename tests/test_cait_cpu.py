@@ -267,7 +267,7 @@ def test_new_native_symbols_are_exported_by_the_library_and_the_host_simulation(
     import __graft_entry__ as ge
     cd = C.CDLL(ge.LIB)
     assert all(hasattr(cd, n) for n in _lib.CAIT_EXPORTS)
-    assert {"i2v_cait_attention_f32", "i2v_cait_attention_bwd_f32", "i2v_cait_create", "i2v_cait_destroy", "i2v_cait_workspace_bytes",
+    assert {"i2v_cait_attention_f32", "i2v_cait_attention_bwd_f32", "i2v_cait_add_pos_f32", "i2v_cait_create", "i2v_cait_destroy", "i2v_cait_workspace_bytes",
             "i2v_cait_forward", "i2v_cait_backward", "i2v_cait_hook_info", "i2v_cait_read_hook"} == set(_lib.CAIT_EXPORTS)
     assert not set(_lib.CAIT_EXPORTS) & (set(_lib.EXPORTS) | set(_lib.VIT_EXPORTS) | set(_lib.SWIN_EXPORTS) | set(_lib.LOADER_EXPORTS)
                                          | set(_lib.CONVNEXT_EXPORTS) | set(_lib.MIXER_EXPORTS))

@@ -298,7 +298,7 @@ def test_new_native_symbols_are_exported_by_the_library_and_the_host_simulation(
     import __graft_entry__ as ge
     cd = C.CDLL(ge.LIB)
     assert all(hasattr(cd, n) for n in _lib.CONVIT_EXPORTS)
-    assert {"i2v_convit_attention_f32", "i2v_convit_attention_bwd_f32", "i2v_convit_create", "i2v_convit_destroy", "i2v_convit_workspace_bytes",
+    assert {"i2v_convit_attention_f32", "i2v_convit_attention_bwd_f32", "i2v_convit_join_cls_f32", "i2v_convit_join_cls_bwd_f32", "i2v_convit_create", "i2v_convit_destroy", "i2v_convit_workspace_bytes",
             "i2v_convit_forward", "i2v_convit_backward", "i2v_convit_hook_info", "i2v_convit_read_hook"} == set(_lib.CONVIT_EXPORTS)
     assert not set(_lib.CONVIT_EXPORTS) & (set(_lib.EXPORTS) | set(_lib.VIT_EXPORTS) | set(_lib.SWIN_EXPORTS) | set(_lib.LOADER_EXPORTS)
                                            | set(_lib.CONVNEXT_EXPORTS) | set(_lib.MIXER_EXPORTS) | set(_lib.CAIT_EXPORTS))
